@@ -2,7 +2,7 @@
 (BASELINE.json configs[2]/[3]) as the headline line, plus the bert-base encode leg
 (configs[1]) as a secondary object of the same JSON line.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--record FILE]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A search "step" is one pass of all 2032 queries over the whole corpus (row-sharded over the N
@@ -10,7 +10,12 @@ ranks, one RCCL all-gather of the per-shard top-80 lists, GPU merge).  Inputs ar
 generated on the device from fixed seeds and resident in HBM before the timed region.  An encode
 "step" is one batch of 512 pre-tokenised 128-token passages through the bert-base tower.
 Rank 0 prints ONE JSON line of at most ~6 KB (the driver keeps the tail of stdout): short machine keys, floats rounded to
-five significant digits, no prose.  What the keys mean:
+five significant digits, no prose.
+
+A plain run sets up, warms up, times the K search steps and prints the headline keys (metric, value, unit, ms_per_step,
+higher_is_better, dtype, config, result).  --dump-outputs DIR writes what the last timed step returned: DIR/scores.npy
+(float32 [nq, k]) and DIR/ids.npy (the int64 row ids as float64), the same for the same arguments from run to run.
+Every other key below is measured with --full only.  What the keys mean:
 
   value / ms_per_step      whole-job queries/s of the timed steps (default scan: the int8 nomination rounds + exact re-scoring)
   roofline                 dominant kernel of the timed search: the ALGORITHMIC 2 Q N d multiply-add flops over the HIP-event time
@@ -84,6 +89,12 @@ def parse():
                         "library's own RCCL communicator (proqa_sharded_search_device)")
     p.add_argument("--force-collective", action="store_true",
                    help="run the all-gather + list merge even with one rank (exercises the RCCL path on one GPU)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline: roofline, fp16 / ordinary-round scans, shard sweep, large k, "
+                        "command-line legs, measured peaks, k-means, online, CPU baseline, float32 index, encode")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed step returned (scores, ids) as DIR/<name>.npy in float32 / float64")
+    p.add_argument("--record", metavar="FILE", help="also write the unabridged record (every key of the line) to FILE")
     return p.parse_args()
 
 
@@ -128,6 +139,24 @@ def timed(fn, steps, warmup, world, device):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy of each [nq, k] result array: floats as float32, ids as float64 (exact below 2^53).  Past DUMP_BYTES in
+    all, a fixed sample of the query rows (seed 0, ascending) is written instead, its row numbers as DIR/query_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    out = {name: a.astype(np.float32 if a.dtype.kind == "f" else np.float64) for name, a in arrays.items()}
+    nq = next(iter(out.values())).shape[0]
+    per_row = sum(a[:1].nbytes for a in out.values()) + 8
+    if nq * per_row > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(nq, (DUMP_BYTES - 4096) // per_row, replace=False))   # 4 KB: headers
+        out = {name: a[rows] for name, a in out.items()}
+        out["query_rows"] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def host_cores():
@@ -933,7 +962,11 @@ def main():
 
     dt = timed(step, args.steps, args.warmup, world, device)
     qps = nq * args.steps / dt
-    # kernel-level timing for the roofline: three more searches with HIP events bracketing every
+    # what the last timed step returned, on the host before anything else runs
+    D_last, I_last = (t.cpu().numpy() for t in result["DI"])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"scores": D_last, "ids": I_last})
+    # kernel-level timing for the roofline (--full): three more searches with HIP events bracketing every
     # mips_filter launch on the search stream (kept out of the timed region: ~60 us per search)
     local = sharded.local_index
 
@@ -948,21 +981,19 @@ def main():
         st_["filter_ms"] = float(np.mean(filt))
         return st_
 
-    st = filter_ms_of_three()
+    st = filter_ms_of_three() if args.full else local.last_stats()
     import hashlib
     digest = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()   # noqa: E731
-    ids_sha, scores_sha = digest(result["DI"][1]), digest(result["DI"][0])
+    ids_sha, scores_sha = (hashlib.sha256(a.tobytes()).hexdigest() for a in (I_last, D_last))
     # roofline of the dominant kernel: ALGORITHMIC flops 2*Q*N_local*d of one search (the fp16 inner products the result is
     # made of) over the HIP-event time of its filter launches (recorded on the search stream).  When the
     # rounds ran on the int8 copy of the rows (nomination + exact re-scoring: the result is the fp16 scan's bit for bit), the
     # same flops are also priced as executed int8 operations against the int8 peak, and the fp16 scan of the same search is
     # timed beside it (fp16_scan) with its digests compared.
     flops = 2.0 * nq * (hi - lo) * D
-    filter_s = st["filter_ms"] / 1e3
-    tflops = flops / filter_s / 1e12
     nominated = bool(st.get("nomination"))
     fp16_scan = None
-    if nominated:
+    if nominated and args.full:
         local.configure_nomination("off")
         n16 = max(3, args.steps // 2)
         dt16 = timed(step, n16, 1, world, device)
@@ -977,7 +1008,7 @@ def main():
     # the same search on ordinary rounds (thresholds at the k-th best) beside the leaping ones
     # (not under --skip-extras: the profile passes of scripts/collect_profiles.sh count launches per search)
     ordinary = None
-    if st.get("leap_rank") and not args.skip_extras:
+    if st.get("leap_rank") and args.full and not args.skip_extras:
         local.configure_leap("off")
         n_ord = max(3, args.steps // 2)
         dt_ord = timed(step, n_ord, 1, world, device)
@@ -1009,21 +1040,25 @@ def main():
     # the result is made of): a secondary figure, not a fraction of the kernel's roofline.  filter_ms_per_search is the scan
     # alone; the exact re-scoring of the nominated rows runs inside the topk_merge launches and is part of
     # `chain_ms_per_search` (step - filter: bootstrap, merges incl. re-scoring, finalize, launch gaps, the host wait).
-    row_bytes_scanned = D * (1 if nominated else 2)
-    hbm_gbs = (hi - lo) * row_bytes_scanned / filter_s / 1e9
-    peak = PEAK_MFMA_I8_TOPS if nominated else PEAK_MFMA_F16_TFLOPS
-    roofline = {"bound": "mfma", "achieved": tflops, "peak": peak, "unit": "TOP/s" if nominated else "TFLOP/s",
-                "frac": tflops / peak, "traffic": pmc_traffic((hi - lo) / n, nominated),
-                "traffic_commit": pmc_traffic_commit(), "traffic_age_commits": pmc_traffic_age(),
-                "kernel": "mips_filter_i8" if nominated else "mips_filter_f16", "nomination": "int8" if nominated else None,
-                "instruction": "v_mfma_i32_32x32x32_i8" if nominated else "v_mfma_f32_32x32x16_f16",
-                "filter_ms_per_search": st["filter_ms"], "chain_ms_per_search": dt / args.steps * 1e3 - st["filter_ms"],
-                "hbm_bytes_per_row_scanned": row_bytes_scanned, "hbm_achieved_GBs": hbm_gbs}
-    if nominated:
-        roofline["fp16_equivalent_frac"] = tflops / PEAK_MFMA_F16_TFLOPS
-        roofline["nominated_per_query"] = st["nominated"] / max(nq, 1)
-        # what the exact re-scoring gathers beside the scan: one 256-byte fp16 row per nominated row (in the merges)
-        roofline["rescore_gather_bytes"] = float(st["nominated"]) * D * 2
+    roofline = None
+    if args.full:
+        filter_s = st["filter_ms"] / 1e3
+        tflops = flops / filter_s / 1e12
+        row_bytes_scanned = D * (1 if nominated else 2)
+        hbm_gbs = (hi - lo) * row_bytes_scanned / filter_s / 1e9
+        peak = PEAK_MFMA_I8_TOPS if nominated else PEAK_MFMA_F16_TFLOPS
+        roofline = {"bound": "mfma", "achieved": tflops, "peak": peak, "unit": "TOP/s" if nominated else "TFLOP/s",
+                    "frac": tflops / peak, "traffic": pmc_traffic((hi - lo) / n, nominated),
+                    "traffic_commit": pmc_traffic_commit(), "traffic_age_commits": pmc_traffic_age(),
+                    "kernel": "mips_filter_i8" if nominated else "mips_filter_f16", "nomination": "int8" if nominated else None,
+                    "instruction": "v_mfma_i32_32x32x32_i8" if nominated else "v_mfma_f32_32x32x16_f16",
+                    "filter_ms_per_search": st["filter_ms"], "chain_ms_per_search": dt / args.steps * 1e3 - st["filter_ms"],
+                    "hbm_bytes_per_row_scanned": row_bytes_scanned, "hbm_achieved_GBs": hbm_gbs}
+        if nominated:
+            roofline["fp16_equivalent_frac"] = tflops / PEAK_MFMA_F16_TFLOPS
+            roofline["nominated_per_query"] = st["nominated"] / max(nq, 1)
+            # what the exact re-scoring gathers beside the scan: one 256-byte fp16 row per nominated row (in the merges)
+            roofline["rescore_gather_bytes"] = float(st["nominated"]) * D * 2
     line = {
         "metric": "queries/sec top-80 MIPS over 18M x 128 index", "value": qps, "unit": "queries/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -1046,8 +1081,9 @@ def main():
                    "backend": dist.get_backend() if dist.is_initialized() else None,
                    "library_communicator": comm_info, "ranks": ranks},
         "result": {"ids_sha256": ids_sha[:16], "scores_sha256": scores_sha[:16]},   # first 16 hex digits of the digests
-        "roofline": roofline,
     }
+    if roofline:
+        line["roofline"] = roofline
     if fp16_scan:
         line["fp16_scan"] = fp16_scan
 
@@ -1055,10 +1091,10 @@ def main():
     # 6.9 GB of 288 at 18M rows) and searches its nq / world queries; one all-gather of the result rows, no rank merge.
     # `value` above stays the row-sharded figure BASELINE configs[3] prescribes; this is what the machine's memory allows
     # (DESIGN.md section 7).  Any failure here is reported in the object and never costs the line.
-    if world > 1 and dist.is_initialized() and not args.skip_extras:
+    if args.full and world > 1 and dist.is_initialized() and not args.skip_extras:
         line["query_shards"] = query_shards_leg(args, n, nq, k, world, rank, device, xq, ids_sha, scores_sha, digest)
 
-    if dist.is_initialized():
+    if args.full and dist.is_initialized():
         # where a sharded step goes: the rank-local search alone (max over ranks) vs the whole step with the exchange
         n_loc = max(5, args.steps // 2)
         dt_loc = timed(lambda: sharded.local_index.search_device(xq, k, idx_offset=lo), n_loc, 1, world, device)
@@ -1079,25 +1115,26 @@ def main():
         local.set_profiling(False)
         return float(np.mean(small)) / 1e3, bool(local.last_stats().get("nomination"))
 
-    small_s, small_nom = small_filter_ms()
-    row_bytes = D * (1 if small_nom else 2)          # what the scan streams per row: the int8 copy, or the fp16 rows
-    small_gbs = (hi - lo) * row_bytes / small_s / 1e9
-    # achieved = bytes the scan STREAMS per search (rows x 128 B of the int8 copy under the nomination scan, rows x 256 B
-    # of fp16 otherwise) over the HIP-event time of all filter launches of the search; fp16_rows_GBs prices the same time
-    # against the algorithmic bytes of SURVEY 8(d) (rows x 256 B): it may exceed the HBM peak, the bytes are not read
-    line["scan_small_batch"] = {
-        "queries": nq_small, "filter_ms_per_search": small_s * 1e3,
-        "roofline": {"bound": "hbm", "achieved": small_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": small_gbs / PEAK_HBM_GBS, "kernel": "mips_filter_i8<QW=1>" if small_nom else "mips_filter_f16<QW=1>",
-                     "bytes_per_row": row_bytes, "fp16_rows_GBs": (hi - lo) * D * 2 / small_s / 1e9}}
-    if small_nom:
-        local.configure_nomination("off")
-        s16, _ = small_filter_ms()
-        local.configure_nomination("auto")
-        g16 = (hi - lo) * D * 2 / s16 / 1e9
-        line["scan_small_batch"]["fp16_scan"] = {"filter_ms_per_search": s16 * 1e3, "achieved": g16, "frac": g16 / PEAK_HBM_GBS}
+    if args.full:
+        small_s, small_nom = small_filter_ms()
+        row_bytes = D * (1 if small_nom else 2)          # what the scan streams per row: the int8 copy, or the fp16 rows
+        small_gbs = (hi - lo) * row_bytes / small_s / 1e9
+        # achieved = bytes the scan STREAMS per search (rows x 128 B of the int8 copy under the nomination scan, rows x 256 B
+        # of fp16 otherwise) over the HIP-event time of all filter launches of the search; fp16_rows_GBs prices the same time
+        # against the algorithmic bytes of SURVEY 8(d) (rows x 256 B): it may exceed the HBM peak, the bytes are not read
+        line["scan_small_batch"] = {
+            "queries": nq_small, "filter_ms_per_search": small_s * 1e3,
+            "roofline": {"bound": "hbm", "achieved": small_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                         "frac": small_gbs / PEAK_HBM_GBS, "kernel": "mips_filter_i8<QW=1>" if small_nom else "mips_filter_f16<QW=1>",
+                         "bytes_per_row": row_bytes, "fp16_rows_GBs": (hi - lo) * D * 2 / small_s / 1e9}}
+        if small_nom:
+            local.configure_nomination("off")
+            s16, _ = small_filter_ms()
+            local.configure_nomination("auto")
+            g16 = (hi - lo) * D * 2 / s16 / 1e9
+            line["scan_small_batch"]["fp16_scan"] = {"filter_ms_per_search": s16 * 1e3, "achieved": g16, "frac": g16 / PEAK_HBM_GBS}
 
-    if world == 1 and not args.skip_extras:
+    if args.full and world == 1 and not args.skip_extras:
         # per-rank work of the strong-scaling runs, timed on this one GPU: the same queries over the first
         # N/G rows (G = 1, 2, 4, 8) -- what a rank of a G-GPU job does before the all-gather
         sweep = []
@@ -1154,7 +1191,7 @@ def main():
         line["online"] = online_leg(args, device, sharded.local_index, hi - lo)
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.skip_cpu:   # CPU baselines: single-GPU runs only (contract)
+    if args.full and rank == 0 and world == 1 and not args.skip_cpu:   # CPU baselines: single-GPU runs only (contract)
         # CPU baseline + id parity on a bounded sample of the same workload
         cores = host_cores()
         ns, qs = hi - lo, nq   # rank 0's whole shard: ~10 s of NumPy/BLAS work on 16 usable cores at 18M rows
@@ -1174,9 +1211,9 @@ def main():
 
     del sharded, xb
     torch.cuda.empty_cache()
-    if not args.skip_float32:
+    if args.full and not args.skip_float32:
         line["float32_index"] = float32_leg(args, device, world, rank, lo, hi)
-    if not args.skip_encode:
+    if args.full and not args.skip_encode:
         torch.cuda.empty_cache()
         enc = encode_leg(args, device, world, rank)
         line["encode"] = enc
@@ -1184,12 +1221,10 @@ def main():
     if rank == 0:
         sys.stdout.flush()
         full = json.dumps(line)
-        try:   # the unabridged record, for the builder (gpurun_out/ is scratch)
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_full.json"), "w") as f:
+        if args.record:   # the unabridged record: every key, before the printed line is compacted
+            os.makedirs(os.path.dirname(os.path.abspath(args.record)), exist_ok=True)
+            with open(args.record, "w") as f:
                 f.write(full + "\n")
-        except OSError:
-            pass
         small = compact(line)
         text = json.dumps(small, separators=(",", ":"))
         # the driver keeps the tail of stdout: should the line still outgrow LINE_BYTES, secondary detail goes first
@@ -1213,7 +1248,7 @@ LINE_TRIM_ORDER = [("encode", "cli_text_non_ascii"), ("search_cli_eval", "loader
                    ("kmeans", "cpu_baseline"), ("search_cli_eval", "host_api_search"), ("online",),
                    ("encode", "corpus_1m"), ("encode", "cli_text"), ("kmeans",), ("float32_index",), ("large_k",), ("peak_measured",)]
 MAX_STRING = 96   # longer strings are prose: they live in the docstring above / DESIGN.md, not in the line
-# keys of the unabridged record (gpurun_out/bench_full.json) that the printed line leaves out below its top level: prose,
+# keys of the unabridged record (--record FILE) that the printed line leaves out below its top level: prose,
 # restatements of the command line, intermediate timings a stage split already covers
 NESTED_DROP = {"note", "metric", "gemm_kernel_full", "host_cores", "loader_workers", "mean_tokens_per_passage", "feed_seconds", "upload_seconds",
                "loader_wait_seconds", "gpu_busy_seconds", "bytes_written_per_rank", "parity_rows", "prepare_seconds_untimed",

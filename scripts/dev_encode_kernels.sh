@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 for kv in "$@"; do export "$kv"; done
 OUT=gpurun_out/enc_kernels_$(echo "$*" | tr -c 'A-Za-z0-9=\n' '_')
 mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o enc -- python3 bench.py --skip-cpu --rows 200000 --queries 64 --steps 1 --warmup 1 --encode-steps 5 --corpus-passages 0 --cli-passages 0 --skip-extras --skip-float32 --skip-varlen > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o enc -- python3 bench.py --full --skip-cpu --rows 200000 --queries 64 --steps 1 --warmup 1 --encode-steps 5 --corpus-passages 0 --cli-passages 0 --skip-extras --skip-float32 --skip-varlen > $OUT/run.log 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/trace/**/*kernel_stats.csv", recursive=True)

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _run(gpus, extra_env=None):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--rows", "400000", "--queries", "64",
-           "--steps", "2", "--warmup", "1", "--skip-encode", "--skip-float32", "--skip-cpu", "--skip-extras"]
+           "--steps", "2", "--warmup", "1", "--full", "--skip-encode", "--skip-float32", "--skip-cpu", "--skip-extras"]
     env = dict(os.environ, **(extra_env or {}))
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
@@ -45,7 +45,7 @@ def test_two_ranks_also_time_query_shards_over_replicated_rows(gpu_device):
     """N > 1 without --skip-extras: beside the row-sharded `value` the line carries the same job with the rows replicated and
     the queries sharded (65 queries on 2 ranks: 33 + 32, the second slice padded), its result equal to the row-sharded one."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "400000", "--queries", "65", "--steps", "2",
-           "--warmup", "1", "--skip-encode", "--skip-float32", "--skip-cpu"]
+           "--warmup", "1", "--full", "--skip-encode", "--skip-float32", "--skip-cpu"]
     env = dict(os.environ, PROQA_DIST_BACKEND="gloo")
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
@@ -61,10 +61,10 @@ def test_two_ranks_also_time_query_shards_over_replicated_rows(gpu_device):
 
 
 def test_the_full_line_fits_the_drivers_tail(gpu_device):
-    """The default N = 1 run with every leg (shrunk: 1M rows, 3 steps, 20 k passages) prints one line of <= 6000 bytes that
+    """The --full N = 1 run with every leg (shrunk: 1M rows, 3 steps, 20 k passages) prints one line of <= 6000 bytes that
     still carries the headline, the roofline object, the fp16 scan beside the nomination scan, and the secondary legs."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "1000000", "--queries", "600", "--steps", "3", "--warmup", "1",
-           "--encode-steps", "2", "--corpus-passages", "4096", "--cli-passages", "4096"]
+           "--encode-steps", "2", "--corpus-passages", "4096", "--cli-passages", "4096", "--full"]
     env = dict(os.environ)
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(v, None)
@@ -89,6 +89,42 @@ def test_the_full_line_fits_the_drivers_tail(gpu_device):
                 "mfma_f16_TFLOPs_8ms_random_operands"):
         assert line["peak_measured"][key] > 100.0, key
     assert line["encode"]["gemm_kernel"]
+
+
+def test_plain_run_times_the_headline_and_dumps_its_outputs(gpu_device, tmp_path):
+    """Without --full the line carries the headline alone, `steps` timed steps of it; --dump-outputs writes the last timed
+    step's scores and ids, the same from run to run and the same as the line's digests."""
+    import hashlib
+
+    import numpy as np
+    env = dict(os.environ)
+    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(v, None)
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", "400000", "--queries", "64",
+               "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(out) == 1, p.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)})
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "queries/s" and line["higher_is_better"] is True and line["dtype"] and line["metric"]
+    assert abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) < 1e-3 * line["value"]
+    for key in ("roofline", "fp16_scan", "scan_small_batch", "shard_sweep", "cpu_baseline", "float32_index", "encode"):
+        assert key not in line, key
+    d = dumps[0]
+    assert sorted(d) == ["ids", "scores"]
+    assert d["scores"].dtype == np.float32 and d["ids"].dtype == np.float64
+    assert d["scores"].shape == d["ids"].shape == (64, 80)
+    assert hashlib.sha256(d["ids"].astype(np.int64).tobytes()).hexdigest()[:16] == line["result"]["ids_sha256"]
+    assert hashlib.sha256(d["scores"].tobytes()).hexdigest()[:16] == line["result"]["scores_sha256"]
+    assert lines[1]["result"] == line["result"]
+    for name in d:
+        np.testing.assert_array_equal(dumps[1][name], d[name])
 
 
 def test_bench_refuses_a_launcher_of_another_size(gpu_device):
