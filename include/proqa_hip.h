@@ -261,7 +261,8 @@ typedef struct proqa_bert_weights {
   const void *emb_ln_g, *emb_ln_b;
   const proqa_bert_layer* layers;              /* n_layers entries (copied by create) */
   const void *pool_w, *pool_b;                 /* pooler.dense */
-  const void *proj_w, *proj_b;                 /* proj_q / proj_c: [128, hidden], [128] */
+  const void *proj_w, *proj_b;                 /* proj_q / proj_c: [128, hidden], [128]; both NULL for a tower without a
+                                                  projection (the reader's bert: proqa_encoder_forward_hidden only) */
 } proqa_bert_weights;
 
 typedef struct proqa_encoder proqa_encoder;
@@ -299,6 +300,45 @@ int proqa_encoder_dense(proqa_encoder* enc, const void* x_dev, const void* w_dev
 int proqa_encoder_forward(proqa_encoder* enc, const int64_t* ids_dev, const int32_t* seq_lens_dev, int batch,
                           int seq_len, int64_t n_valid_tokens, int flags, void* out, int out_dtype, void* stream);
 
+/* The tower up to its last hidden state, with token-type (segment) embeddings: BertModel(input_ids, input_mask,
+ * token_type_ids) of the reader (qa/bert_retrieve_qa.py:58-62).  Every layer runs for every token (no [CLS]-only last
+ * layer); no projection.
+ *   type_ids_dev:   int64 laid out like ids_dev, or NULL = all 0 (then the table below may be NULL: weights' type_emb row 0)
+ *   type_emb_table: the full [n_types, hidden] fp16 token_type_embeddings table (ids outside [0, n_types) read row 0)
+ *   Layout is the caller's choice: flags = PROQA_ENC_PACKED (n_valid_tokens = sum of the lengths, required) writes
+ *   hidden_out packed [n_valid_tokens, hidden] (sequence b from row cu_seqlens[b], the exclusive prefix sum of seq_lens);
+ *   flags = 0 writes [batch * seq_len, hidden] (padding rows hold finite values nothing should read).  No other flag.
+ *   pooled_out: [batch, hidden] fp16 tanh pooler output (BertModel(...)[1]), or NULL.
+ * Same workspace and capture rules as proqa_encoder_forward; works on a handle created with or without a projection. */
+int proqa_encoder_forward_hidden(proqa_encoder* enc, const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                 const void* type_emb_table, int n_types, const int32_t* seq_lens_dev, int batch,
+                                 int seq_len, int64_t n_valid_tokens, int flags, void* hidden_out, void* pooled_out,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Reader head (qa/bert_retrieve_qa.py:58-77 + the span choice of qa/train_retrieve_qa.py:300-313) over the hidden
+ * states of proqa_encoder_forward_hidden, one launch for a batch of [CLS] q [SEP] p [SEP] sequences:
+ *   logit[t] = fp16(fp32(hidden[t] . qa_w[k]) + qa_b[k]), k = 0 start / 1 end  (a half-precision nn.Linear(hidden, 2))
+ *   span of sequence b = argmax over para_offset[b] <= i <= j < len(b) - 1, j - i <= max_answer_len, of
+ *     score = fp32(start[i]) + fp32(end[j])   (the paragraph mask: [para_offset, len - 1))
+ *   TIE RULE: the lowest start, then the lowest end (the reference's CPU argmax: row maxima first, then that row's end).
+ *   A sequence without a paragraph token gets start = end = -1, score = -inf (the reference raises IndexError there).
+ *   A start whose candidate scores are all -inf or NaN (fp16 logits that overflowed) is skipped; if every start is, the
+ *   sequence reports no span the same way, where the reference would still return some span.
+ * Layout: exactly one of seq_lens_dev (padded: sequence b is rows b * seq_len .., len(b) = seq_lens[b]) and cu_seqlens_dev
+ * (packed: rows cu_seqlens[b] .. cu_seqlens[b + 1], [batch + 1] int32) is non-NULL; seq_len is the padded row stride,
+ * or in the packed layout any bound on the longest sequence (<= 4096).  para_offset_dev [batch] int32.
+ * Outputs (device): start_out / end_out [batch] int32 positions within the sequence, score_out [batch] fp32, logits_out
+ * (optional) [rows, 2] fp16 (start, end) for the valid rows.  hidden and qa_w 16-byte aligned; hidden <= 1024. */
+int proqa_reader_span_f16(const void* hidden, const int32_t* seq_lens_dev, const int32_t* cu_seqlens_dev, int batch,
+                          int seq_len, int hidden_size, const int32_t* para_offset_dev, const void* qa_w, const void* qa_b,
+                          int max_answer_len, int32_t* start_out, int32_t* end_out, float* score_out, void* logits_out,
+                          void* stream);
+/* select_outputs = Linear(hidden, 1) on the pooled output (--add-select): out[b] = fp16(pooled[b] . select_w + select_b),
+ * returned as fp32 [batch] (device).  pooled [batch, hidden] and select_w [hidden] fp16, 16-byte aligned. */
+int proqa_reader_select_f16(const void* pooled, int batch, int hidden_size, const void* select_w, const void* select_b,
+                            float* out, void* stream);
+
 /* The kernels the encoder is made of, individually (tests, other drivers). */
 /* y[m,n] = epilogue(x[m,k] . w[n,k]^T + bias[n]): the encoder's dense layer as a hand-written MFMA GEMM (fp16 in, fp32
  * accumulate, fp16 out; 256 x 256 x 64 tiles, LDS-DMA ring).  epilogue 0: none (bias ignored), 1: + bias,
@@ -315,6 +355,13 @@ int proqa_embed_layernorm_f16(const int64_t* ids_dev, int64_t n_tokens, int seq_
                               const void* type_emb, const void* ln_gamma, const void* ln_beta,
                               float eps, void* out, void* stream);
 
+/* the same with token types: out[t] = LayerNorm(word[ids[t]] + pos[t % seq_len] + type_table[type_ids[t]]), type_ids int64
+ * laid out like ids (NULL = all 0; ids outside [0, n_types) read row 0); BertEmbeddings with token_type_ids */
+int proqa_embed_layernorm_typed_f16(const int64_t* ids_dev, const int64_t* type_ids_dev, int64_t n_tokens, int seq_len,
+                                    int hidden, const void* word_emb, int64_t vocab, const void* pos_emb,
+                                    const void* type_emb_table, int n_types, const void* ln_gamma, const void* ln_beta,
+                                    float eps, void* out, void* stream);
+
 /* Packed ("varlen") token layout: sequences are stored back to back without padding rows,
  * cu_seqlens[b] = first row of sequence b, cu_seqlens[batch] = total tokens (int32, device).
  * Every per-token operator is unchanged on the packed [T, hidden] matrix; only the embedding
@@ -326,6 +373,12 @@ int proqa_embed_layernorm_varlen_f16(const int64_t* ids_dev, const int32_t* cu_s
                                      int seq_len, int hidden, const void* word_emb, int64_t vocab,
                                      const void* pos_emb, const void* type_emb, const void* ln_gamma,
                                      const void* ln_beta, float eps, void* out_packed, void* stream);
+/* packed layout with token types (type_ids padded [batch, seq_len] like ids, NULL = all 0) */
+int proqa_embed_layernorm_typed_varlen_f16(const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                           const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden,
+                                           const void* word_emb, int64_t vocab, const void* pos_emb,
+                                           const void* type_emb_table, int n_types, const void* ln_gamma,
+                                           const void* ln_beta, float eps, void* out_packed, void* stream);
 
 /* fused multi-head self-attention for one layer:
  *   ctx = softmax(Q K^T / sqrt(64) + key_mask) V,   head_dim 64

@@ -27,6 +27,7 @@ SOURCES = [
     "attention_kernel.hip",
     "lt_gemm.cpp",
     "encoder.cpp",
+    "reader_kernels.hip",
     "kmeans_kernels.hip",
     "microbench.hip",
 ]

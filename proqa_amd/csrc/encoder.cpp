@@ -26,6 +26,7 @@ namespace proqa {
 int launch_cu_seqlens(const int32_t* seq_lens_dev, int batch, int32_t* cu_out, void* stream);
 int launch_small_dense(const void* x, int rows, const void* w, const void* bias, int n_feat, int k_dim, int act, void* y,
                        void* stream);
+int launch_pooler(const void* x, int batch, int hidden, const void* w_pool, const void* b_pool, void* pooled, void* stream);
 int launch_gather_rows(const void* src, int64_t src_row_stride_elems, const int32_t* row_index_dev, int64_t fixed_stride_rows,
                        int n_rows, int cols, void* dst, void* stream);
 }  // namespace proqa
@@ -206,6 +207,43 @@ int ensure_workspace(proqa_encoder* e, int batch, int64_t rows, hipStream_t st) 
   return PROQA_OK;
 }
 
+// Encoder layers [0, n_run) over the token rows in ws.h (the dense layers see `rows` rows: the tokens, possibly rounded up
+// to the GEMM tile).  Each layer leaves its output in ws.h, except that with last_out != nullptr the final LayerNorm of
+// layer n_run - 1 writes last_out instead, `last_rows` rows of it (the caller's buffer has no tile padding).
+int run_layers(proqa_encoder* e, int n_run, int64_t rows, const int32_t* lens, const int32_t* cu, int batch, int seq_len,
+               hipStream_t st, void* stream, _Float16* last_out, int64_t last_rows) {
+  const proqa_bert_weights& w = e->w;
+  const int H = w.hidden, I = w.intermediate, NH = w.n_heads;
+  const float eps = w.layer_norm_eps;
+  Workspace& ws = e->ws;
+  // the fused dense+GELU kernel wants whole 256-row tiles and enough of them to occupy every XCD
+  const bool own_ffn1 = e->own_ffn1 && rows % 256 == 0 && rows >= 64 * 256 && I % 256 == 0 && H % 64 == 0;
+  _Float16 *h = ws.h, *h1 = ws.h1;
+  for (int l = 0; l < n_run; ++l) {
+    const proqa_bert_layer& L = w.layers[l];
+    const bool to_caller = last_out && l == n_run - 1;
+    if (int rc = gemm_tn(e, h, L.qkv_w, ws.qkv, rows, 3 * H, H, st)) return rc;                       // fused Q|K|V projection
+    if (int rc = launch_attention(ws.qkv, L.qkv_b, lens, cu, batch, seq_len, NH, ws.ctx, stream)) return rc;
+    if (int rc = gemm_tn(e, ws.ctx, L.ao_w, ws.tmp, rows, H, H, st)) return rc;
+    if (int rc = proqa_bias_residual_layernorm_f16(ws.tmp, L.ao_b, h, L.ln1_g, L.ln1_b, eps, rows, H, h1, stream)) return rc;
+    if (small_dense_ok(rows, I, H)) {
+      if (int rc = launch_small_dense(h1, (int)rows, L.ff1_w, L.ff1_b, I, H, 1, ws.ff, stream)) return rc;
+    } else if (own_ffn1) {
+      // BertIntermediate as ONE launch: the hand-written GEMM adds the bias and applies the erf GELU in its epilogue
+      // (gemm_kernels.hip), which saves the 2 x rows x 3072 x 2 B round trip of a separate bias_gelu pass
+      if (int rc = proqa_gemm_tn_f16(h1, L.ff1_w, L.ff1_b, ws.ff, rows, I, H, PROQA_GEMM_EPI_BIAS_GELU, stream)) return rc;
+    } else {
+      if (int rc = gemm_tn(e, h1, L.ff1_w, ws.ff, rows, I, H, st)) return rc;
+      if (int rc = proqa_bias_gelu_f16(ws.ff, L.ff1_b, rows, I, stream)) return rc;
+    }
+    if (int rc = gemm_tn(e, ws.ff, L.ff2_w, ws.tmp, rows, H, I, st)) return rc;
+    if (int rc = proqa_bias_residual_layernorm_f16(ws.tmp, L.ff2_b, h1, L.ln2_g, L.ln2_b, eps, to_caller ? last_rows : rows, H,
+                                                   to_caller ? last_out : h, stream))
+      return rc;
+  }
+  return PROQA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -217,9 +255,11 @@ int proqa_encoder_create(const proqa_bert_weights* w, proqa_encoder** out) {
     return fail(PROQA_EINVAL, "encoder_create: hidden=%d must be n_heads*64 (head_dim 64)", w->hidden);
   if (w->n_layers <= 0 || w->intermediate <= 0 || w->intermediate % 8 || w->vocab <= 0 || w->max_position <= 0 || !w->layers)
     return fail(PROQA_EINVAL, "encoder_create: bad model geometry");
-  const void* need[] = {w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, w->pool_w, w->pool_b, w->proj_w, w->proj_b};
+  const void* need[] = {w->word_emb, w->pos_emb, w->type_emb, w->emb_ln_g, w->emb_ln_b, w->pool_w, w->pool_b};
   for (const void* p : need)
     if (!p) return fail(PROQA_EINVAL, "encoder_create: NULL weight pointer");
+  // a tower without a projection (the reader's bert: proqa_encoder_forward_hidden only) has neither pointer
+  if (!w->proj_w != !w->proj_b) return fail(PROQA_EINVAL, "encoder_create: NULL weight pointer");
   for (int l = 0; l < w->n_layers; ++l) {
     const proqa_bert_layer& L = w->layers[l];
     const void* lp[] = {L.qkv_w, L.qkv_b, L.ao_w, L.ao_b, L.ln1_g, L.ln1_b, L.ff1_w, L.ff1_b, L.ff2_w, L.ff2_b, L.ln2_g, L.ln2_b};
@@ -290,6 +330,8 @@ int proqa_encoder_forward(proqa_encoder* e, const int64_t* ids_dev, const int32_
     return fail(PROQA_EINVAL, "encoder_forward: sequence length %d exceeds max_position_embeddings %d", seq_len,
                 e->w.max_position);
   if (out_dtype != PROQA_F16 && out_dtype != PROQA_F32) return fail(PROQA_EINVAL, "encoder_forward: bad out dtype");
+  if (!e->w.proj_w)
+    return fail(PROQA_EINVAL, "encoder_forward: this encoder has no projection (proj_w = NULL); use proqa_encoder_forward_hidden");
   if (batch == 0) return PROQA_OK;
   const proqa_bert_weights& w = e->w;
   const int H = w.hidden, I = w.intermediate, NH = w.n_heads;
@@ -326,29 +368,9 @@ int proqa_encoder_forward(proqa_encoder* e, const int64_t* ids_dev, const int32_
   // hold finite stale values nothing reads back; small batches stay small)
   const int64_t rows = n > 4096 ? round_up<int64_t>(n, kRowTile) : n;
   const int32_t* lens = packed ? nullptr : seq_lens_dev;
-  // the fused dense+GELU kernel wants whole 256-row tiles and enough of them to occupy every XCD
-  const bool own_ffn1 = e->own_ffn1 && rows % 256 == 0 && rows >= 64 * 256 && I % 256 == 0 && H % 64 == 0;
-  _Float16 *h = ws.h, *h1 = ws.h1;
+  _Float16* h = ws.h;
   const int n_full = cls_only ? w.n_layers - 1 : w.n_layers;
-  for (int l = 0; l < n_full; ++l) {
-    const proqa_bert_layer& L = w.layers[l];
-    if (int rc = gemm_tn(e, h, L.qkv_w, ws.qkv, rows, 3 * H, H, st)) return rc;                       // fused Q|K|V projection
-    if (int rc = launch_attention(ws.qkv, L.qkv_b, lens, cu, batch, seq_len, NH, ws.ctx, stream)) return rc;
-    if (int rc = gemm_tn(e, ws.ctx, L.ao_w, ws.tmp, rows, H, H, st)) return rc;
-    if (int rc = proqa_bias_residual_layernorm_f16(ws.tmp, L.ao_b, h, L.ln1_g, L.ln1_b, eps, rows, H, h1, stream)) return rc;
-    if (small_dense_ok(rows, I, H)) {
-      if (int rc = launch_small_dense(h1, (int)rows, L.ff1_w, L.ff1_b, I, H, 1, ws.ff, stream)) return rc;
-    } else if (own_ffn1) {
-      // BertIntermediate as ONE launch: the hand-written GEMM adds the bias and applies the erf GELU in its epilogue
-      // (gemm_kernels.hip), which saves the 2 x rows x 3072 x 2 B round trip of a separate bias_gelu pass
-      if (int rc = proqa_gemm_tn_f16(h1, L.ff1_w, L.ff1_b, ws.ff, rows, I, H, PROQA_GEMM_EPI_BIAS_GELU, stream)) return rc;
-    } else {
-      if (int rc = gemm_tn(e, h1, L.ff1_w, ws.ff, rows, I, H, st)) return rc;
-      if (int rc = proqa_bias_gelu_f16(ws.ff, L.ff1_b, rows, I, stream)) return rc;
-    }
-    if (int rc = gemm_tn(e, ws.ff, L.ff2_w, ws.tmp, rows, H, I, st)) return rc;
-    if (int rc = proqa_bias_residual_layernorm_f16(ws.tmp, L.ff2_b, h1, L.ln2_g, L.ln2_b, eps, rows, H, h, stream)) return rc;
-  }
+  if (int rc = run_layers(e, n_full, rows, lens, cu, batch, seq_len, st, stream, nullptr, 0)) return rc;
   // h[:, 0] of every sequence -> dst [batch, H]
   auto cls_rows = [&](_Float16* dst) {
     return launch_gather_rows(h, H, cu, seq_len, batch, H, dst, stream);
@@ -376,6 +398,59 @@ int proqa_encoder_forward(proqa_encoder* e, const int64_t* ids_dev, const int32_
     if (int rc = cls_rows(ws.c_h)) return rc;
   }
   return proqa_pool_project_f16(ws.c_h, batch, 1, H, w.pool_w, w.pool_b, w.proj_w, w.proj_b, ws.pooled, out, out_dtype, stream);
+}
+
+int proqa_encoder_forward_hidden(proqa_encoder* e, const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                 const void* type_emb_table, int n_types, const int32_t* seq_lens_dev, int batch, int seq_len,
+                                 int64_t n_valid_tokens, int flags, void* hidden_out, void* pooled_out, void* stream) {
+  if (!e || (batch > 0 && (!ids_dev || !seq_lens_dev || !hidden_out)))
+    return fail(PROQA_EINVAL, "encoder_forward_hidden: NULL argument");
+  if (batch < 0 || seq_len <= 0) return fail(PROQA_EINVAL, "encoder_forward_hidden: bad sizes");
+  if (seq_len > e->w.max_position)
+    return fail(PROQA_EINVAL, "encoder_forward_hidden: sequence length %d exceeds max_position_embeddings %d", seq_len,
+                e->w.max_position);
+  if (type_ids_dev && (!type_emb_table || n_types <= 0))
+    return fail(PROQA_EINVAL, "encoder_forward_hidden: type_ids need the token-type table and its row count");
+  const bool packed = (flags & PROQA_ENC_PACKED) != 0;
+  if (packed && n_valid_tokens < 0) return fail(PROQA_EINVAL, "encoder_forward_hidden: PROQA_ENC_PACKED needs n_valid_tokens");
+  if (flags & ~PROQA_ENC_PACKED) return fail(PROQA_EINVAL, "encoder_forward_hidden: flags other than PROQA_ENC_PACKED");
+  if (batch == 0) return PROQA_OK;
+  const proqa_bert_weights& w = e->w;
+  const int H = w.hidden;
+  const float eps = w.layer_norm_eps;
+  const int64_t n_padded = (int64_t)batch * seq_len;
+  if (n_valid_tokens > n_padded) return fail(PROQA_EINVAL, "encoder_forward_hidden: n_valid_tokens exceeds batch*seq_len");
+  const void* type_table = type_ids_dev ? type_emb_table : w.type_emb;
+  const int n_type_rows = type_ids_dev ? n_types : 1;
+  PROQA_ON_DEVICE(e->device);
+  hipStream_t st = as_stream(stream);
+  if (int rc = ensure_workspace(e, batch, round_up<int64_t>(n_padded, kRowTile), st)) return rc;
+  Workspace& ws = e->ws;
+  PROQA_BLAS(rocblas_set_stream(e->blas, st));
+
+  int64_t n = n_padded;
+  const int32_t* cu = nullptr;
+  if (packed) {
+    n = n_valid_tokens;
+    if (int rc = launch_cu_seqlens(seq_lens_dev, batch, ws.cu, stream)) return rc;
+    cu = ws.cu;
+    if (int rc = proqa_embed_layernorm_typed_varlen_f16(ids_dev, type_ids_dev, cu, batch, seq_len, H, w.word_emb, w.vocab,
+                                                        w.pos_emb, type_table, n_type_rows, w.emb_ln_g, w.emb_ln_b, eps, ws.h,
+                                                        stream))
+      return rc;
+  } else {
+    if (int rc = proqa_embed_layernorm_typed_f16(ids_dev, type_ids_dev, n, seq_len, H, w.word_emb, w.vocab, w.pos_emb,
+                                                 type_table, n_type_rows, w.emb_ln_g, w.emb_ln_b, eps, ws.h, stream))
+      return rc;
+  }
+  const int64_t rows = n > 4096 ? round_up<int64_t>(n, kRowTile) : n;
+  const int32_t* lens = packed ? nullptr : seq_lens_dev;
+  // every layer for every token; the last LayerNorm writes the caller's buffer directly, its n token rows only
+  if (int rc = run_layers(e, w.n_layers, rows, lens, cu, batch, seq_len, st, stream, (_Float16*)hidden_out, n)) return rc;
+  if (!pooled_out) return PROQA_OK;
+  // BertPooler: tanh(Wp . h[:, 0] + bp) of every sequence
+  if (int rc = launch_gather_rows(hidden_out, H, cu, seq_len, batch, H, ws.c_h, stream)) return rc;
+  return launch_pooler(ws.c_h, batch, H, w.pool_w, w.pool_b, pooled_out, stream);
 }
 
 }  // extern "C"

@@ -66,14 +66,15 @@ __device__ __forceinline__ void layernorm_store(float (&x)[kMaxChunksPerLane][8]
   }
 }
 
-// BertEmbeddings: LN(word[id] + pos[s] + type[0])
+// BertEmbeddings: LN(word[id] + pos[s] + type[t]), t = type_ids[tok] (0 when type_ids is null)
 // cu_seqlens != nullptr: ids stay padded [B, seq_len] but the output is packed -- token (b, s) with
 // s < len(b) goes to row cu_seqlens[b] + s, padding positions produce nothing
 __global__ __launch_bounds__(256) void embed_layernorm(const long long* __restrict__ ids, long long n_tokens,
                                                        const int* __restrict__ cu_seqlens, int seq_len, int hidden,
                                                        const _Float16* __restrict__ word, long long vocab,
                                                        const _Float16* __restrict__ pos,
-                                                       const _Float16* __restrict__ type0,
+                                                       const _Float16* __restrict__ type_table,
+                                                       const long long* __restrict__ type_ids, int n_types,
                                                        const _Float16* __restrict__ gamma,
                                                        const _Float16* __restrict__ beta, float eps,
                                                        _Float16* __restrict__ out) {
@@ -82,6 +83,9 @@ __global__ __launch_bounds__(256) void embed_layernorm(const long long* __restri
   if (tok >= n_tokens) return;
   long long id = ids[tok];
   if (id < 0 || id >= vocab) id = 0;  // never index outside the table
+  long long tt = type_ids ? type_ids[tok] : 0;
+  if (tt < 0 || tt >= n_types) tt = 0;
+  const _Float16* type0 = type_table + tt * hidden;
   const int s = (int)(tok % seq_len);
   long long out_row = tok;
   if (cu_seqlens) {
@@ -302,6 +306,17 @@ int launch_small_dense(const void* x, int rows, const void* w, const void* bias,
   return PROQA_OK;
 }
 
+// pooled[b] = tanh(Wp . x[b] + bp), x [batch, hidden] contiguous: BertPooler alone (the reader tower has no projection)
+int launch_pooler(const void* x, int batch, int hidden, const void* w_pool, const void* b_pool, void* pooled, void* stream) {
+  if (batch == 0) return PROQA_OK;
+  if (hidden % 32) return fail(PROQA_EINVAL, "pooler: hidden=%d must be a multiple of 32", hidden);
+  hipLaunchKernelGGL((cls_dense_mfma<true, _Float16>), dim3((unsigned)ceil_div<int>(hidden, 128), (unsigned)ceil_div<int>(batch, 32)),
+                     dim3(256), 0, as_stream(stream), (const _Float16*)x, (long long)hidden, batch, (const _Float16*)w_pool,
+                     (const _Float16*)b_pool, hidden, hidden, (_Float16*)pooled, hidden);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
 int launch_gather_rows(const void* src, int64_t src_row_stride_elems, const int32_t* row_index_dev, int64_t fixed_stride_rows,
                        int n_rows, int cols, void* dst, void* stream) {
   if (n_rows == 0) return PROQA_OK;
@@ -319,11 +334,11 @@ extern "C" {
 
 static int launch_embed_layernorm(const int64_t* ids_dev, int64_t n_tokens, const int32_t* cu_seqlens_dev, int seq_len,
                                   int hidden, const void* word_emb, int64_t vocab, const void* pos_emb,
-                                  const void* type_emb, const void* ln_gamma, const void* ln_beta, float eps, void* out,
-                                  void* stream) {
+                                  const void* type_emb, const int64_t* type_ids_dev, int n_types, const void* ln_gamma,
+                                  const void* ln_beta, float eps, void* out, void* stream) {
   if (!ids_dev || !word_emb || !pos_emb || !type_emb || !ln_gamma || !ln_beta || !out)
     return fail(PROQA_EINVAL, "embed_layernorm: NULL argument");
-  if (n_tokens < 0 || seq_len <= 0 || vocab <= 0) return fail(PROQA_EINVAL, "embed_layernorm: bad sizes");
+  if (n_tokens < 0 || seq_len <= 0 || vocab <= 0 || n_types <= 0) return fail(PROQA_EINVAL, "embed_layernorm: bad sizes");
   if (hidden <= 0 || hidden % 8 || hidden > 64 * kMaxChunksPerLane * 8)
     return fail(PROQA_EINVAL, "embed_layernorm: hidden=%d must be a multiple of 8 and <= %d", hidden,
                 64 * kMaxChunksPerLane * 8);
@@ -331,7 +346,8 @@ static int launch_embed_layernorm(const int64_t* ids_dev, int64_t n_tokens, cons
   const unsigned grid = (unsigned)ceil_div<int64_t>(n_tokens, kRowsPerBlock);
   hipLaunchKernelGGL(embed_layernorm, dim3(grid), dim3(256), 0, as_stream(stream), (const long long*)ids_dev,
                      (long long)n_tokens, (const int*)cu_seqlens_dev, seq_len, hidden, (const _Float16*)word_emb,
-                     (long long)vocab, (const _Float16*)pos_emb, (const _Float16*)type_emb, (const _Float16*)ln_gamma,
+                     (long long)vocab, (const _Float16*)pos_emb, (const _Float16*)type_emb,
+                     (const long long*)type_ids_dev, n_types, (const _Float16*)ln_gamma,
                      (const _Float16*)ln_beta, eps, (_Float16*)out);
   PROQA_LAUNCH_CHECK();
   return PROQA_OK;
@@ -340,8 +356,16 @@ static int launch_embed_layernorm(const int64_t* ids_dev, int64_t n_tokens, cons
 int proqa_embed_layernorm_f16(const int64_t* ids_dev, int64_t n_tokens, int seq_len, int hidden,
                               const void* word_emb, int64_t vocab, const void* pos_emb, const void* type_emb,
                               const void* ln_gamma, const void* ln_beta, float eps, void* out, void* stream) {
-  return launch_embed_layernorm(ids_dev, n_tokens, nullptr, seq_len, hidden, word_emb, vocab, pos_emb, type_emb,
-                                ln_gamma, ln_beta, eps, out, stream);
+  return launch_embed_layernorm(ids_dev, n_tokens, nullptr, seq_len, hidden, word_emb, vocab, pos_emb, type_emb, nullptr,
+                                1, ln_gamma, ln_beta, eps, out, stream);
+}
+
+int proqa_embed_layernorm_typed_f16(const int64_t* ids_dev, const int64_t* type_ids_dev, int64_t n_tokens, int seq_len,
+                                    int hidden, const void* word_emb, int64_t vocab, const void* pos_emb,
+                                    const void* type_emb_table, int n_types, const void* ln_gamma, const void* ln_beta,
+                                    float eps, void* out, void* stream) {
+  return launch_embed_layernorm(ids_dev, n_tokens, nullptr, seq_len, hidden, word_emb, vocab, pos_emb, type_emb_table,
+                                type_ids_dev, n_types, ln_gamma, ln_beta, eps, out, stream);
 }
 
 int proqa_embed_layernorm_varlen_f16(const int64_t* ids_dev, const int32_t* cu_seqlens_dev, int batch, int seq_len,
@@ -350,7 +374,18 @@ int proqa_embed_layernorm_varlen_f16(const int64_t* ids_dev, const int32_t* cu_s
                                      void* out_packed, void* stream) {
   if (!cu_seqlens_dev || batch < 0) return fail(PROQA_EINVAL, "embed_layernorm_varlen: bad argument");
   return launch_embed_layernorm(ids_dev, (int64_t)batch * seq_len, cu_seqlens_dev, seq_len, hidden, word_emb, vocab,
-                                pos_emb, type_emb, ln_gamma, ln_beta, eps, out_packed, stream);
+                                pos_emb, type_emb, nullptr, 1, ln_gamma, ln_beta, eps, out_packed, stream);
+}
+
+int proqa_embed_layernorm_typed_varlen_f16(const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                           const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden,
+                                           const void* word_emb, int64_t vocab, const void* pos_emb,
+                                           const void* type_emb_table, int n_types, const void* ln_gamma,
+                                           const void* ln_beta, float eps, void* out_packed, void* stream) {
+  if (!cu_seqlens_dev || batch < 0) return fail(PROQA_EINVAL, "embed_layernorm_typed_varlen: bad argument");
+  return launch_embed_layernorm(ids_dev, (int64_t)batch * seq_len, cu_seqlens_dev, seq_len, hidden, word_emb, vocab,
+                                pos_emb, type_emb_table, type_ids_dev, n_types, ln_gamma, ln_beta, eps, out_packed,
+                                stream);
 }
 
 int proqa_bias_residual_layernorm_f16(const void* x, const void* bias, const void* residual, const void* gamma,

@@ -195,6 +195,15 @@ class TokenizeCollate:
         except Exception:
             return None
 
+    @property
+    def has_native(self):
+        """True when the batches go through libproqa_hip.so's own WordPiece (native_threads > 0 and a plain BERT vocabulary)."""
+        return self._native_spec is not None
+
+    def native_handle(self):
+        """(library, proqa_wordpiece handle) of the native tokenizer (created on first use); None without one."""
+        return self._native_handle() if self.has_native else None
+
     def _native_handle(self):
         if self._native is None and self._native_spec is not None:
             import ctypes

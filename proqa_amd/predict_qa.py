@@ -1,0 +1,181 @@
+"""`python train_retrieve_qa.py --do_predict ...`: the reference's open-domain QA evaluation (qa/train_retrieve_qa.py
+predict :274-401 over OnlineSampler.eval_load, qa/online_sampler.py:266-335) on MI355X.
+
+Same command line, same printed lines in the same order.  Where the reference runs one question at a time, this runs
+    1. the question tower over all questions (batches of 256),
+    2. one exact top-eval_k search of the index (the reference searches IVF-Flat, nlist 100 / nprobe 20),
+    3. pair building on the host: every retrieved passage once, all its words WordPiece'd in one native batch,
+    4. the reader over packed batches of up to --reader-batch sequences (proqa_encoder_forward_hidden +
+       proqa_reader_span_f16: the best span of each sequence comes back, never the [B, L, L] score tensor),
+    5. answer texts and the alpha sweep on the host.
+The rank score of a passage is its search score (fp32 dot product of the fp16 question embedding and the fp16 row);
+under --efficient_eval the reference rounds it to fp16.  A passage without any paragraph token gets the answer ""
+(the reference raises IndexError there).  Training (--do_train) is not part of this project.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+TRAINING_FLAGS = ("--do_train", "--train_file", "--raw-train-data", "--learning_rate", "--train_batch_size",
+                  "--num_train_epochs", "--shared-norm", "--separate", "--use-spanbert", "--fp16", "--retriever-path",
+                  "--matched-para-path", "--fix-para-encoder", "--MI", "--drop-early", "--save-all")
+
+LAST_RUN_STATS = {}
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="ProQA reader evaluation (--do_predict) on MI355X")
+    p.add_argument("--do_predict", action="store_true")
+    p.add_argument("--raw-eval-data", type=str, default="../data/nq-dev.txt")
+    p.add_argument("--init_checkpoint", type=str, default="")
+    p.add_argument("--index-path", type=str, default="retrieval/index_data/para_embed_100k.npy")
+    p.add_argument("--db-path", type=str, default="../data/nq_paras.db")
+    p.add_argument("--index2paraid", type=str, default="retrieval/index_data/idx_id.json",
+                   help="idx_id.json of the index (the reference's OnlineSampler default)")
+    p.add_argument("--eval-k", type=int, default=5)
+    p.add_argument("--max_seq_length", type=int, default=512)
+    p.add_argument("--max_query_length", type=int, default=50)
+    p.add_argument("--bert_model_name", type=str, default="bert-base-uncased")
+    p.add_argument("--do_lower_case", action="store_true", default=True)
+    p.add_argument("--efficient_eval", action="store_true",
+                   help="accepted for compatibility: the reader always runs in fp16 here")
+    p.add_argument("--regex", action="store_true")
+    p.add_argument("--add-select", action="store_true")
+    p.add_argument("--save-pred", action="store_true")
+    p.add_argument("--prefix", type=str, default="eval")
+    p.add_argument("--max_answer_len", type=int, default=20, help="ignored, as in the reference (spans of <= 10 pieces)")
+    p.add_argument("--predict_batch_size", type=int, default=100, help="ignored (the reference runs one question at a time)")
+    p.add_argument("--eval-workers", type=int, default=16, help="threads of the native WordPiece tokenizer")
+    p.add_argument("--seed", type=int, default=3)
+    p.add_argument("--output_dir", type=str, default="logs")
+    p.add_argument("--reader-batch", type=int, default=256, help="sequences per reader launch (not in the reference)")
+    return p
+
+
+def _refuse_training(argv):
+    for a in argv:
+        flag = a.split("=", 1)[0]
+        if flag in TRAINING_FLAGS:
+            raise SystemExit(f"train_retrieve_qa.py: {flag} is not supported: this project runs the reader's "
+                             "evaluation (--do_predict) only; train with the reference.")
+
+
+def load_qa(path):
+    with open(path) as f:
+        return [json.loads(line) for line in f.readlines()]
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    _refuse_training(argv)
+    args = build_parser().parse_args(argv)
+    if not args.do_predict:
+        raise SystemExit("train_retrieve_qa.py: only --do_predict is supported")
+    import torch
+    from transformers import BertTokenizer
+    from . import qa_utils as qu
+    from .datasets import TokenizeCollate
+    from .get_embed import load_bert_config
+    from .index import IndexFlatIP
+    from .reader import BertReader
+    from .utils import DocDB
+
+    t_start = time.perf_counter()
+    stats = LAST_RUN_STATS
+    stats.clear()
+    cfg = load_bert_config(args.bert_model_name)
+    tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    reader = BertReader.load(args.init_checkpoint, cfg, dev)
+    if args.add_select and not reader.add_select:
+        raise SystemExit("--add-select: the checkpoint has no select_outputs")
+    reader.add_select = bool(args.add_select)
+    qa_data = load_qa(args.raw_eval_data)
+    with open(args.index2paraid) as f:
+        index2paraid = json.load(f)
+    para_embed = np.load(args.index_path).astype("float32")
+    index = IndexFlatIP(128)
+    index.add(para_embed)
+
+    # 1 + 2: all questions through the question tower, one search
+    t0 = time.perf_counter()
+    questions = [qa["question"] for qa in qa_data]
+    q_ids = [tokenizer.encode(q, max_length=args.max_query_length, truncation=True) for q in questions]
+    collate = TokenizeCollate(tokenizer, args.max_query_length)
+    embeds = []
+    for b0 in range(0, len(questions), 256):
+        batch = collate(questions[b0:b0 + 256])
+        embeds.append(reader.retriever.get_embed({"input_ids": batch["input_ids"].to(dev),
+                                                  "input_mask": batch["input_mask"].to(dev)}, True, check_mask=False,
+                                                 seq_lens_host=batch["seq_lens"])["embed"].float())
+    q_embed = torch.cat(embeds).cpu().numpy() if embeds else np.zeros((0, 128), np.float32)
+    D, I = index.search(q_embed, args.eval_k)
+    t1 = time.perf_counter()
+
+    # 3: pair building -- every retrieved passage once
+    rows = sorted({int(r) for r in I.reshape(-1).tolist() if r >= 0})
+    with DocDB(args.db_path) as db:
+        texts = [qu.normalize(qu.normalize(db.get_doc_text(index2paraid[str(r)]))) for r in rows]
+    wp = qu.WordPieces(tokenizer, threads=args.eval_workers)
+    prepared = dict(zip(rows, qu.prepare_many(texts, wp)))
+    cls_id, sep_id = tokenizer.convert_tokens_to_ids("[CLS]"), tokenizer.convert_tokens_to_ids("[SEP]")
+    items = []      # (question index, row, rank score, ids, segments, para_offset)
+    for qi in range(len(questions)):
+        for r, d in zip(I[qi].tolist(), D[qi].tolist()):
+            if r < 0:
+                continue
+            ids, seg, po, _ = qu.build_pair(q_ids[qi], prepared[r]["piece_ids"], args.max_seq_length, cls_id, sep_id)
+            items.append((qi, r, d, ids, seg, po))
+    t2 = time.perf_counter()
+
+    # 4: the reader over packed batches
+    spans, selects = [], []
+    for b0 in range(0, len(items), args.reader_batch):
+        chunk = items[b0:b0 + args.reader_batch]
+        L = max(len(it[3]) for it in chunk)
+        ids = np.zeros((len(chunk), L), np.int64)
+        seg = np.zeros((len(chunk), L), np.int64)
+        for k, it in enumerate(chunk):
+            ids[k, :len(it[3])] = it[3]
+            seg[k, :len(it[4])] = it[4]
+        out = reader.forward({"input_ids": torch.from_numpy(ids).to(dev), "segment_ids": torch.from_numpy(seg).to(dev),
+                              "seq_lens": [len(it[3]) for it in chunk], "para_offset": [it[5] for it in chunk]})
+        spans.append(torch.stack([out["start"], out["end"], out["span_score"].view(torch.int32)], 1))
+        if out["select"] is not None:
+            selects.append(out["select"])
+    spans = torch.cat(spans).cpu().numpy() if spans else np.zeros((0, 3), np.int32)
+    selects = torch.cat(selects).cpu().numpy().tolist() if selects else None
+    t3 = time.perf_counter()
+
+    # 5: texts, grouping by question hash, alpha sweep
+    qid2results, qid2ground = {}, {}
+    scores = spans[:, 2].copy().view(np.float32).tolist()
+    for n, (qi, r, d, _, _, po) in enumerate(items):
+        p = prepared[r]
+        text = qu.answer_text(int(spans[n, 0]), int(spans[n, 1]), po, p["doc_tokens"], p["all_doc_tokens"],
+                              p["tok_to_orig_index"], args.do_lower_case)
+        qid = qu.hash_question(questions[qi])
+        qid2results.setdefault(qid, []).append({
+            "text": text, "rank_score": selects[n] if args.add_select else d,
+            "span_score": scores[n] if spans[n, 0] >= 0 else None,
+            "passage": " ".join(p["doc_tokens"]), "question": questions[qi]})
+        qid2ground[qid] = qa_data[qi]["answer"]
+    _, best = qu.alpha_sweep(qid2results, qid2ground, regex=args.regex,
+                             save_prefix=args.prefix if args.save_pred else None)
+    print(best)
+    t4 = time.perf_counter()
+    stats.update(questions=len(questions), sequences=len(items), tokens=int(sum(len(it[3]) for it in items)),
+                 startup_seconds=t0 - t_start, search_seconds=t1 - t0, pair_building_seconds=t2 - t1,
+                 reader_seconds=t3 - t2, postprocess_seconds=t4 - t3, total_seconds=t4 - t_start)
+    if os.environ.get("PROQA_STATS_JSON"):
+        with open(os.environ["PROQA_STATS_JSON"], "w") as f:
+            json.dump(stats, f)
+    return best
+
+
+if __name__ == "__main__":
+    main()

@@ -86,8 +86,9 @@ class _Tower:
                 ln2_g=w(f"{p}.output.LayerNorm.weight"), ln2_b=w(f"{p}.output.LayerNorm.bias")))
         self.pool_w = w(f"{prefix}.pooler.dense.weight")   # [H, H] (out, in): read row-wise by the kernel
         self.pool_b = w(f"{prefix}.pooler.dense.bias")
-        self.proj_w = w(f"{proj_prefix}.weight")           # [128, H]
-        self.proj_b = w(f"{proj_prefix}.bias")
+        # [128, H]; a tower without a projection (proj_prefix None: the reader's bert) passes NULL for both
+        self.proj_w = w(f"{proj_prefix}.weight") if proj_prefix else None
+        self.proj_b = w(f"{proj_prefix}.bias") if proj_prefix else None
         self._handle = None
         self._create_encoder(cfg, device)
 
@@ -104,7 +105,8 @@ class _Tower:
                               word_emb=self.word.data_ptr(), pos_emb=self.pos.data_ptr(), type_emb=self.type0.data_ptr(),
                               emb_ln_g=self.emb_g.data_ptr(), emb_ln_b=self.emb_b.data_ptr(), layers=layers,
                               pool_w=self.pool_w.data_ptr(), pool_b=self.pool_b.data_ptr(),
-                              proj_w=self.proj_w.data_ptr(), proj_b=self.proj_b.data_ptr())
+                              proj_w=self.proj_w.data_ptr() if self.proj_w is not None else None,
+                              proj_b=self.proj_b.data_ptr() if self.proj_b is not None else None)
         handle = ctypes.c_void_p()
         with torch.cuda.device(device):
             _lib.check(lib.proqa_encoder_create(ctypes.byref(bw), ctypes.byref(handle)))
@@ -166,6 +168,16 @@ class BertForRetriever:
             True: _Tower(sd, "bert_q", "proj_q", self.config, self.device),
             False: _Tower(sd, "bert_c", "proj_c", self.config, self.device),
         }
+        return self
+
+    def load_query_tower(self, state_dict, prefix="bert_q", proj_prefix="proj_q"):
+        """Only the question tower, from `prefix` / `proj_prefix` of a state dict (a reader checkpoint holds it as
+        retriever.bert_q / retriever.proj_q): get_embed(..., is_query_embed=True) works, the passage tower is not loaded."""
+        keys = tower_keys(prefix, self.config.num_hidden_layers) + [f"{proj_prefix}.weight", f"{proj_prefix}.bias"]
+        missing = [k for k in keys if k not in state_dict]
+        if missing:
+            raise RuntimeError(f"Error(s) in loading the query tower: missing keys {missing[:8]}")
+        self.towers = {True: _Tower(state_dict, prefix, proj_prefix, self.config, self.device)}
         return self
 
     def tune_gemms(self, enable=True):
