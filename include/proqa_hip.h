@@ -453,6 +453,67 @@ int proqa_kmeans_update_device(proqa_kmeans* h, const void* x_f16_dev, int64_t n
 int proqa_rand_perm(int64_t n, int64_t seed, int32_t* perm_out);
 
 /* ------------------------------------------------------------------------------------
+ * Inverted-file index.  Replaces
+ *     quantizer = faiss.IndexFlatIP(128); index = faiss.IndexIVFFlat(quantizer, 128, nlist)
+ *     index.train(x); index.add(x); index.nprobe = 20; D, I = index.search(q, k)
+ * at qa/online_sampler.py:75-79 and :274 (faiss 1.6.3 semantics, restated: DESIGN.md section 2.8).  The metric is L2,
+ * faiss' default when IndexIVFFlat is given no metric: the nprobe lists are picked by inner product with the float32
+ * centroids (the IndexFlatIP quantizer; ties to the lowest list), and inside them rows rank by squared L2 distance
+ * (D ascending; exact ties to the lowest id).  A short result ends in I = -1, D = +FLT_MAX.  Training is the caller's
+ * (proqa_kmeans_*); this handle takes the centroids.  Rows are fp16 in HBM, list-major: one copy of the rows
+ * (256 B), |x|^2 / 2 (4 B), the id of every position and the position of every id (8 B each) -- 276 B per row.
+ * Limits of this version: d = 128, 1 <= nlist <= 4096, 1 <= k <= 128, min(nprobe, nlist) <= 1024, fewer than
+ * 2^32 - 1 rows.
+ * ---------------------------------------------------------------------------------- */
+typedef struct proqa_ivf proqa_ivf;
+int proqa_ivf_create(int d, int nlist, proqa_ivf** out);
+int proqa_ivf_free(proqa_ivf* h);
+/* the float32 centroids [nlist, 128] (device); only while the index holds no rows */
+int proqa_ivf_set_centroids(proqa_ivf* h, const float* centroids_dev);
+/* float32 queries that fp16 cannot hold: rounded (allow != 0) or refused (default) */
+int proqa_ivf_allow_rounding(proqa_ivf* h, int allow);
+/* append n fp16 rows [n, 128] (device) with ids ntotal .. ntotal + n - 1.  Each row goes to the list of its largest inner
+ * product with the centroids (proqa_kmeans_assign_device; ties to the lowest list), after the list's earlier rows, in
+ * input order: several adds give the lists of one add of the concatenation.  Re-lays the index out (old and new copies
+ * side by side while it runs); waits for `stream` before it returns. */
+int proqa_ivf_add_device(proqa_ivf* h, const void* xb_f16_dev, int64_t n, void* stream);
+/* D float32 [nq, k], I int64 [nq, k] and, if ip_dev != NULL, the inner product q.x of every returned row (float32
+ * [nq, k], the bits proqa_index_search reports for that (query, row); -FLT_MAX in empty slots).  xq_dev [nq, 128]
+ * PROQA_F16, or PROQA_F32 that fp16 holds (see proqa_ivf_allow_rounding).  The result does not depend on the batch:
+ * a query gets the same bits alone.
+ * Host round trips: ONE, the per-list query counts of the coarse step (nlist + 2 words), read before the scan is laid
+ * out; the scan, merge and outputs stay on `stream`.
+ * Workspace, grown on demand and kept for later calls: nq (256 + 12 nprobe' + 4) + 20 nlist + 32 W + 8 k S bytes,
+ * nprobe' = min(nprobe, nlist), W the work items and S = sum over the lists of (queries probing it) x ceil(size / chunk),
+ * chunk <= 32768 rows: S <= nq nprobe' ceil(max list size / 4096). */
+int proqa_ivf_search_device(proqa_ivf* h, const void* xq_dev, int dtype, int64_t nq, int k, int nprobe, float* D_dev,
+                            int64_t* I_dev, float* ip_dev, void* stream);
+/* rows by original id (faiss reconstruct_batch): ids int64 [n] (device) -> out [n, 128] fp16 or float32; ids outside
+ * [0, ntotal) give zero rows */
+int proqa_ivf_reconstruct_batch_device(const proqa_ivf* h, const int64_t* ids_dev, int64_t n, void* out_dev, int out_dtype,
+                                       void* stream);
+int proqa_ivf_ntotal(const proqa_ivf* h, int64_t* out);
+/* sizes_out int64 [nlist] (host) */
+int proqa_ivf_list_sizes(const proqa_ivf* h, int64_t* sizes_out);
+/* ids_out int64 [ntotal] (host): the ids of list 0 in list order, then list 1, ... (faiss invlists->get_ids) */
+int proqa_ivf_list_ids(const proqa_ivf* h, int64_t* ids_out);
+int proqa_ivf_reset(proqa_ivf* h);
+typedef struct proqa_ivf_stats {
+  int64_t nq;             /* queries of the last search */
+  int64_t rows_scanned;   /* sum over its queries of the sizes of the probed lists */
+  int64_t partial_lists;  /* (query, probed list, chunk) lists the scan wrote */
+  int32_t nprobe;         /* lists probed per query: min(nprobe, nlist) */
+  int32_t work_items;     /* scan workgroups: (list, chunk, 32 of the list's queries) */
+  int32_t chunk_rows;     /* rows per chunk */
+  float search_ms;        /* HIP-event time of the whole search on its stream */
+  float scan_ms;          /* of the scan kernel alone */
+  int32_t reserved;
+} proqa_ivf_stats;
+/* statistics of the last proqa_ivf_search_device call on this handle (waits for it to finish); all zero when that call
+ * failed or was refused */
+int proqa_ivf_search_stats(proqa_ivf* h, proqa_ivf_stats* out);
+
+/* ------------------------------------------------------------------------------------
  * .npy index files.  Replace np.save (retrieval/get_embed.py:139) and np.load
  * (retrieval/eval_retrieval.py:99-100) for 2-D C-order '<f2' / '<f4' arrays, format v1.0,
  * header padded so that data starts at a multiple of 64 bytes.

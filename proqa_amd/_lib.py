@@ -38,6 +38,13 @@ class SearchStats(ctypes.Structure):
                 ("leap_rank", ctypes.c_int32), ("leap_state", ctypes.c_int32)]
 
 
+class IvfStats(ctypes.Structure):
+    """proqa_ivf_stats"""
+    _fields_ = [("nq", c_int64), ("rows_scanned", c_int64), ("partial_lists", c_int64), ("nprobe", ctypes.c_int32),
+                ("work_items", ctypes.c_int32), ("chunk_rows", ctypes.c_int32), ("search_ms", c_float),
+                ("scan_ms", c_float), ("reserved", ctypes.c_int32)]
+
+
 class BertLayer(ctypes.Structure):
     """proqa_bert_layer: device fp16 pointers of one encoder layer."""
     _fields_ = [(n, c_void_p) for n in ("qkv_w", "qkv_b", "ao_w", "ao_b", "ln1_g", "ln1_b", "ff1_w", "ff1_b",
@@ -144,6 +151,19 @@ SIGNATURES = {
                                                   c_void_p]),
     "proqa_kmeans_update_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "proqa_rand_perm": (c_int, [c_int64, c_int64, c_void_p]),
+    "proqa_ivf_create": (c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "proqa_ivf_free": (c_int, [c_void_p]),
+    "proqa_ivf_set_centroids": (c_int, [c_void_p, c_void_p]),
+    "proqa_ivf_allow_rounding": (c_int, [c_void_p, c_int]),
+    "proqa_ivf_add_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "proqa_ivf_search_device": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "proqa_ivf_reconstruct_batch_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "proqa_ivf_ntotal": (c_int, [c_void_p, ctypes.POINTER(c_int64)]),
+    "proqa_ivf_list_sizes": (c_int, [c_void_p, c_void_p]),
+    "proqa_ivf_list_ids": (c_int, [c_void_p, c_void_p]),
+    "proqa_ivf_reset": (c_int, [c_void_p]),
+    "proqa_ivf_search_stats": (c_int, [c_void_p, ctypes.POINTER(IvfStats)]),
     "proqa_npy_stat": (c_int, [c_char_p, ctypes.POINTER(NpyInfo)]),
     "proqa_npy_read_rows": (c_int, [c_char_p, c_int64, c_int64, c_void_p, c_size_t]),
     "proqa_npy_write": (c_int, [c_char_p, c_void_p, c_int64, c_int64, c_int]),

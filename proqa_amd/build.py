@@ -29,6 +29,8 @@ SOURCES = [
     "encoder.cpp",
     "reader_kernels.hip",
     "kmeans_kernels.hip",
+    "ivf_index.cpp",
+    "ivf_kernels.hip",
     "microbench.hip",
 ]
 

@@ -8,7 +8,8 @@ The reference searches with
 `IndexFlatIP` here keeps that shape (numpy in, numpy out) over libproqa_hip.so;
 `ShardedIndexFlatIP` row-shards the corpus over the ranks of a torch.distributed group (one
 process per GPU, RCCL over xGMI), all-gathers the per-shard (score, id) lists once and merges
-them on the GPU.  Neither class has a CPU path.
+them on the GPU.  `IndexIVFFlat` is the reference's other index, faiss.IndexIVFFlat(IndexFlatIP quantizer, d, nlist)
+with its default L2 metric (qa/online_sampler.py:75-79).  None of the classes has a CPU path.
 """
 import ctypes
 
@@ -240,6 +241,248 @@ class IndexFlatIP:
 
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
+
+
+METRIC_INNER_PRODUCT = 0   # faiss' metric constants; IndexIVFFlat offers METRIC_L2 only
+METRIC_L2 = 1
+IVF_MAX_K = 128            # kIvfMaxK of the library
+IVF_QUERY_BATCH = 4096     # queries per library call: bounds the partial lists of a search in HBM
+
+
+class IndexIVFFlat:
+    """faiss.IndexIVFFlat(quantizer, d, nlist) as the reference's qa/online_sampler.py:75-79 builds it, on MI355X.
+
+    faiss 1.6.3 semantics, restated (faiss is not installed here; nothing below is pinned against it):
+      - the metric is L2: `IndexIVFFlat(quantizer, d, nlist)` without a metric argument is METRIC_L2 (faiss source).  The
+        quantizer, an IndexFlatIP, picks the probed lists by INNER PRODUCT; inside them rows rank by squared L2 distance
+        (D ascending).  Rows of large norm win by inner product and lose by L2: the result is not an approximation of
+        the exact inner-product top k.
+      - train(x): Level1Quantizer's training, Clustering(d, nlist) with niter = 10 (the value Level1Quantizer sets),
+        max_points_per_centroid = 256, seed 1234, assignment by the quantizer's inner product = group_paras.KMeans(...,
+        spherical_metric=True).  The centroids end up in the quantizer (quantizer.ntotal == nlist).
+      - add(x): every row to the list of its largest inner product with the centroids (ties to the lowest list), after
+        the list's earlier rows, ids ntotal + i.
+      - search(xq, k): the nprobe lists of largest inner product (ties to the lowest list; probes past nlist are skipped),
+        then the k rows of smallest sum (q - x)^2 among them; exact distance ties go to the lowest id (faiss leaves it
+        unspecified).  Fewer than k probed rows: the tail is I = -1, D = +FLT_MAX (the L2 heap's neutral value).
+      - faiss computes the coarse scores in fp32 (sgemm, or its own loops below 20 queries); here they are correctly
+        rounded (double accumulation), so the two can probe different lists only where two centroid scores lie within
+        fp32 round-off of each other.
+    Rows and queries are fp16, or float32 that fp16 holds exactly (the --fp16 .npy payload, the fp16 question tower);
+    other float32 input is refused unless allow_rounding(True).  1 <= k <= 128.  No CPU path."""
+
+    def __init__(self, quantizer, d=EMBED_DIM, nlist=100, metric=METRIC_L2):
+        if not isinstance(quantizer, IndexFlatIP):
+            raise TypeError(f"IndexIVFFlat: the quantizer must be a proqa_amd.index.IndexFlatIP, got {type(quantizer).__name__}")
+        if metric != METRIC_L2:
+            raise ValueError("IndexIVFFlat: only METRIC_L2 (faiss' default) is offered")
+        if quantizer.d != int(d):
+            raise ValueError(f"IndexIVFFlat: quantizer.d={quantizer.d}, d={d}")
+        if quantizer.ntotal:
+            raise ValueError("IndexIVFFlat: the quantizer must be empty (train() puts the centroids into it)")
+        self._lib = _lib.load()
+        _lib.require_gpu()
+        self.quantizer = quantizer
+        self.d = int(d)
+        self.nlist = int(nlist)
+        self.nprobe = 1
+        self._rounding = False
+        self.centroids = None
+        handle = ctypes.c_void_p()
+        _lib.check(self._lib.proqa_ivf_create(self.d, self.nlist, ctypes.byref(handle)))
+        self._h = handle
+
+    # -- inputs ---------------------------------------------------------------------------
+    def _device(self):
+        import torch
+        return torch.device("cuda", torch.cuda.current_device())
+
+    def _rows_f16(self, x, what):
+        """CUDA fp16 [n, d] tensor of x (numpy or torch); float32 must be held exactly by fp16 unless allow_rounding."""
+        import torch
+        if not _is_torch(x):
+            x = _as_matrix(x, self.d, what)
+            if x.dtype not in (np.float16, np.float32):
+                raise TypeError(f"{what} must be float16 or float32, got {x.dtype}")
+            dev = self._device()
+            out = torch.empty((x.shape[0], self.d), dtype=torch.float16, device=dev)
+            step = 1 << 21
+            for r0 in range(0, x.shape[0], step):
+                out[r0:r0 + step] = self._to_f16(torch.from_numpy(x[r0:r0 + step]).to(dev), what)
+            return out
+        if not x.is_cuda:
+            x = x.to(self._device())
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise ValueError(f"{what} must have shape [n, {self.d}], got {tuple(x.shape)}")
+        return self._to_f16(x, what).contiguous()
+
+    def _to_f16(self, t, what):
+        import torch
+        if t.dtype == torch.float16:
+            return t
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what} must be float16 or float32, got {t.dtype}")
+        h = t.half()
+        if not self._rounding and not torch.equal(h.float(), t):
+            raise ValueError(f"{what}: float32 values that fp16 cannot hold (allow_rounding(True) rounds them)")
+        return h
+
+    # -- faiss-shaped API ---------------------------------------------------------------
+    @property
+    def is_trained(self):
+        return self.centroids is not None
+
+    @property
+    def ntotal(self):
+        n = ctypes.c_int64()
+        _lib.check(self._lib.proqa_ivf_ntotal(self._h, ctypes.byref(n)))
+        return n.value
+
+    def allow_rounding(self, allow=True):
+        """Round float32 rows and queries that fp16 cannot hold instead of refusing them (off by default)."""
+        self._rounding = bool(allow)
+        _lib.check(self._lib.proqa_ivf_allow_rounding(self._h, 1 if allow else 0))
+
+    def train(self, x):
+        from .group_paras import KMeans
+        if self.ntotal:
+            raise RuntimeError("IndexIVFFlat.train: the index holds rows (reset() first)")
+        x16 = self._rows_f16(x, "x")
+        import torch
+        with torch.cuda.device(x16.device):
+            km = KMeans(self.d, self.nlist, niter=10, max_points_per_centroid=256, seed=1234, spherical_metric=True)
+            km.train(x16)
+            self.set_centroids(km.centroids)
+
+    def add(self, x):
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.add: train() first")
+        x16 = self._rows_f16(x, "x")
+        import torch
+        with torch.cuda.device(x16.device):
+            _lib.check(self._lib.proqa_ivf_add_device(self._h, x16.data_ptr(), x16.shape[0], _lib.current_stream_ptr()))
+
+    def _check_search(self, k):
+        k = int(k)
+        if not 1 <= k <= IVF_MAX_K:
+            raise ValueError(f"IndexIVFFlat.search: k={k}; this index searches 1 <= k <= {IVF_MAX_K} "
+                             "(IndexFlatIP searches any k)")
+        if int(self.nprobe) < 1:
+            raise ValueError(f"IndexIVFFlat.search: nprobe={self.nprobe} < 1")
+        return k
+
+    def search(self, xq, k, inner_products=False):
+        """(D float32 [nq,k], I int64 [nq,k]) as numpy arrays (+ the inner products q.x when inner_products)."""
+        k = self._check_search(k)
+        if not _is_torch(xq):
+            xq = _as_matrix(xq, self.d, "xq")
+            _np_dtype_code(xq)
+            import torch
+            xq = torch.from_numpy(xq).to(self._device())
+        out = self.search_device(xq, k, inner_products=inner_products)
+        return tuple(t.cpu().numpy() for t in out)
+
+    def search_device(self, xq, k, inner_products=False):
+        """CUDA tensor in, CUDA tensors out: (D, I) or, with inner_products, (D, I, IP) -- IP [nq,k] float32 has the bits
+        IndexFlatIP reports for the same (query, row)."""
+        import torch
+        k = self._check_search(k)
+        if not self.is_trained:
+            raise RuntimeError("IndexIVFFlat.search: train() first")
+        if not xq.is_cuda:
+            raise ValueError("search_device expects a CUDA tensor")
+        xq = xq.contiguous()
+        if xq.dim() != 2 or xq.shape[1] != self.d:
+            raise ValueError(f"xq must have shape [nq, {self.d}], got {tuple(xq.shape)}")
+        code = _torch_dtype_code(xq)
+        nq = xq.shape[0]
+        D = torch.empty((nq, k), dtype=torch.float32, device=xq.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=xq.device)
+        IP = torch.empty((nq, k), dtype=torch.float32, device=xq.device) if inner_products else None
+        self._batch_stats = []       # the library's statistics of the earlier calls of this search (last_stats sums them)
+        with torch.cuda.device(xq.device):
+            for q0 in range(0, max(nq, 1), IVF_QUERY_BATCH):
+                if q0:
+                    self._batch_stats.append(self._library_stats())   # (waits for the previous call's kernels)
+                part = xq[q0:q0 + IVF_QUERY_BATCH]
+                _lib.check(self._lib.proqa_ivf_search_device(self._h, part.data_ptr(), code, part.shape[0], k, int(self.nprobe),
+                                                             D[q0:].data_ptr(), I[q0:].data_ptr(),
+                                                             IP[q0:].data_ptr() if IP is not None else None,
+                                                             _lib.current_stream_ptr()))
+        return (D, I, IP) if inner_products else (D, I)
+
+    def reconstruct_batch_device(self, ids, dtype=None):
+        """Rows by original id (as IndexFlatIP.reconstruct_batch_device): ids int64 CUDA tensor of any shape ->
+        [*ids.shape, d] of `dtype` (torch.float16 or torch.float32); ids outside the index give zero rows."""
+        import torch
+        if not ids.is_cuda or ids.dtype != torch.int64:
+            raise ValueError("reconstruct_batch_device expects an int64 CUDA tensor")
+        dtype = dtype or torch.float16
+        ids = ids.contiguous()
+        out = torch.empty(tuple(ids.shape) + (self.d,), dtype=dtype, device=ids.device)
+        with torch.cuda.device(ids.device):
+            _lib.check(self._lib.proqa_ivf_reconstruct_batch_device(self._h, ids.data_ptr(), ids.numel(), out.data_ptr(),
+                                                                    _torch_dtype_code(out), _lib.current_stream_ptr()))
+        return out
+
+    def list_sizes(self):
+        sizes = np.zeros(self.nlist, dtype=np.int64)
+        _lib.check(self._lib.proqa_ivf_list_sizes(self._h, sizes.ctypes.data))
+        return sizes
+
+    def list_ids(self):
+        """[ids of list l in list order for l in range(nlist)] (numpy int64 arrays)"""
+        ids = np.zeros(self.ntotal, dtype=np.int64)
+        _lib.check(self._lib.proqa_ivf_list_ids(self._h, ids.ctypes.data))
+        return np.split(ids, np.cumsum(self.list_sizes())[:-1])
+
+    def set_centroids(self, centroids):
+        """Use these float32 centroids [nlist, d] instead of training (they go into the quantizer too); only while the
+        index holds no rows."""
+        import torch
+        cent = torch.as_tensor(centroids, dtype=torch.float32)
+        cent = (cent if cent.is_cuda else cent.to(self._device())).contiguous()
+        if tuple(cent.shape) != (self.nlist, self.d):
+            raise ValueError(f"centroids must have shape [{self.nlist}, {self.d}], got {tuple(cent.shape)}")
+        with torch.cuda.device(cent.device):
+            _lib.check(self._lib.proqa_ivf_set_centroids(self._h, cent.data_ptr()))
+            self.quantizer.reset()
+            self.quantizer.add_device(cent)
+        self.centroids = cent
+
+    def _library_stats(self):
+        st = _lib.IvfStats()
+        _lib.check(self._lib.proqa_ivf_search_stats(self._h, ctypes.byref(st)))
+        return st
+
+    def last_stats(self):
+        """Of the last search, summed over its library calls (IVF_QUERY_BATCH queries each): queries, rows scanned (the
+        sum over the queries of their probed list sizes) and per query, lists probed per query, partial lists, scan work
+        items, the rows per chunk of the last call, and the HIP-event times (ms) of the searches and of their scans.  A
+        search that failed reports zeros."""
+        parts = list(getattr(self, "_batch_stats", [])) + [self._library_stats()]
+        nq = sum(p.nq for p in parts)
+        rows = sum(p.rows_scanned for p in parts)
+        return {"nq": nq, "rows_scanned": rows, "rows_scanned_per_query": rows / nq if nq else 0.0,
+                "lists_probed": parts[-1].nprobe, "partial_lists": sum(p.partial_lists for p in parts),
+                "work_items": sum(p.work_items for p in parts), "chunk_rows": parts[-1].chunk_rows,
+                "search_ms": sum(p.search_ms for p in parts), "scan_ms": sum(p.scan_ms for p in parts),
+                "library_calls": len(parts)}
+
+    def reset(self):
+        """Drop the rows (the centroids stay, as in faiss)."""
+        _lib.check(self._lib.proqa_ivf_reset(self._h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.proqa_ivf_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PipelinedSearcher:

@@ -6,10 +6,12 @@ with the query tower, searches k = 5000 (training, :113) or k = eval_k (:274), m
 paragraph ids through `index2paraid` and gathers `para_embed[I]` (:116-117, :277).  Its own
 commented-out alternative is the exact `IndexFlatIP` (:80-82).
 
-`OnlineRetriever` is that retrieval step on `proqa_amd.index.IndexFlatIP`: exact instead of
-approximate (a superset in quality of the IVF probe; over 18M rows 0.87 ms per question at k <= 80, 1.1 ms
-at k = 5000), same outputs.  The sampler's span matching / batching is training code and is not rebuilt here.
-No CPU path.
+`OnlineRetriever` is that retrieval step, by default on `proqa_amd.index.IndexFlatIP`: the exact inner-product top k
+(over 18M rows 0.87 ms per question at k <= 80, 1.1 ms at k = 5000), same outputs.  That is NOT the reference's result:
+`IndexIVFFlat(quantizer, 128, 100)` has no metric argument, so faiss ranks the rows of the probed lists by L2 distance,
+and rows of large norm that win by inner product lose there.  `index=proqa_amd.index.IndexIVFFlat` (trained and filled,
+nprobe set) retrieves as the reference does, for k <= 128 (eval_k; the sampler's k = 5000 is training).  The sampler's
+span matching / batching is training code and is not rebuilt here.  No CPU path.
 """
 import numpy as np
 import torch
@@ -80,8 +82,8 @@ class OnlineRetriever:
         index2paraid: the idx_id.json mapping {"<row>": paragraph id} (the reference's format), a row-ordered
         sequence of paragraph ids (ten times cheaper per lookup: at k = 5000 the dict route costs ~3 ms per question,
         more than the encode and the search together), or None.
-        index: an IndexFlatIP that already holds the rows in HBM (then para_embed may be None or just a dtype: the
-        rows the sampler gathers come from the index's copy either way)."""
+        index: an IndexFlatIP or an IndexIVFFlat that already holds the rows in HBM (then para_embed may be None or just a
+        dtype: the rows the sampler gathers come from the index's copy either way)."""
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if index is not None:
             self.index = index

@@ -3,13 +3,16 @@ predict :274-401 over OnlineSampler.eval_load, qa/online_sampler.py:266-335) on 
 
 Same command line, same printed lines in the same order.  Where the reference runs one question at a time, this runs
     1. the question tower over all questions (batches of 256),
-    2. one exact top-eval_k search of the index (the reference searches IVF-Flat, nlist 100 / nprobe 20),
+    2. one top-eval_k search of the index: exact inner product by default (--search exact), or the reference's own
+       IVF-Flat (--search ivf: nlist 100 / nprobe 20, L2 inside the probed lists, qa/online_sampler.py:75-79),
     3. pair building on the host: every retrieved passage once, all its words WordPiece'd in one native batch,
     4. the reader over packed batches of up to --reader-batch sequences (proqa_encoder_forward_hidden +
        proqa_reader_span_f16: the best span of each sequence comes back, never the [B, L, L] score tensor),
     5. answer texts and the alpha sweep on the host.
-The rank score of a passage is its search score (fp32 dot product of the fp16 question embedding and the fp16 row);
-under --efficient_eval the reference rounds it to fp16.  A passage without any paragraph token gets the answer ""
+The rank score of a passage is its fp32 dot product with the fp16 question embedding (the search score of the exact
+index; under --search ivf the inner product the IVF search returns beside its L2 distance, as the reference's rank_logits
+is q . para_embed of the gathered rows, qa/bert_retrieve_qa.py:76); under --efficient_eval the reference rounds it to
+fp16.  A passage without any paragraph token gets the answer ""
 (the reference raises IndexError there).  Training (--do_train) is not part of this project.
 """
 import argparse
@@ -53,7 +56,25 @@ def build_parser():
     p.add_argument("--seed", type=int, default=3)
     p.add_argument("--output_dir", type=str, default="logs")
     p.add_argument("--reader-batch", type=int, default=256, help="sequences per reader launch (not in the reference)")
+    p.add_argument("--search", choices=("exact", "ivf"), default="exact",
+                   help="exact inner-product search (default), or the reference's IndexIVFFlat (L2 lists behind an "
+                        "inner-product quantizer, qa/online_sampler.py:75-79; not in the reference's command line)")
+    p.add_argument("--nlist", type=int, default=100, help="--search ivf: inverted lists (the reference's 100)")
+    p.add_argument("--nprobe", type=int, default=20, help="--search ivf: lists probed per question (the reference's 20)")
     return p
+
+
+def check_search_args(args):
+    """Refuses --search ivf settings the index cannot run, before any GPU work."""
+    if args.search != "ivf":
+        return
+    from .index import IVF_MAX_K
+    if not 1 <= args.eval_k <= IVF_MAX_K:
+        raise SystemExit(f"--search ivf: --eval-k {args.eval_k} outside [1, {IVF_MAX_K}] (--search exact takes any k)")
+    if args.nprobe < 1:
+        raise SystemExit(f"--search ivf: --nprobe {args.nprobe} < 1")
+    if args.nlist < 1:
+        raise SystemExit(f"--search ivf: --nlist {args.nlist} < 1")
 
 
 def _refuse_training(argv):
@@ -75,12 +96,13 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if not args.do_predict:
         raise SystemExit("train_retrieve_qa.py: only --do_predict is supported")
+    check_search_args(args)
     import torch
     from transformers import BertTokenizer
     from . import qa_utils as qu
     from .datasets import TokenizeCollate
     from .get_embed import load_bert_config
-    from .index import IndexFlatIP
+    from .index import IndexFlatIP, IndexIVFFlat
     from .reader import BertReader
     from .utils import DocDB
 
@@ -98,8 +120,25 @@ def main(argv=None):
     with open(args.index2paraid) as f:
         index2paraid = json.load(f)
     para_embed = np.load(args.index_path).astype("float32")
-    index = IndexFlatIP(128)
-    index.add(para_embed)
+    if args.search == "ivf":
+        # qa/online_sampler.py:75-79, and no IndexFlatIP of the rows beside it
+        rows16 = torch.from_numpy(para_embed).to(dev)
+        rows16 = rows16.half() if torch.equal(rows16.half().float(), rows16) else rows16
+        del para_embed
+        index = IndexIVFFlat(IndexFlatIP(128), 128, args.nlist)
+        t_ivf = time.perf_counter()
+        index.train(rows16)
+        torch.cuda.synchronize()
+        stats["ivf_train_seconds"] = time.perf_counter() - t_ivf
+        t_ivf = time.perf_counter()
+        index.add(rows16)
+        torch.cuda.synchronize()
+        stats["ivf_add_seconds"] = time.perf_counter() - t_ivf
+        index.nprobe = args.nprobe
+        del rows16
+    else:
+        index = IndexFlatIP(128)
+        index.add(para_embed)
 
     # 1 + 2: all questions through the question tower, one search
     t0 = time.perf_counter()
@@ -113,7 +152,13 @@ def main(argv=None):
                                                   "input_mask": batch["input_mask"].to(dev)}, True, check_mask=False,
                                                  seq_lens_host=batch["seq_lens"])["embed"].float())
     q_embed = torch.cat(embeds).cpu().numpy() if embeds else np.zeros((0, 128), np.float32)
-    D, I = index.search(q_embed, args.eval_k)
+    if args.search == "ivf":
+        t_ivf = time.perf_counter()
+        _, I, D = index.search(q_embed, args.eval_k, inner_products=True)     # D: the rank score q . x
+        stats["ivf_search_seconds"] = time.perf_counter() - t_ivf
+        stats["ivf_search_stats"] = index.last_stats()
+    else:
+        D, I = index.search(q_embed, args.eval_k)
     t1 = time.perf_counter()
 
     # 3: pair building -- every retrieved passage once
