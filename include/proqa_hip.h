@@ -30,6 +30,8 @@
 extern "C" {
 #endif
 
+/* proqa_inbatch_eval_f16 was added WITHOUT a bump: it is purely additive (no existing symbol, struct or meaning changed),
+ * and a caller that needs it finds out by looking the symbol up. */
 #define PROQA_ABI_VERSION 7
 
 /* element types of embedding matrices (the .npy index is '<f2' under --fp16, else '<f4':
@@ -512,6 +514,31 @@ typedef struct proqa_ivf_stats {
 /* statistics of the last proqa_ivf_search_device call on this handle (waits for it to finish); all zero when that call
  * failed or was refused */
 int proqa_ivf_search_stats(proqa_ivf* h, proqa_ivf_stats* out);
+
+/* ------------------------------------------------------------------------------------
+ * In-batch scoring: the retriever's dev metric and the forward value of its training objective.  Replaces
+ *     product = torch.mm(q, c.t()); product.argmax(-1) == target; CrossEntropyLoss(product, target)
+ * at retrieval/train_retriever.py:203-205 and :318-323 without forming the [nq, nc] product.
+ * q [nq, 128], c [nc, 128] fp16 row-major (device, 16-byte aligned); dim must be 128.  target int32 [nq] (device): the gold
+ * column of every row; NULL means target[i] = i and needs nq <= nc.  With s[i, j] the fp32-accumulated dot product (the
+ * bits proqa_index_search reports for that pair), per row i, each output (device, [nq]) optional (NULL):
+ *   argmax_out  the lowest j among the greatest scores (torch's product.argmax(-1) on the CPU path)
+ *   max_out     max_j s[i, j]
+ *   gold_out    s[i, target[i]]
+ *   rank_out    #{j : s[i, j] > gold} + #{j < target[i] : s[i, j] == gold}; 0 = correct
+ *   lse_out     log sum_j exp(s[i, j]), the maximum subtracted as torch.logsumexp does; lse - gold is the row's
+ *               CrossEntropyLoss
+ * Non-finite scores follow torch: a NaN is greater than every number (and equal to another NaN), the first NaN wins the
+ * argmax, and such a row has max = lse = NaN; a row holding +inf has lse = +inf, a row of -inf has lse = -inf.  A
+ * target[i] outside [0, nc) gives gold = NaN and rank = -1 for that row.  nq == 0 succeeds and does nothing; nc == 0 with
+ * nq > 0 is refused, and so are more than 2^24 rows on either side.  Enqueued on `stream`, no host synchronisation.
+ * Small nq splits the columns over several workgroups per row tile through a per-device workspace (640 KiB) allocated
+ * by the first such call and kept: no allocation afterwards.  Such calls of one device are ordered on the device: a
+ * call on another stream than the previous one makes its stream wait (hipStreamWaitEvent) for that call's last kernel.
+ * ---------------------------------------------------------------------------------- */
+int proqa_inbatch_eval_f16(const void* q, const void* c, const int32_t* target, int nq, int nc, int dim,
+                           int32_t* argmax_out, int32_t* rank_out, float* max_out, float* gold_out, float* lse_out,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------
  * .npy index files.  Replace np.save (retrieval/get_embed.py:139) and np.load

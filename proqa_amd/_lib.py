@@ -120,6 +120,8 @@ SIGNATURES = {
     "proqa_reader_span_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "proqa_reader_select_f16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "proqa_inbatch_eval_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
     "proqa_embed_layernorm_typed_f16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p,
                                                 c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     "proqa_embed_layernorm_typed_varlen_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64,

@@ -28,6 +28,7 @@ SOURCES = [
     "lt_gemm.cpp",
     "encoder.cpp",
     "reader_kernels.hip",
+    "inbatch_kernels.hip",
     "kmeans_kernels.hip",
     "ivf_index.cpp",
     "ivf_kernels.hip",

@@ -1,7 +1,8 @@
-"""Inference dataset + collate of the encode path.
+"""Inference datasets + collates of the encode path and of the retriever's dev evaluation.
 
 Mirrors /root/reference/retrieval/datasets.py: collate_tokens (:29-45), EmDataset (:257-295),
-em_collate (:298-305).  Tokenisation is transformers' BertTokenizer, exactly as in the reference.
+em_collate (:298-305), ReDataset (:153-209), re_collate (:231-240).  Tokenisation is transformers' BertTokenizer, exactly
+as in the reference.
 
 `EmDataset` + `em_collate` are the reference's per-item shapes.  `get_embed.py` feeds the GPU through `EmTextView` +
 `TokenizeCollate` instead: the same ids and masks (checked against the per-item path and the reference's golden batches in
@@ -382,3 +383,86 @@ class TextBatchLoader:
                 yield item
         finally:
             stop.set()
+
+
+class ReDataset(Dataset):
+    """JSON-lines file of {'Question', 'Paragraph'[, 'Answer']} -> the (question, paragraph) pairs of the retriever's
+    in-batch objective (retrieval/datasets.py:153-209): item i is {'input_ids_q', 'input_mask_q', 'input_ids_c',
+    'input_mask_c'}, the question truncated to max_query_length and the paragraph to max_length - max_query_length
+    (both counts include [CLS] and [SEP]; truncation as in EmDataset).  filter=True keeps the items filter_sample
+    accepts; group_indexs are the three strided index groups ReSampler shuffles."""
+
+    def __init__(self, tokenizer, data_path, max_query_length, max_length, filter=False):
+        super().__init__()
+        self.tokenizer = tokenizer
+        self.filter = filter
+        print(f"Loading data from {data_path}")
+        with open(data_path) as f:
+            self.data = [json.loads(line) for line in f.readlines()]
+        original_count = len(self.data)
+        if self.filter:
+            self.data = [item for item in self.data if self.filter_sample(item)]
+            print(f"Using {len(self.data)} out of {original_count}")
+        self.max_query_length = max_query_length
+        self.max_length = max_length
+        num_group = 3
+        indexs = list(range(len(self.data)))
+        self.group_indexs = [indexs[i::num_group] for i in range(num_group)]
+
+    def filter_sample(self, item):
+        from .qa_utils import normalize_answer
+        if len(item["Paragraph"].split()) < 20:
+            return False
+        if normalize_answer(item["Answer"]) in normalize_answer(item["Question"]):
+            return False
+        return True
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, index):
+        sample = self.data[index]
+        question_ids = torch.LongTensor(self.tokenizer.encode(
+            sample["Question"], max_length=self.max_query_length, truncation=True))
+        paragraph_ids = torch.LongTensor(self.tokenizer.encode(
+            sample["Paragraph"], max_length=self.max_length - self.max_query_length, truncation=True))
+        return {"input_ids_q": question_ids, "input_mask_q": torch.ones(question_ids.shape).bool(),
+                "input_ids_c": paragraph_ids, "input_mask_c": torch.ones(paragraph_ids.shape).bool()}
+
+
+def re_collate(samples):
+    if len(samples) == 0:
+        return {}
+    return {k: collate_tokens([s[k] for s in samples], 0)
+            for k in ("input_ids_q", "input_mask_q", "input_ids_c", "input_mask_c")}
+
+
+class ReTextView(Dataset):
+    """The (Question, Paragraph) strings of a ReDataset, untokenised: item i is what ReDataset.__getitem__(i) encodes."""
+
+    def __init__(self, dataset):
+        self.data = dataset.data
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, index):
+        sample = self.data[index]
+        return sample["Question"], sample["Paragraph"]
+
+
+class ReTokenizeCollate:
+    """collate_fn over (question, paragraph) string pairs: == re_collate([ReDataset[i] ...]) plus the host lists
+    'seq_lens_q' / 'seq_lens_c', through one TokenizeCollate per side (native WordPiece where it applies)."""
+
+    def __init__(self, tokenizer, max_query_length, max_length, parallel=False, native_threads=0):
+        self.q = TokenizeCollate(tokenizer, max_query_length, parallel=parallel, native_threads=native_threads)
+        self.c = TokenizeCollate(tokenizer, max_length - max_query_length, parallel=parallel, native_threads=native_threads)
+
+    def __call__(self, pairs):
+        if len(pairs) == 0:
+            return {}
+        q = self.q([p[0] for p in pairs])
+        c = self.c([p[1] for p in pairs])
+        return {"input_ids_q": q["input_ids"], "input_mask_q": q["input_mask"], "input_ids_c": c["input_ids"],
+                "input_mask_c": c["input_mask"], "seq_lens_q": q["seq_lens"], "seq_lens_c": c["seq_lens"]}

@@ -4,6 +4,7 @@ Mirrors /root/reference/retrieval/retriever.py (BertForRetriever :10-20, get_emb
 
     model.get_embed({'input_ids': LongTensor[B,L], 'input_mask': BoolTensor[B,L]}, is_query_embed)
         -> {'embed': Tensor[B,128]}
+    model({'input_ids_q', 'input_mask_q', 'input_ids_c', 'input_mask_c'}) -> {'q': Tensor[B,128], 'c': Tensor[B,128]}
 
 Each tower is BertModel (embeddings, N x BertLayer, pooler) followed by Linear(hidden, 128) on
 the pooled [CLS] vector.  The whole tower runs inside libproqa_hip.so (`proqa_encoder_forward`):
@@ -231,8 +232,15 @@ class BertForRetriever:
         self.out_dtype = torch.float32
         return self
 
-    def __call__(self, batch):
-        raise NotImplementedError("training forward (retriever.py:22-31) is outside the encode/search hot path")
+    @torch.no_grad()
+    def __call__(self, batch, check_mask=True, seq_lens_q=None, seq_lens_c=None):
+        """The reference's forward (retriever.py:22-31) without gradients: both towers over one collated batch of
+        re_collate -> {'q': [B, 128], 'c': [B, 128]}, the rows get_embed gives for the same ids and masks.  seq_lens_* /
+        check_mask as in get_embed."""
+        return {"q": self.encode(batch["input_ids_q"], batch["input_mask_q"], True, check_mask=check_mask,
+                                 seq_lens_host=seq_lens_q),
+                "c": self.encode(batch["input_ids_c"], batch["input_mask_c"], False, check_mask=check_mask,
+                                 seq_lens_host=seq_lens_c)}
 
     @torch.no_grad()
     def get_embed(self, batch, is_query_embed, check_mask=True, seq_lens_host=None):
