@@ -23,7 +23,6 @@
 //   * the K-steps of consecutive output tiles form ONE prefetch stream (two steps ahead), across the epilogues.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "common.h"
 
@@ -69,22 +68,10 @@ __device__ __forceinline__ void lds_wait(f16x8 (&fa)[4], f16x8 (&fb)[2]) {
 // Abramowitz & Stegun 7.1.26 loses the tail and needs a reciprocal on top).  Beyond a = 6 (Phi(-6) = 1e-9) a is clamped in
 // both factors: the correction is below the fp16 resolution of x, and of 0.  9 plain VALU operations + one exp2 per
 // element where libdevice's erff costs ~40; coefficients from scripts/dev_gelu_fit.py.
-__device__ __forceinline__ float gelu_erf(float x) {
-  const float a = __builtin_fminf(__builtin_fabsf(x), 6.0f);
-  float q = __builtin_fmaf(2.299005791428499e-05f, a, -0.000611100229434669f);
-  q = __builtin_fmaf(q, a, 0.007195569109171629f);
-  q = __builtin_fmaf(q, a, -0.05118535831570625f);
-  q = __builtin_fmaf(q, a, -0.46127188205718994f);
-  q = __builtin_fmaf(q, a, -1.1501742601394653f);
-  q = __builtin_fmaf(q, a, -1.000064730644226f);
-  const float u = __builtin_amdgcn_exp2f(q);                   // Phi(-a)
-  return __builtin_fmaf(-a, u, __builtin_fmaxf(x, 0.0f));
-}
-
-// The same on packed fp32 (v_pk_fma_f32 / v_pk_add_f32: two elements per instruction at the scalar forms' rate): the seven
+//
+// Evaluated on packed fp32 (v_pk_fma_f32 / v_pk_add_f32: two elements per instruction at the scalar forms' rate): the seven
 // fused multiply-adds and the bias add of an element pair become eight instructions instead of sixteen (~1200 instead of
-// ~1600 VALU instructions per wave and 256 x 256 tile).  Same operations in the same order per element: bit-identical to
-// gelu_erf.
+// ~1600 VALU instructions per wave and 256 x 256 tile).
 typedef float f32x4e __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f32x4e splat4(float v) { return f32x4e{v, v, v, v}; }
 // FOUR elements per call: every Horner step is applied to all four before the next one, i.e. two independent v_pk_fma_f32
@@ -92,7 +79,7 @@ __device__ __forceinline__ f32x4e splat4(float v) { return f32x4e{v, v, v, v}; }
 // instructions through one register pair back to back (the kernel sits at 252 VGPRs) and the epilogue stayed latency-bound:
 // packed arithmetic alone measured -1 % (ABLATIONS R6.7).
 // Written in an = -a = max(-|x|, -6) (one v_max_f32 with source modifiers): the Horner steps of q alternate in sign -- every
-// odd intermediate is the exact negative of gelu_erf's, fused multiply-adds round symmetrically -- and the last step is
+// odd intermediate is the exact negative of the Horner form in a, fused multiply-adds round symmetrically -- and the last step is
 // fma(an, u, m) without a negation (hipcc turns a negated four-vector into 128 v_xor_b32 per tile).
 __device__ __forceinline__ f32x4e gelu_erf4(f32x4e x) {
   f32x4e an;
@@ -130,7 +117,7 @@ __device__ __forceinline__ f32x4e gelu_erf4(f32x4e x) {
 // that data start in phase 3, one barrier later for X and two for Y.  Barriers are raw s_barrier (no vmcnt drain).
 //   At the end of an output tile X takes one extra barrier (the groups fall in step), both run the epilogue at the same
 // time, then Y takes one extra barrier (anti-phase again).
-template <int EPI, int DBG = 0, bool PK = true>   // PK: packed-fp32 epilogue arithmetic (false: the scalar form, developer A/B).  DBG (timing experiments, wrong results): bit 0 = no fragment reads after the first step, bit 1 = no DMA after the prologue, bit 2 = no epilogue, bit 3 = every DMA from the same 64 KiB
+template <int EPI>
 __global__ __launch_bounds__(kWaves * 64) void gemm_tn_f16(const _Float16* __restrict__ X, const _Float16* __restrict__ W,
                                                              const _Float16* __restrict__ bias, _Float16* __restrict__ Y,
                                                              int M, int N, int K) {
@@ -176,8 +163,7 @@ __global__ __launch_bounds__(kWaves * 64) void gemm_tn_f16(const _Float16* __res
   };
   // region 0: A0 rows, 1: B0 rows, 2: A1 rows, 3: B1 rows of K-step `step` of the tile at (wbase, xbase) into ring buffer `buf`
   auto issue_region = [&](int region, const char* wbase, const char* xbase, int step, int buf) {
-    const long long koff = (DBG & 8) ? 0 : (long long)step * kRowB;   // DBG 8: every DMA re-reads the same 64 KiB (L2 hits)
-    if (DBG & 8) { wbase = (const char*)W; xbase = (const char*)X; }
+    const long long koff = (long long)step * kRowB;
     const int bo = buf * 2 * kOpBytes;
     if (region == 0) {
 #pragma unroll
@@ -315,33 +301,33 @@ __global__ __launch_bounds__(kWaves * 64) void gemm_tn_f16(const _Float16* __res
         __builtin_amdgcn_s_setprio(0);
       };
       // ---- phase 0: A0, DMA B0 rows of step + 2 (their last reader was phase 3 of the previous step) -> (A0, B0)
-      if (!(DBG & 1) || step == 0) read_a(fa, 0, buf);
-      if (pf_valid && !(DBG & 2)) issue_region(1, pf_w, pf_x, pf_step, pf_buf);
+      read_a(fa, 0, buf);
+      if (pf_valid) issue_region(1, pf_w, pf_x, pf_step, pf_buf);
       PP_END_LOAD();
       quadrant(fa, fb0, 0, 0);
       PP_END_COMPUTE();
       // ---- phase 1: B1, DMA A0 rows of step + 2 -> (A0, B1)
-      if (!(DBG & 1) || step == 0) read_b(fb1, 1, buf);
-      if (pf_valid && !(DBG & 2)) issue_region(0, pf_w, pf_x, pf_step, pf_buf);
+      read_b(fb1, 1, buf);
+      if (pf_valid) issue_region(0, pf_w, pf_x, pf_step, pf_buf);
       PP_END_LOAD();
       quadrant(fa, fb1, 0, 1);
       PP_END_COMPUTE();
       // ---- phase 2: A1, retire the DMAs of step + 1 (4 younger ones stay in flight), DMA B1 rows of step + 2 -> (A1, B1)
-      if (!(DBG & 1) || step == 0) read_a(fa, 1, buf);
+      read_a(fa, 1, buf);
       if (!pf_valid)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else if (after_epilogue)
         asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
       else
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      if (pf_valid && !(DBG & 2)) issue_region(3, pf_w, pf_x, pf_step, pf_buf);
+      if (pf_valid) issue_region(3, pf_w, pf_x, pf_step, pf_buf);
       PP_END_LOAD();
       quadrant(fa, fb1, 1, 1);
       PP_END_COMPUTE();
       // ---- phase 3: B0 of the next step, DMA A1 rows of step + 2 -> (A1, B0)
-      if (!last_of_all && (!(DBG & 1) || step == 0)) read_b(fb0n, 0, buf ^ 1);
+      if (!last_of_all) read_b(fb0n, 0, buf ^ 1);
       if (pf_valid) {
-        if (!(DBG & 2)) issue_region(2, pf_w, pf_x, pf_step, pf_buf);
+        issue_region(2, pf_w, pf_x, pf_step, pf_buf);
         pf_advance();
       }
       PP_END_LOAD();
@@ -362,16 +348,6 @@ __global__ __launch_bounds__(kWaves * 64) void gemm_tn_f16(const _Float16* __res
     char* stage = lds + 2 * 2 * kOpBytes + wave * 4096;
     const int wr_sw = (li >> 1) & 7;
     const int rd_row = lane >> 3, rd_q = lane & 7;
-    if (DBG & 4) {   // keep the accumulators alive with one store
-      float z = 0.f;
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) z += acc[a][b][e];
-      if (z == 123.456f) Y[tid] = (_Float16)z;
-    } else {
     // the lane's 2 x 32 bias values, requested before anything is stored: a load issued between the stores of the two
     // 64-feature blocks would wait for the first block's stores (vmcnt retires in order)
     f16x8 bias8[2][4];
@@ -399,28 +375,18 @@ __global__ __launch_bounds__(kWaves * 64) void gemm_tn_f16(const _Float16* __res
 #pragma unroll
           for (int c = 0; c < 2; ++c) {
             f16x8 o;
-            if constexpr (PK) {   // packed fp32, four elements side by side
 #pragma unroll
-              for (int e0 = 0; e0 < 8; e0 += 4) {
-                f32x4e x, b4;
+            for (int e0 = 0; e0 < 8; e0 += 4) {   // packed fp32, four elements side by side
+              f32x4e x, b4;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                  x[e] = v[8 * c + e0 + e];
-                  b4[e] = EPI != EPI_NONE ? bv[16 * j + 8 * c + e0 + e] : 0.f;
-                }
-                if (EPI != EPI_NONE) x += b4;
-                if (EPI == EPI_BIAS_GELU) x = gelu_erf4(x);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e0 + e] = (_Float16)x[e];
+              for (int e = 0; e < 4; ++e) {
+                x[e] = v[8 * c + e0 + e];
+                b4[e] = EPI != EPI_NONE ? bv[16 * j + 8 * c + e0 + e] : 0.f;
               }
-            } else {
+              if (EPI != EPI_NONE) x += b4;
+              if (EPI == EPI_BIAS_GELU) x = gelu_erf4(x);
 #pragma unroll
-              for (int e = 0; e < 8; ++e) {
-                float x = v[8 * c + e];
-                if (EPI != EPI_NONE) x += bv[16 * j + 8 * c + e];
-                if (EPI == EPI_BIAS_GELU) x = gelu_erf(x);
-                o[e] = (_Float16)x;
-              }
+              for (int e = 0; e < 4; ++e) o[e0 + e] = (_Float16)x[e];
             }
             const int piece = 4 * half + 2 * j + c;
             *(f16x8*)(stage + li * 128 + ((piece ^ wr_sw) << 4)) = o;
@@ -434,7 +400,6 @@ __global__ __launch_bounds__(kWaves * 64) void gemm_tn_f16(const _Float16* __res
           __builtin_nontemporal_store(o, (f16x8*)(dst + (long long)row * N));
         }
       }
-    }
     }
     after_epilogue = true;
   }
@@ -461,15 +426,6 @@ int proqa_gemm_tn_f16(const void* x, const void* w, const void* bias, void* y, i
   const unsigned grid = (unsigned)std::min<long long>(tiles, device_cu_count());
   hipStream_t st = as_stream(stream);
   const dim3 g(grid), b(kWaves * 64);
-  // developer switch: cut experiments on the main loop (wrong results by design; scripts/dev_gemm_ablate.py)
-  static const int kDbg = getenv("PROQA_GEMM_DBG") ? atoi(getenv("PROQA_GEMM_DBG")) : 0;
-  if (kDbg) {
-#define PP_DBG_CASE(D) case D: hipLaunchKernelGGL((gemm_tn_f16<EPI_NONE, D>), g, b, 0, st, (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias, (_Float16*)y, (int)m, n, k); break;
-    switch (kDbg) { PP_DBG_CASE(4) PP_DBG_CASE(5) PP_DBG_CASE(6) PP_DBG_CASE(7) PP_DBG_CASE(12) default: return fail(PROQA_EINVAL, "gemm_tn: PROQA_GEMM_DBG=%d is not built", kDbg); }
-#undef PP_DBG_CASE
-    PROQA_LAUNCH_CHECK();
-    return PROQA_OK;
-  }
   switch (epilogue) {
     case EPI_NONE:
       hipLaunchKernelGGL(gemm_tn_f16<EPI_NONE>, g, b, 0, st, (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias,
@@ -479,16 +435,9 @@ int proqa_gemm_tn_f16(const void* x, const void* w, const void* bias, void* y, i
       hipLaunchKernelGGL(gemm_tn_f16<EPI_BIAS>, g, b, 0, st, (const _Float16*)x, (const _Float16*)w, (const _Float16*)bias,
                          (_Float16*)y, (int)m, n, k);
       break;
-    default: {
-      // developer A/B switch: PROQA_GEMM_EPI_SCALAR=1 runs the scalar-fp32 epilogue of rounds 2-5 (same results)
-      static const bool kScalarEpi = getenv("PROQA_GEMM_EPI_SCALAR") && atoi(getenv("PROQA_GEMM_EPI_SCALAR")) != 0;
-      if (kScalarEpi)
-        hipLaunchKernelGGL((gemm_tn_f16<EPI_BIAS_GELU, 0, false>), g, b, 0, st, (const _Float16*)x, (const _Float16*)w,
-                           (const _Float16*)bias, (_Float16*)y, (int)m, n, k);
-      else
-        hipLaunchKernelGGL(gemm_tn_f16<EPI_BIAS_GELU>, g, b, 0, st, (const _Float16*)x, (const _Float16*)w,
-                           (const _Float16*)bias, (_Float16*)y, (int)m, n, k);
-    }
+    default:
+      hipLaunchKernelGGL(gemm_tn_f16<EPI_BIAS_GELU>, g, b, 0, st, (const _Float16*)x, (const _Float16*)w,
+                         (const _Float16*)bias, (_Float16*)y, (int)m, n, k);
   }
   PROQA_LAUNCH_CHECK();
   return PROQA_OK;

@@ -191,16 +191,7 @@ constexpr int kMaxRounds = kOverflowWords;   // 96
 // round (adds a host sync per round), PROQA_DEBUG_ROUNDS prints per-round filter times when profiling
 bool debug_flag(const char* name) { return getenv(name) != nullptr; }
 const bool kDebugCand = debug_flag("PROQA_DEBUG_CAND");
-// query blocks per wave for batches of more than 256 queries: 2 (8 waves x 64 queries) or, PROQA_FILTER_QW=4, the
-// 4-wave variant with 128 resident queries per wave (one wave per SIMD; experiment of DESIGN.md section 2.3)
-const unsigned kFilterFlags = getenv("PROQA_FILTER_FLAGS") ? (unsigned)atoi(getenv("PROQA_FILTER_FLAGS")) : 0u;
-const int kWideQw = getenv("PROQA_FILTER_QW") && (atoi(getenv("PROQA_FILTER_QW")) == 4 || atoi(getenv("PROQA_FILTER_QW")) == 1)
-                        ? atoi(getenv("PROQA_FILTER_QW")) : 2;
 const bool kDebugRounds = debug_flag("PROQA_DEBUG_ROUNDS");
-// developer A/B switches of the HBM-bound int8 scan (<= 256 queries): the one-workgroup-per-CU form with four pair buffers
-// (measured slower: off), and the row-split launch of <= 128 queries (on)
-const bool kDeepRing = getenv("PROQA_I8_DEEP_RING") && atoi(getenv("PROQA_I8_DEEP_RING")) != 0;
-const bool kRowSplit = !(getenv("PROQA_I8_ROW_SPLIT") && atoi(getenv("PROQA_I8_ROW_SPLIT")) == 0);
 // k x growth up to which a nominating round takes the 1024-key merge (developer / test override: PROQA_NOM_SMALL_MERGE_LIMIT)
 const double kSmallMergeLimit = getenv("PROQA_NOM_SMALL_MERGE_LIMIT") ? atof(getenv("PROQA_NOM_SMALL_MERGE_LIMIT")) : 200.0;
 
@@ -513,8 +504,6 @@ int ensure_store(proqa_index* idx, unsigned chunks, unsigned n_qtiles, int64_t n
 // so a slab of g*seen rows yields ~g*k candidates per query; g is capped so that those fit the
 // lane lists and one LDS merge pass next to the k running keys (kCandidateBudget per round).
 constexpr double kCandidateBudget = 640.0;
-// developer override of the budget (schedule experiments)
-const double kBudget = getenv("PROQA_CAND_BUDGET") ? atof(getenv("PROQA_CAND_BUDGET")) : kCandidateBudget;
 
 // Default growth: 4 for MFMA-bound batches (fewer candidates per round keep the rare path rare); 8 for
 // the HBM-bound small batches (one query tile per wave: two rounds fewer of launch + merge latency,
@@ -522,7 +511,7 @@ const double kBudget = getenv("PROQA_CAND_BUDGET") ? atof(getenv("PROQA_CAND_BUD
 // Rounds on the int8 copy: 2.  A nominated row costs a 256-byte gather and a share of an MFMA in the merge, and the scan
 // nominates ~1.9 x the rows that pass, so the time of a search follows the nominations more steeply than an fp16 search
 // follows its candidates; two or three more rounds (each ~35 us of launch + merge latency) are cheaper than the rows
-// they save (scripts/dev_schedule_sweep.py, 1 .. 2032 queries x 2.25M .. 18M rows: ABLATIONS R5.8).
+// they save (scripts/attic/dev_schedule_sweep.py, 1 .. 2032 queries x 2.25M .. 18M rows: ABLATIONS R5.8).
 // Small batches (qw == 1) on the int8 copy: 6 -- their merges are few workgroups on an idle chip, what they save is the ~9 us
 // every launch costs before it streams (re-swept in round 6 with the 1024-thread merges, stream time for growth 4 / 6 / 8:
 // one question 0.502 / 0.488 / 0.499 ms at 18M rows, 32 queries 0.522 / 0.516 / 0.517, 128 queries 0.585 / 0.581 / 0.589; 2032
@@ -530,17 +519,15 @@ const double kBudget = getenv("PROQA_CAND_BUDGET") ? atof(getenv("PROQA_CAND_BUD
 double growth_for(int k, int configured, int qw, bool nominating = false) {
   const int g = configured > 0 ? configured : nominating ? (qw == 1 ? 6 : 2) : (qw == 1 ? 8 : 4);
   // big pages: 60 % of the free keys of the big merge (the rest is headroom for the spread of the candidate count)
-  const double budget = k <= kPageK ? kBudget : 0.6 * (kBigSortKeys - k);
+  const double budget = k <= kPageK ? kCandidateBudget : 0.6 * (kBigSortKeys - k);
   return std::min<double>(g, budget / k);
 }
 
-// `start` > 0: rows [0, start) were covered by the bootstrap
 // Rounds of EQUAL growth behind a bootstrap of `start` rows: as many rounds as the capped growth needs, each multiplying
 // the rows seen by the same factor (N / start)^(1/R).  A schedule of "cap, cap, ..., whatever is left" wastes candidates:
 // a round yields ~k x (slab / rows seen) of them whatever its size, and the time of a search follows their total
 // (measured: ~17 us per 100 candidates per query at 2032 queries), so the same number of rounds at the smallest equal
 // growth is the cheapest (18M rows: 6 rounds at 3.05 instead of 4, 4, 4, 4, 4, 0.4: 10 % fewer candidates).
-const bool kEqualGrowth = !(getenv("PROQA_EQUAL_GROWTH") && atoi(getenv("PROQA_EQUAL_GROWTH")) == 0);   // developer A/B switch
 std::vector<Slab> plan_slabs_equal(long long n, long long start, double growth_cap) {
   std::vector<Slab> out;
   if (start <= 0 || start >= n) return out;
@@ -558,29 +545,11 @@ std::vector<Slab> plan_slabs_equal(long long n, long long start, double growth_c
   return out;
 }
 
-// developer experiment: PROQA_GROWTH_LIST="7,5,3,2" = slab / rows-seen ratio of round 1, 2, ... (the last one repeats)
-const std::vector<double> kGrowthList = [] {
-  std::vector<double> v;
-  if (const char* e = getenv("PROQA_GROWTH_LIST")) {
-    for (const char* p = e; *p;) {
-      char* end = nullptr;
-      const double g = strtod(p, &end);
-      if (end == p) break;
-      if (g > 0) v.push_back(g);
-      p = *end ? end + 1 : end;
-    }
-  }
-  return v;
-}();
-
+// `start` > 0: rows [0, start) were covered by the bootstrap
 std::vector<Slab> plan_slabs(long long n, int first, double growth, long long start = 0) {
   std::vector<Slab> out;
   long long seen = start;
-  auto growth_of = [&](size_t round) {
-    if (kGrowthList.empty() || start == 0) return growth;
-    return std::min(growth * 2.0, kGrowthList[std::min(round, kGrowthList.size() - 1)]);
-  };
-  long long next = start > 0 ? std::max<long long>(kStageRows, round_up<long long>((long long)(start * growth_of(0)), kStageRows))
+  long long next = start > 0 ? std::max<long long>(kStageRows, round_up<long long>((long long)(start * growth), kStageRows))
                              : std::min<long long>(n, round_up<long long>(first, kStageRows));
   while (seen < n) {
     long long r1 = std::min(n, seen + next);
@@ -588,7 +557,7 @@ std::vector<Slab> plan_slabs(long long n, int first, double growth, long long st
     if (n - r1 < next / 4) r1 = n;
     out.push_back({seen, r1});
     seen = r1;
-    next = std::max<long long>(kStageRows, round_up<long long>((long long)(seen * growth_of(out.size())), kStageRows));
+    next = std::max<long long>(kStageRows, round_up<long long>((long long)(seen * growth), kStageRows));
   }
   return out;
 }
@@ -663,7 +632,7 @@ LeapPlan plan_leap(long long n, long long boot, int k, int qw, bool nominating, 
     if (j >= k) continue;
     const double m = j * (rho - 1.0);
     const double spread = 1.0 + 5.0 / std::sqrt((double)j);
-    const bool fits = nominating ? m * spread * 2.5 <= (double)kMaxSortKeys : m * spread <= (double)(kMaxSortKeys - k) && m <= kBudget;
+    const bool fits = nominating ? m * spread * 2.5 <= (double)kMaxSortKeys : m * spread <= (double)(kMaxSortKeys - k) && m <= kCandidateBudget;
     if (!fits && fixed_rounds <= 0) continue;
     const double cost = r * (round_cost + m);
     if (!best.rounds || cost < best_cost) {
@@ -762,14 +731,11 @@ int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, uns
   // search was set up for it: two workgroups per CU, deep lane lists instead of a spill log
   const bool nominate = idx->q8_active && !inclusive && !dense && !bounded && !shape.want_chunks && !shape.compact;
   if (nominate) {
-    // (developer switch, off: ONE workgroup per CU with four pair buffers -- 96 KB of LDS-DMA in flight -- for the batches of
-    // <= 256 queries measured 10-19 % slower than two workgroups with two, ABLATIONS R6.2)
-    const bool deep = qw == 1 && kDeepRing;
     // at most 128 queries: row-split launch (mips_filter_i8<SPLIT>) -- the 1 / 2 / 4 query blocks that hold queries are
     // replicated over the eight waves, which share the units of the stream (and the lists of their queries)
     unsigned q_blocks = 0;
-    if (qw == 1 && kRowSplit && idx->pending_nq <= 128) q_blocks = idx->pending_nq <= 32 ? 1u : (idx->pending_nq <= 64 ? 2u : 4u);
-    const unsigned want = std::max<unsigned>(64u, (unsigned)((deep ? 1 : 2) * device_cu_count() / (int)n_qtiles) / 8 * 8);
+    if (qw == 1 && idx->pending_nq <= 128) q_blocks = idx->pending_nq <= 32 ? 1u : (idx->pending_nq <= 64 ? 2u : 4u);
+    const unsigned want = std::max<unsigned>(64u, (unsigned)(2 * device_cu_count() / (int)n_qtiles) / 8 * 8);
     const LaunchGeom g = geometry(slab.r1 - slab.r0, n_qtiles, false, k, want);
     if (int rc = ensure_store(idx, round_up<unsigned>(g.chunks, 8), n_qtiles, nq_pad, kNominateLaneCap)) return rc;
     FilterArgsI8 fa;
@@ -783,10 +749,9 @@ int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, uns
     fa.blk = idx->blk8;
     fa.store = store_of(idx, nq_pad, n_qtiles, kNominateLaneCap, round_up<unsigned>(g.chunks, 8));
     fa.overflow = overflow_word;
-    fa.flags = kFilterFlags;
     fa.q_blocks = q_blocks;
     if (f0) PROQA_HIP(hipEventRecord(f0, st));
-    PROQA_HIP(launch_filter_i8(fa, qw, g.grid, st, deep));
+    PROQA_HIP(launch_filter_i8(fa, qw, g.grid, st));
     if (f1) PROQA_HIP(hipEventRecord(f1, st));
     MergeArgs ma = {};
     ma.store = fa.store;
@@ -853,7 +818,6 @@ int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, uns
   fa.ub = bounded ? (idx->exact ? idx->ub_filter : idx->ub) : nullptr;
   fa.store = store_of(idx, nq_pad, n_qtiles, lane_cap, round_up<unsigned>(g.chunks, 8));
   fa.overflow = overflow_word;
-  fa.flags = kFilterFlags;
   fa.compact = shape.compact ? 1 : 0;
   if (f0) PROQA_HIP(hipEventRecord(f0, st));
   PROQA_HIP(launch_filter(fa, qw, inclusive, g.grid, st));
@@ -947,7 +911,7 @@ int page_enqueue(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64_
     // 1324 candidates per query, -40 us; where it would save a round instead -- 4.5M, 18M rows -- the larger bootstrap
     // costs what the round did)
     // (nominating rounds: always -- the rows of the larger bootstrap are rows no round nominates from)
-    if (idx->bootstrap_auto && kEqualGrowth && boot * 2 <= kBootstrapMaxRows && idx->n >= 8 * boot) {
+    if (idx->bootstrap_auto && boot * 2 <= kBootstrapMaxRows && idx->n >= 8 * boot) {
       const double cap = std::log(1.0 + growth_for(page_k, idx->growth, gqw, idx->q8_active));
       const int r1 = (int)std::ceil(std::log((double)idx->n / (double)boot) / cap - 1e-9);
       const int r2 = (int)std::ceil(std::log((double)idx->n / (double)(2 * boot)) / cap - 1e-9);
@@ -961,8 +925,7 @@ int page_enqueue(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64_
   double page_growth = growth_for(page_k, idx->growth, gqw, idx->q8_active);
   // leaping rounds (plan_leap): behind a bootstrap, on the default schedule, unless this index is pausing them
   LeapPlan leap;
-  if (boot && !bounded && !idx->exact && idx->leap_mode && env_int("PROQA_LEAP", 1) != 0 && idx->growth == 0 && kEqualGrowth && kGrowthList.empty() &&
-      page_k <= kLeapMaxK) {
+  if (boot && !bounded && !idx->exact && idx->leap_mode && env_int("PROQA_LEAP", 1) != 0 && idx->growth == 0 && page_k <= kLeapMaxK) {
     if (idx->leap_epoch != idx->rows_epoch) {
       idx->leap_epoch = idx->rows_epoch;
       idx->leap_pause = idx->leap_skip = idx->leap_strikes = 0;
@@ -999,8 +962,7 @@ int page_enqueue(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64_
                "reach them)", (void*)idx, leap.rounds, boot, leap.rank, page_k, leap.per_round);
     }
   } else {
-    plan->slabs = boot && kEqualGrowth && kGrowthList.empty() ? plan_slabs_equal(idx->n, boot, page_growth)
-                                                            : plan_slabs(idx->n, first, page_growth, boot);
+    plan->slabs = boot ? plan_slabs_equal(idx->n, boot, page_growth) : plan_slabs(idx->n, first, page_growth);
   }
   idx->page_growth = page_growth;
   plan->boot = boot;
@@ -1205,8 +1167,7 @@ OnePassPlan plan_one_pass(const proqa_index* idx, int64_t nq_pad, int k, bool la
   if (p.n_sample > idx->n / 4) return p;                       // k is a large part of the shard
   // Dense regime (thousands of queries x a large k: more than every second 32-row unit of a wave holds a score above its
   // threshold): compact lists of 8-byte keys, ~24 per list of 70; otherwise column records, ~8 per list of 24.
-  // (compact lists exist for the 8 x 64-query tiling only: with PROQA_FILTER_QW=4 / 1 the launch logs column records)
-  p.compact = kOnePassCompact && !latency_bound && kWideQw == 2 && expected / (double)idx->n * 2048.0 > 0.5;
+  p.compact = kOnePassCompact && !latency_bound && expected / (double)idx->n * 2048.0 > 0.5;
   p.lane_cap = p.compact ? (unsigned)kCompactLaneCap : (unsigned)kOnePassLaneCap;
   const double per_list = p.compact ? 24.0 : 8.0;
   p.want_chunks = round_up<unsigned>((unsigned)std::ceil(expected / (2.0 * per_list)), 8);   // two lists per chunk
@@ -1315,10 +1276,9 @@ int one_pass_big_launch_i8(proqa_index* idx, const OnePassPlan& pl, int qw, unsi
   fa.blk = idx->blk8;
   fa.store = store_of(idx, (unsigned)nq_pad, n_qtiles, kNominateLaneCap, round_up<unsigned>(g.chunks, 8));
   fa.overflow = word;
-  fa.flags = kFilterFlags;
   // (row-split launch as in run_round: the 1 / 2 / 4 query blocks that hold queries, the eight waves share the units of the stream)
-  fa.q_blocks = kRowSplit && nq <= 128 ? (nq <= 32 ? 1u : (nq <= 64 ? 2u : 4u)) : 0u;
-  PROQA_HIP(launch_filter_i8(fa, qw, g.grid, st, false));
+  fa.q_blocks = nq <= 128 ? (nq <= 32 ? 1u : (nq <= 64 ? 2u : 4u)) : 0u;
+  PROQA_HIP(launch_filter_i8(fa, qw, g.grid, st));
   CandidateStore emitted;
   emitted.lane_log = idx->emit_log;
   emitted.lane_cnt = idx->emit_cnt;
@@ -1471,7 +1431,7 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
   // needs to: a round that falls short leaves the sample's r-th best too LOW, i.e. a looser threshold for the launch over
   // the shard, whose result is checked as ever (>= k rows per query, no overflow).
   int leap_rank_sample = 0;
-  if (boot && r <= 256 && idx->leap_mode && env_int("PROQA_LEAP", 1) != 0 && idx->growth == 0 && kGrowthList.empty()) {
+  if (boot && r <= 256 && idx->leap_mode && env_int("PROQA_LEAP", 1) != 0 && idx->growth == 0) {
     // (the plan is kept: the negative-binomial sums for r = 256 are ~0.2 ms of host time)
     const long long key[4] = {pl.n_sample, boot, r, qw};
     if (std::memcmp(key, idx->leap_sample_key, sizeof key) != 0) {
@@ -1730,7 +1690,7 @@ int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, in
   PROQA_ON_DEVICE(idx->device);
 
   // wave tile: 2 query blocks of 32 per wave (512 queries per workgroup) unless the batch is small
-  const int qw = nq > 256 ? kWideQw : 1;
+  const int qw = nq > 256 ? 2 : 1;
   const unsigned tile_q = filter_tile_queries(qw);
   const unsigned n_qtiles = (unsigned)ceil_div<int64_t>(nq, tile_q);
   const int64_t nq_pad = (int64_t)n_qtiles * tile_q;

@@ -10,8 +10,8 @@ namespace proqa {
 constexpr int kDim = PROQA_EMBED_DIM;  // 128
 constexpr int kFilterWaves = 8;
 constexpr int kFilterThreads = kFilterWaves * 64;
-// queries of one filter workgroup: 8 waves x qw blocks of 32 (qw = 1, 2), or 4 waves x 4 blocks (qw = 4)
-__host__ __device__ constexpr unsigned filter_tile_queries(int qw) { return (qw == 4 ? 4u : 8u) * (unsigned)qw * 32u; }
+// queries of one filter workgroup: 8 waves x qw blocks of 32 (qw = 1, 2)
+__host__ __device__ constexpr unsigned filter_tile_queries(int qw) { return (unsigned)kFilterWaves * (unsigned)qw * 32u; }
 constexpr int kStageRows = 128;  // corpus rows per LDS stage (32 KiB of fp16 rows)
 constexpr int kMergeThreads = 256;
 // merge_lists sorts up to this many gathered keys per query in LDS (128 KiB); above it the merge
@@ -83,7 +83,6 @@ struct FilterArgs {
   const float* ub;       // paged (k > kPageK) searches: scores above ub[q] were reported by an earlier page
   CandidateStore store;
   unsigned* overflow;    // set to 1 if a record had to be dropped in this launch
-  unsigned flags;        // developer experiments (PROQA_FILTER_FLAGS), 0 in production
   int compact;           // lane lists hold the passing scores as 8-byte keys (mips_filter_f16<COMPACT>), not column records
 };
 
@@ -154,12 +153,11 @@ struct FilterArgsI8 {
                             // blocks past the shard's last one (the scan fetches whole pairs of stages)
   CandidateStore store;     // lane lists of 8-byte records {first row of the column, 16 nominee bits} in the column records' slots
   unsigned* overflow;
-  unsigned flags;           // developer cut experiments (PROQA_FILTER_FLAGS; wrong results), 0 in production
   unsigned q_blocks;        // row-split launches (few queries): 32-query blocks that hold queries -- 1, 2 or 4; else 0.  The 8 /
                             // q_blocks waves that share a query block take every (8 / q_blocks)-th 32-row unit each and append
                             // to the block's lists through workgroup-shared counters
 };
-hipError_t launch_filter_i8(const FilterArgsI8& a, int qw, unsigned grid, hipStream_t st, bool deep = false);
+hipError_t launch_filter_i8(const FilterArgsI8& a, int qw, unsigned grid, hipStream_t st);
 // column statistics of fp16 rows [0, n): partial[g][0..127] sums, [g][128..255] minima, [g][256..383] maxima per workgroup g
 // (deterministic two-level reduction), then mean / scale per dimension: col[0..127] mean, col[128..255] 1 / c, col[256..383] c
 constexpr int kColStatGroups = 1024;

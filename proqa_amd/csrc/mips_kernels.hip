@@ -140,7 +140,7 @@ __device__ __forceinline__ void write_record(WaveRecord* dst, const f32x16& acc,
                           __float_as_uint(acc[4 * g + 2]), __float_as_uint(acc[4 * g + 3]));
 }
 
-// Tiling: a workgroup = 8 waves; wave w keeps query blocks (32 queries each) w*QW .. w*QW+QW-1 of
+// Tiling: a workgroup = 8 waves; wave w keeps query blocks (32 queries each; QW = 1 or 2) w*QW .. w*QW+QW-1 of
 // its query tile as MFMA B fragments in VGPRs and every wave reads the same corpus sub-tile
 // (32 rows, MFMA A operand) from LDS.  The loop is arranged so that the MFMA pipe always has
 // queued work from a single wave:
@@ -160,9 +160,9 @@ __device__ __forceinline__ void write_record(WaveRecord* dst, const f32x16& acc,
 // taken for ~10 % of them at 13 000 survivors per query over 8.8M rows) and a passing score is appended as the 8-byte key the
 // merge sorts -- (score, row) -- to the lane's own list in HBM: 10 x fewer bytes than the 80-byte column that carries one
 // such score, and a list's consecutive 8-byte appends are combined in the XCD's L2 (the open lines of a launch's lists fit).
-template <int QW, int NW, bool INCLUSIVE, bool BOUNDED, bool COMPACT = false>
-__global__ __launch_bounds__(NW * 64) void mips_filter_f16(FilterArgs a) {
-  static_assert(((QW == 1 || QW == 2) && NW == 8) || (QW == 4 && NW == 4), "8 waves x 32/64 queries or 4 waves x 128 queries");
+template <int QW, bool INCLUSIVE, bool BOUNDED, bool COMPACT = false>
+__global__ __launch_bounds__(kFilterThreads) void mips_filter_f16(FilterArgs a) {
+  static_assert(QW == 1 || QW == 2, "8 waves x 32 or 64 queries");
   static_assert(!COMPACT || (!INCLUSIVE && !BOUNDED), "compact lists: first page, strict threshold only");
   // the only LDS object of the kernel (a second one makes hipcc drain vmcnt before ds_reads)
   __shared__ __attribute__((aligned(16))) char lds[4 * kStageBytes];
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(NW * 64) void mips_filter_f16(FilterArgs a) {
 
   // resident query fragments (MFMA B operand): lane (li, half), k-step j holds the 16-byte
   // piece 2j+half of query row q0 + blk*32 + li.
-  const unsigned q0 = qt * (NW * QW * 32) + wave * (QW * 32);
+  const unsigned q0 = qt * (kFilterWaves * QW * 32) + wave * (QW * 32);
   f16x8 qf[QW][8];
   float tau[QW];
   float ub[QW];              // BOUNDED (pages after the first of a k > kPageK search)
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(NW * 64) void mips_filter_f16(FilterArgs a) {
   // LDS-DMA: per stage each wave issues 4 instructions of 1 KiB (4 corpus rows); lane t lands
   // at base + 16 t = (row t>>4, slot t&15) and therefore fetches piece (t&15) ^ (row&15).
   // Rows past the chunk end re-read the chunk's last row (never logged: rows_left excludes them).
-  constexpr int kDmaPerWave = 32 / NW;   // 1 KiB pieces of a 32 KiB stage each wave fetches
+  constexpr int kDmaPerWave = 32 / kFilterWaves;   // 1 KiB pieces of a 32 KiB stage each wave fetches
   const int dma_row = lane >> 4;
   const int dma_slot = lane & 15;
   int dma_rel[kDmaPerWave];
@@ -257,10 +257,8 @@ __global__ __launch_bounds__(NW * 64) void mips_filter_f16(FilterArgs a) {
   auto publish = [&](bool younger_stage_in_flight) {
     if (younger_stage_in_flight) {
       // (a raw s_barrier: __syncthreads() lets hipcc drain vmcnt to 0 on account of the LDS-DMA in flight)
-      if constexpr (kDmaPerWave == 4)
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+      static_assert(kDmaPerWave == 4, "the counted wait below");
+      asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
     } else {
@@ -273,8 +271,6 @@ __global__ __launch_bounds__(NW * 64) void mips_filter_f16(FilterArgs a) {
   if (nstages > 2) issue_stage(2, off2);
   publish(nstages > 2);  // prologue: stages 0 and 1 landed
 
-  if ((a.flags & 1u) && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);   // experiment: static priority for the younger half
-  if ((a.flags & 2u) && (wave & 1)) __builtin_amdgcn_s_setprio(1);         // experiment: every other wave
   f16x8 af[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) af[j] = *(const f16x8*)(lds + off0 + rd_off[j]);
@@ -291,11 +287,7 @@ __global__ __launch_bounds__(NW * 64) void mips_filter_f16(FilterArgs a) {
 #pragma unroll
     for (int blk = 0; blk < QW; ++blk) {
       unsigned long long* list = (unsigned long long*)lane_list[blk];
-#ifdef PROQA_COMPACT_FLAG128   // developer A/B build: the run-time switch to the per-register test (round 5)
-      if (!kCheckRows && !(a.flags & 128u)) {
-#else
       if (!kCheckRows) {
-#endif
         // Every unit but the chunk's last stage: ONE wave-wide branch per query block (the column maximum), then straight-line
         // code -- the 16-bit set of the lane's scores above its threshold (32 VALU operations, no branch); a lane with ONE such
         // score (almost every hit) appends (its maximum, the row of the set bit); lanes with several take the per-register
@@ -652,11 +644,8 @@ __device__ __forceinline__ unsigned column_rows_mask(int rows_left) {
 // fp16 scan would be five stores and ten times the write traffic); a full list is reported through `overflow` (the round is
 // then re-scanned by the fp16 overflow-safe path): no spill log, no capacity branch in the hit path.
 //
-// NP = pair buffers of the LDS image (NP - 1 pairs of LDS-DMA in flight).  NP = 2 (64 KiB, two workgroups per CU: 64 KB in
-// flight per CU) is the shipped form for every batch size.  NP = 4 -- ONE workgroup per CU with 128 KiB of LDS and three
-// pairs (96 KB) in flight, what the fp16 scan's ring holds -- was built for the HBM-bound batches (QW = 1) on the round-5
-// review's reading that bytes in flight bound them; it measured 10-19 % SLOWER (the second workgroup's waves are worth more
-// than the third pair: ABLATIONS R6.2) and stays behind PROQA_I8_DEEP_RING=1.
+// Two pair buffers (one pair of LDS-DMA in flight) and two workgroups per CU for every batch size: a deeper ring in one
+// workgroup per CU measured 10-19 % slower (ABLATIONS R6.2).
 //
 // SPLIT (QW = 1, at most 128 queries): with one query block per wave a batch of <= 32 queries keeps ONE wave of the
 // workgroup busy -- it alone walks every 32-row unit of the chunk (fragment reads -> four dependent MFMAs -> test, in series:
@@ -665,12 +654,11 @@ __device__ __forceinline__ unsigned column_rows_mask(int rows_left) {
 // blocks are replicated over the 8 waves, the R = 8 / q_blocks waves of a block take every R-th unit each and append to
 // the block's lists (one per query and accumulator half, as ever) through list lengths kept in LDS -- an LDS atomic per
 // logged record, and records are rare where queries are few; the merge sees the same lists as from any other launch.
-template <int QW, int NP, bool SPLIT = false>
-__global__ __launch_bounds__(kFilterThreads, NP == 2 ? 2 : 1) void mips_filter_i8(FilterArgsI8 a) {
+template <int QW, bool SPLIT = false>
+__global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8 a) {
   static_assert(QW == 1 || QW == 2, "8 waves x 32 / 64 queries");
-  static_assert(NP == 2 || NP == 4, "two pair buffers (two workgroups per CU) or four (one)");
   static_assert(!SPLIT || QW == 1, "row-split launches keep one query block per wave");
-  __shared__ __attribute__((aligned(16))) char lds[2 * NP * kStageBytesI8];
+  __shared__ __attribute__((aligned(16))) char lds[4 * kStageBytesI8];
   constexpr int NW = kFilterWaves;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -735,7 +723,7 @@ __global__ __launch_bounds__(kFilterThreads, NP == 2 ? 2 : 1) void mips_filter_i
     dma_rel[e] = (wave * kDmaPerWave + e) * 8 + (lane >> 3);
     dma_piece_off[e] = ((lane & 7) ^ ((dma_rel[e] >> 1) & 7)) * 16;
   }
-  auto issue_pair = [&](int p) {   // stages 2p, 2p+1 -> the pair buffer p % NP
+  auto issue_pair = [&](int p) {   // stages 2p, 2p+1 -> the pair buffer p % 2
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int s = 2 * p + h;
@@ -746,7 +734,7 @@ __global__ __launch_bounds__(kFilterThreads, NP == 2 ? 2 : 1) void mips_filter_i
           rel = rel < n_rows ? rel : n_rows - 1;
           const signed char* src = chunk_base + (long long)rel * kRowBytesI8 + dma_piece_off[e];
           __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                           (__attribute__((address_space(3))) void*)(lds + ((p & (NP - 1)) * 2 + h) * kStageBytesI8 +
+                                           (__attribute__((address_space(3))) void*)(lds + ((p & 1) * 2 + h) * kStageBytesI8 +
                                                                                      (wave * kDmaPerWave + e) * 1024),
                                            16, 0, QW == 1 ? kDmaAux : 0);
         }
@@ -754,31 +742,12 @@ __global__ __launch_bounds__(kFilterThreads, NP == 2 ? 2 : 1) void mips_filter_i
     }
   };
   int st_cur = 0;   // record-store instructions of this wave since the last barrier: all younger than the awaited DMA pieces
-  // `p`: the pair the barrier publishes.  Younger than its DMA pieces are this wave's record stores since the last barrier
-  // and (NP = 4) its pieces of the pairs p+1, p+2 -- 2 kDmaPerWave instructions per whole pair; a chunk's last pair may hold
-  // one stage.  Waiting for fewer outstanding operations than that is always safe: the tail of a chunk (the last two
-  // pairs) and lists of more than four records wait a little longer than they must.
-  auto publish = [&](int p) {
+  // The barrier that publishes a pair: younger than the pair's DMA pieces are only this wave's record stores since the last
+  // barrier.  Waiting for fewer outstanding operations than that is always safe: lists of more than eight records wait a
+  // little longer than they must.
+  auto publish = [&]() {
     const int allowed = __builtin_amdgcn_readfirstlane(st_cur);
-    if (NP == 4) {
-      constexpr int kPairOps = 4 * kDmaPerWave;             // instructions of two whole pairs in flight behind pair p
-      if (2 * (p + 2) + 2 <= nstages) {                     // pairs p+1 and p+2 are whole
-        static_assert(kPairOps == 8, "the immediates below");
-        if (allowed >= 4) {
-          asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        } else if (allowed >= 2) {
-          asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        } else if (allowed >= 1) {
-          asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        }
-      } else if (2 * (p + 1) + 2 <= nstages) {              // pair p+1 is whole, pair p+2 short or absent
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    } else if (allowed >= 8) {
+    if (allowed >= 8) {
       asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     } else if (allowed >= 6) {
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -798,13 +767,11 @@ __global__ __launch_bounds__(kFilterThreads, NP == 2 ? 2 : 1) void mips_filter_i
     asm volatile("" ::: "memory");
     st_cur = 0;
   };
-#pragma unroll
-  for (int p = 0; p < NP - 1; ++p)
-    if (p < npairs) issue_pair(p);
+  if (npairs > 0) issue_pair(0);
   if (!wave_live) {   // padding / exhausted queries only: the wave helps streaming and meets the barriers
     for (int p = 0; p < npairs; ++p) {
-      publish(p);
-      if (p + NP - 1 < npairs) issue_pair(p + NP - 1);
+      publish();
+      if (p + 1 < npairs) issue_pair(p + 1);
     }
   }
   // The block constants {G_b, X_b} of a pair's eight units are wave-uniform: ONE scalar load of 64 bytes per pair (hipcc
@@ -824,9 +791,9 @@ __global__ __launch_bounds__(kFilterThreads, NP == 2 ? 2 : 1) void mips_filter_i
   };
   for (int p = 0; wave_live && p < npairs; ++p) {
     const f32x16 bc = load_blocks(p);
-    publish(p);
-    if (p + NP - 1 < npairs) issue_pair(p + NP - 1);
-    const char* base = lds + (p & (NP - 1)) * 2 * kStageBytesI8;
+    publish();
+    if (p + 1 < npairs) issue_pair(p + 1);
+    const char* base = lds + (p & 1) * 2 * kStageBytesI8;
     const int nunits = (nstages - 2 * p >= 2 ? 2 : 1) * (kStageRows / kSubRows);
     i32x4 af[4];
     if constexpr (!SPLIT) {
@@ -2633,54 +2600,43 @@ __global__ void emit_sorted_prefix(const unsigned long long* __restrict__ keys, 
 // ---------------------------------------------------------------------------------------
 // launch wrappers (called from mips_index.cpp)
 // ---------------------------------------------------------------------------------------
-template <int QW, int NW, bool INCLUSIVE>
+template <int QW, bool INCLUSIVE>
 static void launch_filter_bounded(const FilterArgs& a, dim3 g, hipStream_t st) {
   if (a.ub)
-    hipLaunchKernelGGL((mips_filter_f16<QW, NW, INCLUSIVE, true>), g, dim3(NW * 64), 0, st, a);
+    hipLaunchKernelGGL((mips_filter_f16<QW, INCLUSIVE, true>), g, dim3(kFilterThreads), 0, st, a);
   else
-    hipLaunchKernelGGL((mips_filter_f16<QW, NW, INCLUSIVE, false>), g, dim3(NW * 64), 0, st, a);
+    hipLaunchKernelGGL((mips_filter_f16<QW, INCLUSIVE, false>), g, dim3(kFilterThreads), 0, st, a);
 }
 
 hipError_t launch_filter(const FilterArgs& a, int qw, bool inclusive, unsigned grid, hipStream_t st) {
   dim3 g(grid);
   if (a.compact) {
     if (qw != 2 || inclusive || a.ub) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((mips_filter_f16<2, 8, false, false, true>), g, dim3(8 * 64), 0, st, a);
+    hipLaunchKernelGGL((mips_filter_f16<2, false, false, true>), g, dim3(kFilterThreads), 0, st, a);
     return hipGetLastError();
   }
-  if (qw == 4) {
+  if (qw == 2) {
     if (inclusive)
-      launch_filter_bounded<4, 4, true>(a, g, st);
+      launch_filter_bounded<2, true>(a, g, st);
     else
-      launch_filter_bounded<4, 4, false>(a, g, st);
-  } else if (qw == 2) {
-    if (inclusive)
-      launch_filter_bounded<2, 8, true>(a, g, st);
-    else
-      launch_filter_bounded<2, 8, false>(a, g, st);
+      launch_filter_bounded<2, false>(a, g, st);
   } else {
     if (inclusive)
-      launch_filter_bounded<1, 8, true>(a, g, st);
+      launch_filter_bounded<1, true>(a, g, st);
     else
-      launch_filter_bounded<1, 8, false>(a, g, st);
+      launch_filter_bounded<1, false>(a, g, st);
   }
   return hipGetLastError();
 }
 
-// deep: the one-workgroup-per-CU form with four pair buffers (QW = 1 only; the caller sizes the grid for it)
-hipError_t launch_filter_i8(const FilterArgsI8& a, int qw, unsigned grid, hipStream_t st, bool deep) {
-  if (qw == 2)   // (flag 256, experiment: 24 KiB of unused dynamic LDS leave room for ONE workgroup per CU)
-    hipLaunchKernelGGL((mips_filter_i8<2, 2>), dim3(grid), dim3(kFilterThreads), (a.flags & 256u) ? 24576 : 0, st, a);
+hipError_t launch_filter_i8(const FilterArgsI8& a, int qw, unsigned grid, hipStream_t st) {
+  if (qw == 2)
+    hipLaunchKernelGGL((mips_filter_i8<2>), dim3(grid), dim3(kFilterThreads), 0, st, a);
   else if (qw == 1 && a.q_blocks) {   // row-split: 1, 2 or 4 query blocks replicated over the eight waves
     if (a.q_blocks != 1 && a.q_blocks != 2 && a.q_blocks != 4) return hipErrorInvalidValue;
-    if (deep)
-      hipLaunchKernelGGL((mips_filter_i8<1, 4, true>), dim3(grid), dim3(kFilterThreads), 0, st, a);
-    else
-      hipLaunchKernelGGL((mips_filter_i8<1, 2, true>), dim3(grid), dim3(kFilterThreads), 0, st, a);
-  } else if (qw == 1 && deep)
-    hipLaunchKernelGGL((mips_filter_i8<1, 4>), dim3(grid), dim3(kFilterThreads), 0, st, a);
-  else if (qw == 1)
-    hipLaunchKernelGGL((mips_filter_i8<1, 2>), dim3(grid), dim3(kFilterThreads), 0, st, a);
+    hipLaunchKernelGGL((mips_filter_i8<1, true>), dim3(grid), dim3(kFilterThreads), 0, st, a);
+  } else if (qw == 1)
+    hipLaunchKernelGGL((mips_filter_i8<1>), dim3(grid), dim3(kFilterThreads), 0, st, a);
   else
     return hipErrorInvalidValue;
   return hipGetLastError();
@@ -2816,17 +2772,14 @@ hipError_t launch_merge(const MergeArgs& a, unsigned nq_pad, hipStream_t st) {
     if (big || a.xq32 || a.compact || a.inclusive || a.bound_keys) return hipErrorInvalidValue;
     // Which merge: (a) at most 256 queries -- the chip is empty during their merges, whose time is a chain of dependent round
     // trips: a 1024-thread workgroup per query re-scores a round's nominated rows in ONE trip of 16 waves instead of three
-    // of four (PROQA_MERGE_NOM_WIDE=0: the 256-thread form, A/B); (b) rounds that nominate few rows (a.nom_keys == 1024: k x
-    // growth <= 200, e.g. the k = 80 search of thousands of queries) -- the merge that holds 1024 keys, EIGHT workgroups per CU,
-    // i.e. the 2032 merges of a round resident at once instead of 1792 + a second wave of 240 (PROQA_MERGE_NOM_CAP=2048: the
-    // seven-per-CU form, A/B); (c) 2048 keys, seven per CU.  A round that nominates more rows than its merge holds is re-scanned
-    // on the overflow-safe path AND suspends the int8 rounds: (b) is only taken with a factor ~4 of headroom.
-    static const bool kSmallNom = !(getenv("PROQA_MERGE_NOM_CAP") && atoi(getenv("PROQA_MERGE_NOM_CAP")) == 2048);
-    static const bool kWideNom = !(getenv("PROQA_MERGE_NOM_WIDE") && atoi(getenv("PROQA_MERGE_NOM_WIDE")) == 0);
-    if (kWideNom && nq_pad <= 256)
+    // of four; (b) rounds that nominate few rows (a.nom_keys == 1024: k x growth <= 200, e.g. the k = 80 search of thousands
+    // of queries) -- the merge that holds 1024 keys, EIGHT workgroups per CU, i.e. the 2032 merges of a round resident at once
+    // instead of 1792 + a second wave of 240; (c) 2048 keys, seven per CU.  A round that nominates more rows than its merge
+    // holds is re-scanned on the overflow-safe path AND suspends the int8 rounds: (b) is only taken with a factor ~4 of headroom.
+    if (nq_pad <= 256)
       hipLaunchKernelGGL((topk_merge<kMergeNominatedI8, kMaxSortKeys, kOnePassMergeThreads>), dim3(nq_pad), dim3(kOnePassMergeThreads), 0,
                          st, a);
-    else if (kSmallNom && a.nom_keys == kNominatedSortKeys)
+    else if (a.nom_keys == kNominatedSortKeys)
       hipLaunchKernelGGL((topk_merge<kMergeNominatedI8, kNominatedSortKeys>), dim3(nq_pad), dim3(kMergeThreads), 0, st, a);
     else
       hipLaunchKernelGGL((topk_merge<kMergeNominatedI8, kMaxSortKeys>), dim3(nq_pad), dim3(kMergeThreads), 0, st, a);

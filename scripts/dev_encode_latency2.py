@@ -1,5 +1,5 @@
-"""dev: latency of encoding one question (bert-base shape) with and without the captured forward (PROQA_ENCODER_GRAPH)."""
-import os, sys, time
+"""dev: latency of encoding one question (bert-base shape)."""
+import sys, time
 import torch
 sys.path.insert(0, ".")
 from proqa_amd.retriever import BertForRetriever, random_state_dict, BERT_BASE
@@ -13,4 +13,4 @@ for B, L in ((1, 16), (1, 30), (4, 32), (1, 128), (8, 32)):
         t0 = time.perf_counter()
         q = model.get_embed({"input_ids": tok, "input_mask": mask}, True, check_mask=False, seq_lens_host=[L] * B)["embed"]
         torch.cuda.synchronize(); ts.append(time.perf_counter() - t0)
-    print(f"graph={os.environ.get('PROQA_ENCODER_GRAPH','1')} B={B} L={L}: median {sorted(ts)[25]*1e3:.3f} ms  sum {q.float().sum().item():.4f}")
+    print(f"B={B} L={L}: median {sorted(ts)[25]*1e3:.3f} ms  sum {q.float().sum().item():.4f}")

@@ -11,7 +11,4 @@ wait
 g++ -shared -o libproqa_hip.so common.o npy_io.o wordpiece.o mips_index.o mips_kernels.o sharded_search.o encoder_kernels.o gemm_kernels.o \
     attention_kernel.o lt_gemm.o encoder.o kmeans_kernels.o microbench.o -Wl,--no-as-needed -lpthread -lm -ldl
 cd ../..
-for f in ${FLAGS:-0}; do
-  echo "== PROQA_FILTER_FLAGS=$f"
-  PROQA_FILTER_FLAGS=$f python scripts/dev_nominate_ab.py 18e6 2032 80 normal 2>&1 | grep "filter stamps\|mode=" | tail -4
-done
+python scripts/dev_nominate_ab.py 18e6 2032 80 normal 2>&1 | grep "filter stamps\|mode=" | tail -4

@@ -1,5 +1,4 @@
 """Developer timing of the HIP search at the BASELINE shape (not part of the test suite)."""
-import os
 import sys
 import time
 
@@ -38,6 +37,6 @@ for cfg in cfgs:
     dt = (time.time() - t) / reps
     st = ix.last_stats()
     flops = 2.0 * nq * n * 128
-    print(f"variant={os.environ.get('PROQA_FILTER_VARIANT','default')} cfg={cfg} wall={dt*1e3:.3f} ms q/s={nq/dt:.0f} "
+    print(f"cfg={cfg} wall={dt*1e3:.3f} ms q/s={nq/dt:.0f} "
           f"rounds={st['rounds']} cand={st['candidates']} filter_ms={st['filter_ms']:.3f} (best {best:.3f}) total_ms={st['total_ms']:.3f} "
           f"filter TF/s={flops/st['filter_ms']/1e9:.1f}")
