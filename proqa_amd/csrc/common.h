@@ -69,6 +69,37 @@ inline hipError_t try_malloc(void** p, size_t bytes) {
   return e;
 }
 
+// An allocation that is grown on demand and never shrinks: the pointer, its capacity and its release live here and
+// nowhere else.  Device memory, or pinned host memory when `pinned_host` is set.  Growing keeps nothing of the contents.
+struct GrowBuffer {
+  void* ptr = nullptr;
+  size_t bytes = 0;
+  bool pinned_host = false;
+  // At least `want` bytes (exactly `want` when it has to grow).  `wait_on`: work enqueued on that stream may still use
+  // the old allocation -- it is waited for before the allocation goes.  On failure the buffer is left empty.
+  hipError_t grow(size_t want, const hipStream_t* wait_on = nullptr) {
+    if (want <= bytes) return hipSuccess;
+    if (wait_on)
+      if (hipError_t e = hipStreamSynchronize(*wait_on)) return e;
+    if (hipError_t e = release()) return e;
+    hipError_t e = pinned_host ? hipHostMalloc(&ptr, want, hipHostMallocDefault) : try_malloc(&ptr, want);
+    if (e != hipSuccess) {
+      if (pinned_host) (void)hipGetLastError();   // (as try_malloc)
+      ptr = nullptr;
+      return e;
+    }
+    bytes = want;
+    return hipSuccess;
+  }
+  hipError_t release() {
+    void* p = ptr;
+    ptr = nullptr;
+    bytes = 0;
+    if (!p) return hipSuccess;
+    return pinned_host ? hipHostFree(p) : hipFree(p);
+  }
+};
+
 template <typename T>
 inline T ceil_div(T a, T b) {
   return (a + b - 1) / b;

@@ -32,6 +32,12 @@ struct Slab {
   long long r0, r1;
 };
 
+struct LeapPlan {   // see plan_leap
+  int rounds = 0;   // 0: no leap
+  int rank = 0;
+  double per_round = 0.0;   // rows expected to beat the threshold per round and query: rank (rho - 1)
+};
+
 }  // namespace proqa
 
 struct proqa_index {
@@ -53,7 +59,7 @@ struct proqa_index {
   float* ub_filter = nullptr;              // workspace [ws_nq_pad]
   int64_t n = 0;
   int64_t capacity = 0;
-  // search workspace (grown on demand)
+  // search workspace (grown on demand: ensure_workspace / free_workspace)
   int64_t ws_nq_pad = 0;
   int ws_k = 0;
   void* xq_pad = nullptr;
@@ -64,99 +70,75 @@ struct proqa_index {
   unsigned long long* bound_keys = nullptr;
   float* ub = nullptr;
   unsigned char* done = nullptr;
-  // candidate records of one filter launch (see CandidateStore in mips_kernels.h)
-  proqa::WaveRecord* lane_log = nullptr;
-  unsigned* lane_cnt = nullptr;
-  proqa::WaveRecord* spill_log = nullptr;
-  unsigned* spill_cnt = nullptr;
-  size_t store_records = 0;                // what the store holds: lane-list records, lane lists, spill slots
-  size_t store_lists = 0;
-  size_t store_slots = 0;
+  // Buffers grown on demand, each the one owner of its allocation (proqa_index_free releases them from one list):
+  // candidate records of one filter launch (see CandidateStore in mips_kernels.h; ensure_store / store_of)
+  proqa::GrowBuffer lane_log, lane_cnt, spill_log, spill_cnt;
+  proqa::GrowBuffer stage_dev;             // staging for host-pointer add/search
+  proqa::GrowBuffer stage_pinned{nullptr, 0, /*pinned_host=*/true};   // the host side of the same
+  proqa::GrowBuffer boot_scores;           // bootstrap (see mips_kernels.hip): score matrix of the first rows, [ws_nq_pad, boot_stride] floats
+  // int8 nomination scan (mips_kernels.hip): an int8 copy of the centred, per-dimension-scaled rows, built lazily by the first
+  // search that can use it and rebuilt when the rows changed (rows_epoch); the fp16 rows stay the data every score comes from
+  proqa::GrowBuffer xb8;                   // signed char rows
+  proqa::GrowBuffer blk8;                  // float2 per 32-row block: scale and largest integer row norm (FilterArgsI8::blk)
+  // compact lists the re-scoring of an int8 one-pass launch writes for its merge (one_pass_big_launch_i8): records, lengths
+  proqa::GrowBuffer emit_log, emit_cnt;
+  proqa::GrowBuffer rescue_buf;            // ids, fp16 query rows, D and I rows of the rescue batch (rescue_short_queries)
   unsigned* overflow = nullptr;            // [kMaxRounds] device
   proqa::SearchMirror* mirror = nullptr;   // pinned host memory the finalize kernel reports into (overflow words, candidates)
   unsigned long long* stat_dev = nullptr;  // [ws_nq_pad] candidates per query (part of the workspace)
-  void* stage_dev = nullptr;               // staging for host-pointer add/search
-  size_t stage_bytes = 0;
-  void* stage_pinned = nullptr;
-  size_t stage_pinned_bytes = 0;
   hipStream_t io_stream = nullptr;         // stream of the host-pointer search (proqa_index_search)
   hipEvent_t ev[2] = {nullptr, nullptr};
   hipEvent_t ev_filter[2 * 96] = {};       // per-round brackets, created when profiling is on
   bool profile = false;
   bool allow_rounding = false;             // accept fp32 inputs that are not exactly representable in fp16
   unsigned* inexact = nullptr;             // device counters: {not exact in fp16, beyond the fp16 range}
-  // bootstrap (see mips_kernels.hip): score matrix of the first rows, [ws_nq_pad, boot_stride] floats
-  float* boot_scores = nullptr;
-  size_t boot_floats = 0;
   int bootstrap_rows = 4096;               // 0 disables it
   bool bootstrap_auto = true;              // not configured by the caller: 8192 rows where that saves candidates (page_enqueue)
-  // int8 nomination scan (mips_kernels.hip): an int8 copy of the centred, per-dimension-scaled rows, built lazily by the first
-  // search that can use it and rebuilt when the rows changed (rows_epoch); the fp16 rows stay the data every score comes from
-  signed char* xb8 = nullptr;
-  float2* blk8 = nullptr;                  // per 32-row block: scale and largest integer row norm (FilterArgsI8::blk)
-  int64_t capacity8 = 0;
   float* col = nullptr;                    // device [3][128]: mean, 127 / c, c / 127
   float* col_partial = nullptr;            // device [kColStatGroups][3][128]
   proqa::QuantStats* qstats = nullptr;     // device
   uint64_t rows_epoch = 1;                 // bumped by every change of the rows
   uint64_t q8_epoch = 0;                   // rows_epoch the int8 copy was built for (0: never)
   bool q8_usable = false;                  // that copy can be scanned (finite statistics)
-  bool q8_unprofitable = false;            // a search on this copy nominated far too many rows: the int8 rounds are SUSPENDED (fp16 scan)
-  // ... until a re-probe succeeds: the q8_probe_after-th eligible search after the suspension runs the int8 rounds again;
-  // a probe that fails doubles the distance (8, 16, 32, 64, 64, ...), one that succeeds lifts the suspension
-  int q8_suspended_searches = 0;           // eligible searches that ran on the fp16 rows since the suspension / the last failed probe
-  int q8_probe_after = 0;
+  // what the automatic mode has learnt about the current copy; ensure_q8 starts it afresh, and the second search of
+  // rescue_short_queries leaves it as it found it
+  struct Q8Auto {
+    bool unprofitable = false;             // a search on this copy nominated far too many rows: the int8 rounds are SUSPENDED (fp16 scan)
+    // ... until a re-probe succeeds: the probe_after-th eligible search after the suspension runs the int8 rounds again;
+    // a probe that fails doubles the distance (8, 16, 32, 64, 64, ...), one that succeeds lifts the suspension
+    int suspended_searches = 0;            // eligible searches that ran on the fp16 rows since the suspension / the last failed probe
+    int probe_after = 0;
+    // the 1024-key nominating merge (eight workgroups per CU) is sized for rows that nominate ~2 x their candidates; rows that
+    // nominate more overflow it although the 2048-key merge would hold them: the first such search switches this index to the
+    // larger merge instead of suspending the int8 rounds (until the rows change)
+    bool small_merge_ok = true;
+    int searches_on_copy = 0;              // searches that scanned the current copy (see q8_short_lived_builds)
+  } q8_auto;
   bool q8_build_due = false;               // an enqueued (begin / finish) search wanted the int8 copy: _finish builds it
   // an index whose rows change between searches (add, search, add, search, ...) would pay three passes over all rows per
   // search for a copy that serves one: after two builds in a row that served at most one search each, automatic mode
   // leaves the first search after a change on the fp16 rows and rebuilds when a second search finds the rows unchanged
-  int q8_searches_on_copy = 0;             // searches that scanned the current copy
   int q8_short_lived_builds = 0;           // consecutive builds whose copy served <= 1 search
   uint64_t q8_seen_epoch = 0;              // rows_epoch of the last search that found the copy stale
   int nominate_mode = 1;                   // 0 off, 1 automatic, 2 always (no profitability check); proqa_index_configure_nomination
-  bool q8_active = false;                  // the search being enqueued runs its rounds on the int8 copy
-  int64_t pending_nq = 0;                  // queries of the search being enqueued (the row-split launch of small batches reads it)
-  double page_growth = 2.0;                // growth cap of the rounds being enqueued (the nominating merge's size follows it)
-  // the 1024-key nominating merge (eight workgroups per CU) is sized for rows that nominate ~2 x their candidates; rows that
-  // nominate more overflow it although the 2048-key merge would hold them: the first such search switches this index to the
-  // larger merge instead of suspending the int8 rounds (until the rows change)
-  bool small_merge_ok = true;
-  bool used_small_merge = false;           // a round of the search being enqueued took the 1024-key merge
-  unsigned overflow_bits = 0;              // OR of the overflow words of the search's rounds (bit 1 alone: only a merge's capacity)
   // Leaping rounds (plan_leap below): thresholds taken at rank j < k of the running list, a quarter of the candidates per row
   // scanned, so half the rounds or fewer; a round in which fewer than k rows reach its threshold is re-scanned by the
   // overflow-safe path (rows in an order the first rows do not stand for).  Such a search pauses the leaps of this index for
-  // leap_pause searches (16, then doubling up to 1024; a search that leaps cleanly clears it)
+  // leap.pause searches (16, then doubling up to 1024; a search that leaps cleanly clears it)
   int leap_mode = 1;                       // 0 never, 1 automatic (developer switch PROQA_LEAP)
-  int leap_pause = 0;                      // length of the current pause
-  int leap_skip = 0;                       // searches of that pause still to go
-  int leap_strikes = 0;                    // what the recent shortfalls cost (note_leap): a pause at eight
-  bool leap_active = false;                // the search being enqueued leaps
+  struct LeapPause {
+    int pause = 0;                         // length of the current pause
+    int skip = 0;                          // searches of that pause still to go
+    int strikes = 0;                       // what the recent shortfalls cost (note_leap): a pause at eight
+    uint64_t epoch = 0;                    // rows_epoch the pause belongs to (changed rows start afresh)
+  } leap;
+  // the plans of the last search are kept: the same index, batch class and k ask again and again
   long long leap_key[6] = {0, 0, 0, 0, 0, 0};   // what the kept plan was made for
-  int leap_plan_rounds = 0, leap_plan_rank = 0;
-  double leap_plan_per_round = 0.0;
+  proqa::LeapPlan leap_plan;
   long long leap_sample_key[4] = {0, 0, 0, 0};   // the same for the sample rounds of the one-pass search of a large k
-  int leap_sample_rounds = 0, leap_sample_rank = 0;
+  proqa::LeapPlan leap_sample_plan;
   int leap_logged = 0;                     // the plan last reported under PROQA_LOG
-  uint64_t leap_epoch = 0;                 // rows_epoch the pause belongs to (changed rows start afresh)
-  int round_next_rank = 0, round_leap_check = 0, round_bit = 0;   // MergeArgs of the round being enqueued
-  // queries a leaping round left short (at most kRescueMax of them, nothing else overflowed) are searched again on ordinary
-  // rounds as a small batch of their own, instead of re-scanning the flagged slabs for every query (rescue_short_queries)
   unsigned* short_rounds = nullptr;        // workspace [ws_nq_pad]: bit r = fell short in round r
-  struct Rescue {
-    std::vector<int> ids;                  // the short queries of the search that just completed (empty: nothing to do)
-    float* D = nullptr;
-    long long* I = nullptr;
-    int k = 0, out_stride = 0;
-    long long idx_offset = 0;
-    hipStream_t st = nullptr;
-  } rescue;
-  // compact lists the re-scoring of an int8 one-pass launch writes for its merge (one_pass_big_launch_i8)
-  proqa::WaveRecord* emit_log = nullptr;
-  unsigned* emit_cnt = nullptr;
-  size_t emit_records = 0, emit_counts = 0;
-  void* rescue_buf = nullptr;              // device: ids, fp16 query rows, D and I rows of the rescue batch
-  size_t rescue_bytes = 0;
   signed char* xq8 = nullptr;              // workspace [ws_nq_pad,128]
   proqa::NominateParams* qparams = nullptr;   // workspace [ws_nq_pad]
   unsigned long long* stat_nom = nullptr;  // workspace [ws_nq_pad] rows re-scored per query
@@ -164,22 +146,39 @@ struct proqa_index {
   int first_slab_rows = 256;
   int growth = 0;                          // 0 = automatic (see growth_for)
   proqa_search_stats stats = {};
-  // a search enqueued by proqa_index_search_begin_device whose host-side completion is still due
-  struct Pending {
-    bool active = false;
-    int qw = 0;
-    unsigned n_qtiles = 0;
-    int64_t nq = 0, nq_pad = 0;
-    int k = 0, dtype = 0;
-    const void* xq_dev = nullptr;
-    float* D = nullptr;
-    long long* I = nullptr;
-    long long idx_offset = 0;
-    hipStream_t st = nullptr;
-    uint32_t* status_dev = nullptr;
-    std::vector<proqa::Slab> slabs;
-    long long boot = 0;
-  } pending;
+  // What the search in progress has to remember between its enqueue and its completion.  Every search starts by
+  // assigning `search = {}`; nothing of it means anything to the next one.
+  struct Search {
+    bool q8_active = false;                // its rounds run on the int8 copy
+    bool leap_active = false;              // it leaps
+    bool used_small_merge = false;         // one of its rounds took the 1024-key merge
+    unsigned overflow_bits = 0;            // OR of the overflow words of its rounds (bit 1 alone: only a merge's capacity)
+    // queries a leaping round left short (at most kRescueMax of them, nothing else overflowed) are searched again on ordinary
+    // rounds as a small batch of their own, instead of re-scanning the flagged slabs for every query (rescue_short_queries)
+    struct Rescue {
+      std::vector<int> ids;                // the short queries of the search that just completed (empty: nothing to do)
+      float* D = nullptr;
+      long long* I = nullptr;
+      int k = 0, out_stride = 0;
+      long long idx_offset = 0;
+      hipStream_t st = nullptr;
+    } rescue;
+    // a search enqueued by proqa_index_search_begin_device whose host-side completion is still due
+    struct Deferred {
+      bool active = false;
+      int qw = 0;
+      unsigned n_qtiles = 0;
+      int64_t nq = 0, nq_pad = 0;
+      int k = 0, dtype = 0;
+      const void* xq_dev = nullptr;
+      float* D = nullptr;
+      long long* I = nullptr;
+      long long idx_offset = 0;
+      hipStream_t st = nullptr;
+      std::vector<proqa::Slab> slabs;
+      long long boot = 0;
+    } deferred;
+  } search;
 };
 
 namespace proqa {
@@ -187,9 +186,16 @@ namespace {
 
 constexpr int kMaxRounds = kOverflowWords;   // 96
 
-// developer switches, read once: PROQA_DEBUG_CAND prints the cumulative candidate count after every
-// round (adds a host sync per round), PROQA_DEBUG_ROUNDS prints per-round filter times when profiling
+// Environment switches: a flag is debug_flag (set at all), an integer env_int; the few fractional ones are read with getenv /
+// atof where they are used.  The k... constants are read once, when the library is loaded; a switch that one process may
+// alternate is read by the search that obeys it.
 bool debug_flag(const char* name) { return getenv(name) != nullptr; }
+int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v && *v ? atoi(v) : dflt;
+}
+// developer switches: PROQA_DEBUG_CAND prints the cumulative candidate count after every
+// round (adds a host sync per round), PROQA_DEBUG_ROUNDS prints per-round filter times when profiling
 const bool kDebugCand = debug_flag("PROQA_DEBUG_CAND");
 const bool kDebugRounds = debug_flag("PROQA_DEBUG_ROUNDS");
 // k x growth up to which a nominating round takes the 1024-key merge (developer / test override: PROQA_NOM_SMALL_MERGE_LIMIT)
@@ -275,14 +281,8 @@ int reserve_rows(proqa_index* idx, int64_t rows) {
 }
 
 int ensure_stage(proqa_index* idx, size_t bytes) {
-  if (bytes > idx->stage_bytes) {
-    if (idx->stage_dev) PROQA_HIP(hipFree(idx->stage_dev));
-    idx->stage_dev = nullptr;
-    idx->stage_bytes = 0;
-    hipError_t e = try_malloc(&idx->stage_dev, bytes);
-    if (e != hipSuccess) return fail(PROQA_ENOMEM, "hipMalloc staging %zu B: %s", bytes, hipGetErrorString(e));
-    idx->stage_bytes = bytes;
-  }
+  const hipError_t e = idx->stage_dev.grow(bytes);
+  if (e != hipSuccess) return fail(PROQA_ENOMEM, "hipMalloc staging %zu B: %s", bytes, hipGetErrorString(e));
   return PROQA_OK;
 }
 
@@ -299,41 +299,27 @@ bool nomination_eligible(const proqa_index* idx, int k) {
 int ensure_q8(proqa_index* idx, hipStream_t st) {
   if (idx->q8_epoch == idx->rows_epoch) return PROQA_OK;
   idx->q8_usable = false;
-  idx->q8_unprofitable = false;
-  idx->q8_suspended_searches = 0;
-  idx->q8_probe_after = 0;
   idx->q8_build_due = false;
-  if (idx->q8_epoch != 0) idx->q8_short_lived_builds = idx->q8_searches_on_copy <= 1 ? idx->q8_short_lived_builds + 1 : 0;
-  idx->q8_searches_on_copy = 0;
-  idx->small_merge_ok = true;
+  if (idx->q8_epoch != 0) idx->q8_short_lived_builds = idx->q8_auto.searches_on_copy <= 1 ? idx->q8_short_lived_builds + 1 : 0;
+  idx->q8_auto = {};
   if (!idx->col) {
     PROQA_HIP(hipMalloc((void**)&idx->col, 3 * kDim * sizeof(float)));
     PROQA_HIP(hipMalloc((void**)&idx->col_partial, (size_t)kColStatGroups * 3 * kDim * sizeof(float)));
     PROQA_HIP(hipMalloc((void**)&idx->qstats, sizeof(QuantStats)));
   }
-  if (idx->n > idx->capacity8) {
-    PROQA_HIP(hipStreamSynchronize(st));
-    if (idx->xb8) PROQA_HIP(hipFree(idx->xb8));
-    if (idx->blk8) PROQA_HIP(hipFree(idx->blk8));
-    idx->xb8 = nullptr;
-    idx->blk8 = nullptr;
-    idx->capacity8 = 0;
+  if ((size_t)idx->n * kDim > idx->xb8.bytes) {   // (the two grow together: rows for the capacity of the fp16 buffer)
     const int64_t cap = round_up<int64_t>(std::max(idx->n, idx->capacity), kStageRows);
-    if (try_malloc((void**)&idx->xb8, (size_t)cap * kDim) != hipSuccess ||
-        try_malloc((void**)&idx->blk8, (size_t)(cap / 32 + 16) * sizeof(float2)) != hipSuccess) {
-      if (idx->rescue_buf) (void)hipFree(idx->rescue_buf);
-  if (idx->emit_log) (void)hipFree(idx->emit_log);
-  if (idx->emit_cnt) (void)hipFree(idx->emit_cnt);
-  if (idx->xb8) (void)hipFree(idx->xb8);
-      idx->xb8 = nullptr;
+    if (idx->xb8.grow((size_t)cap * kDim, &st) != hipSuccess ||
+        idx->blk8.grow((size_t)(cap / 32 + 16) * sizeof(float2), &st) != hipSuccess) {
+      (void)idx->xb8.release();
+      (void)idx->blk8.release();
       idx->q8_epoch = idx->rows_epoch;   // no room for the copy: this index is searched on its fp16 rows
       return PROQA_OK;
     }
-    idx->capacity8 = cap;
   }
   PROQA_HIP(hipMemsetAsync(idx->qstats, 0, sizeof(QuantStats), st));
   PROQA_HIP(launch_column_stats(idx->xb, idx->n, idx->col_partial, idx->col, idx->qstats, st));
-  PROQA_HIP(launch_quantise_rows_i8(idx->xb, idx->n, idx->col, idx->xb8, idx->blk8, idx->qstats, st));
+  PROQA_HIP(launch_quantise_rows_i8(idx->xb, idx->n, idx->col, (signed char*)idx->xb8.ptr, (float2*)idx->blk8.ptr, idx->qstats, st));
   QuantStats h;
   PROQA_HIP(hipMemcpyAsync(&h, idx->qstats, sizeof h, hipMemcpyDeviceToHost, st));
   PROQA_HIP(hipStreamSynchronize(st));
@@ -353,11 +339,11 @@ int ingest_f32_piece(proqa_index* idx, int64_t row, int64_t m, const void* src_h
   if (int rc = ensure_stage(idx, (size_t)kAddPieceRows * kDim * 4)) return rc;
   char* dst = idx->xb + (size_t)row * kDim * 2;
   if (pinned)
-    PROQA_HIP(hipMemcpyAsync(idx->stage_dev, src_host, (size_t)m * kDim * 4, hipMemcpyHostToDevice, st));
+    PROQA_HIP(hipMemcpyAsync(idx->stage_dev.ptr, src_host, (size_t)m * kDim * 4, hipMemcpyHostToDevice, st));
   else
-    PROQA_HIP(hipMemcpy(idx->stage_dev, src_host, (size_t)m * kDim * 4, hipMemcpyHostToDevice));
+    PROQA_HIP(hipMemcpy(idx->stage_dev.ptr, src_host, (size_t)m * kDim * 4, hipMemcpyHostToDevice));
   PROQA_HIP(hipMemsetAsync(idx->inexact, 0, 2 * sizeof(unsigned), st));
-  PROQA_HIP(launch_convert_f32_to_f16((const float*)idx->stage_dev, dst, m * kDim, idx->inexact, st));
+  PROQA_HIP(launch_convert_f32_to_f16((const float*)idx->stage_dev.ptr, dst, m * kDim, idx->inexact, st));
   unsigned bad = 0;
   if (int rc = read_inexact(idx, "index_add", st, &bad)) return rc;
   if (bad && !idx->allow_rounding && !idx->exact) {
@@ -366,7 +352,7 @@ int ingest_f32_piece(proqa_index* idx, int64_t row, int64_t m, const void* src_h
     if (int rc = enable_exact(idx, st)) return rc;
     if (int rc = finish_rows_exact(idx, idx->n, row - idx->n, nullptr, st)) return rc;   // earlier pieces were exact
   }
-  if (int rc = finish_rows_exact(idx, row, m, (const float*)idx->stage_dev, st)) return rc;
+  if (int rc = finish_rows_exact(idx, row, m, (const float*)idx->stage_dev.ptr, st)) return rc;
   if (idx->exact) PROQA_HIP(hipStreamSynchronize(st));   // stage_dev is reused by the next piece
   return PROQA_OK;
 }
@@ -406,43 +392,24 @@ struct NpyRing {
   }
 };
 
-void free_store(proqa_index* idx) {
-  void* ptrs[] = {idx->lane_log, idx->lane_cnt, idx->spill_log, idx->spill_cnt};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  idx->lane_log = nullptr;
-  idx->lane_cnt = nullptr;
-  idx->spill_log = nullptr;
-  idx->spill_cnt = nullptr;
-  idx->store_records = 0;
-  idx->store_lists = 0;
-  idx->store_slots = 0;
+void release_store(proqa_index* idx) {
+  for (GrowBuffer* b : {&idx->lane_log, &idx->lane_cnt, &idx->spill_log, &idx->spill_cnt}) (void)b->release();
 }
 
 void free_workspace(proqa_index* idx) {
-  void* ptrs[] = {idx->xq_pad, idx->tau, idx->run_n, idx->run_keys, idx->stat_dev, idx->bound_keys, idx->ub, idx->done,
-                  idx->xq32, idx->margin, idx->tau_filter, idx->ub_filter, idx->xq8, idx->qparams, idx->stat_nom, idx->short_rounds};
-  idx->short_rounds = nullptr;
-  idx->xq8 = nullptr;
-  idx->qparams = nullptr;
-  idx->stat_nom = nullptr;
-  idx->xq32 = nullptr;
-  idx->margin = nullptr;
-  idx->tau_filter = nullptr;
-  idx->ub_filter = nullptr;
-  idx->bound_keys = nullptr;
-  idx->ub = nullptr;
-  idx->done = nullptr;
-  for (void* p : ptrs)
+  for (void* p : {(void*)idx->xq_pad, (void*)idx->tau, (void*)idx->run_n, (void*)idx->run_keys, (void*)idx->stat_dev, (void*)idx->bound_keys,
+                  (void*)idx->ub, (void*)idx->done, (void*)idx->xq32, (void*)idx->margin, (void*)idx->tau_filter, (void*)idx->ub_filter,
+                  (void*)idx->xq8, (void*)idx->qparams, (void*)idx->stat_nom, (void*)idx->short_rounds})
     if (p) (void)hipFree(p);
   idx->xq_pad = nullptr;
-  idx->tau = nullptr;
-  idx->run_n = nullptr;
-  idx->run_keys = nullptr;
-  idx->stat_dev = nullptr;
+  idx->tau = idx->ub = idx->xq32 = idx->margin = idx->tau_filter = idx->ub_filter = nullptr;
+  idx->run_n = idx->short_rounds = nullptr;
+  idx->run_keys = idx->stat_dev = idx->bound_keys = idx->stat_nom = nullptr;
+  idx->done = nullptr;
+  idx->xq8 = nullptr;
+  idx->qparams = nullptr;
   idx->ws_nq_pad = 0;
   idx->ws_k = 0;
-  free_store(idx);
 }
 
 int ensure_workspace(proqa_index* idx, int64_t nq_pad, int k) {
@@ -450,6 +417,7 @@ int ensure_workspace(proqa_index* idx, int64_t nq_pad, int k) {
   const int64_t q = std::max(nq_pad, idx->ws_nq_pad);
   const int kk = std::max(k, idx->ws_k);
   free_workspace(idx);
+  release_store(idx);   // (the candidate store goes with the workspace and is sized again by the next launch)
   PROQA_HIP(hipMalloc(&idx->xq_pad, (size_t)q * kDim * 2));
   PROQA_HIP(hipMalloc((void**)&idx->tau, (size_t)q * sizeof(float)));
   PROQA_HIP(hipMalloc((void**)&idx->run_n, (size_t)q * sizeof(unsigned)));
@@ -479,24 +447,26 @@ int ensure_store(proqa_index* idx, unsigned chunks, unsigned n_qtiles, int64_t n
   const size_t lists = (size_t)chunks * nq_pad * 2;
   const size_t records = lists * lane_cap;
   const size_t slots = (size_t)chunks * n_qtiles * kFilterWaves;
-  if (records <= idx->store_records && lists <= idx->store_lists && slots <= idx->store_slots) return PROQA_OK;
-  const size_t want_records = std::max(records, idx->store_records), want_lists = std::max(lists, idx->store_lists),
-               want_slots = std::max(slots, idx->store_slots);
-  free_store(idx);
+  // (bytes: the lane lists' records, their lengths, the spill slots' records, their lengths)
+  const size_t need[4] = {records * sizeof(WaveRecord), lists * sizeof(unsigned), slots * kSpillCap * sizeof(WaveRecord), slots * sizeof(unsigned)};
+  GrowBuffer* const buf[4] = {&idx->lane_log, &idx->lane_cnt, &idx->spill_log, &idx->spill_cnt};
+  size_t want[4];
+  bool fits = true;
+  for (int i = 0; i < 4; ++i) {
+    fits = fits && need[i] <= buf[i]->bytes;
+    want[i] = std::max(need[i], buf[i]->bytes);
+  }
+  if (fits) return PROQA_OK;
+  release_store(idx);   // all four before any is allocated again: on a full GPU the old store is the room for the new one
   // developer/test switch, read on this (rare) growth path only: a store above the limit fails the way a full GPU fails
   // it -- by a hipMalloc that really fails (1 EiB), so that HIP's sticky error state is the real one
-  const char* lim = getenv("PROQA_DEBUG_STORE_LIMIT_MB");
-  const bool refuse = lim && want_records * sizeof(WaveRecord) > ((size_t)atoll(lim) << 20);
-  hipError_t e = try_malloc((void**)&idx->lane_log, refuse ? (size_t)1 << 60 : want_records * sizeof(WaveRecord));
+  const int limit_mb = env_int("PROQA_DEBUG_STORE_LIMIT_MB", -1);
+  const bool refuse = limit_mb >= 0 && want[0] > ((size_t)limit_mb << 20);
+  const hipError_t e = idx->lane_log.grow(refuse ? (size_t)1 << 60 : want[0]);
   if (e != hipSuccess)
     return fail(PROQA_ENOMEM, "search: candidate store of %zu lists x %u records: %s (fewer queries per call need less)", lists,
                 lane_cap, hipGetErrorString(e));
-  idx->store_records = want_records;
-  PROQA_HIP(hipMalloc((void**)&idx->lane_cnt, want_lists * sizeof(unsigned)));
-  idx->store_lists = want_lists;
-  PROQA_HIP(hipMalloc((void**)&idx->spill_log, want_slots * kSpillCap * sizeof(WaveRecord)));
-  PROQA_HIP(hipMalloc((void**)&idx->spill_cnt, want_slots * sizeof(unsigned)));
-  idx->store_slots = want_slots;
+  for (int i = 1; i < 4; ++i) PROQA_HIP(buf[i]->grow(want[i]));
   return PROQA_OK;
 }
 
@@ -577,10 +547,6 @@ std::vector<Slab> plan_slabs(long long n, int first, double growth, long long st
 // (1e-8: one second search in ~10^4 searches of 2032 queries).  The result never depends on any of this.
 // (developer switches, read at every search so that one process can alternate them: PROQA_LEAP=0 never; PROQA_LEAP_ROUNDS /
 // PROQA_LEAP_RANK / PROQA_LEAP_EPS fix the rounds behind the bootstrap, the rank, the probability)
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
 constexpr int kLeapMaxK = 128;
 constexpr double kLeapEps = 1e-8;
 // Queries that leaping rounds left short are searched again by themselves -- all of them, however many: a second search of s <= nq
@@ -588,7 +554,7 @@ constexpr double kLeapEps = 1e-8;
 // every query ~1.7 x (developer / test switch PROQA_LEAP_RESCUE_MAX: at most that many, 0 = always the slab re-scan).  Up to
 // kRescueCheap of them count as a cheap shortfall (note_leap).
 constexpr int kRescueCheap = 256;
-const int kRescueMax = getenv("PROQA_LEAP_RESCUE_MAX") ? atoi(getenv("PROQA_LEAP_RESCUE_MAX")) : (1 << 30);
+const int kRescueMax = env_int("PROQA_LEAP_RESCUE_MAX", 1 << 30);
 
 // P(fewer than k rows beat the rank-j score after the rows seen grew by the factor rho): the negative-binomial sum
 double leap_fail_probability(int k, int j, double rho) {
@@ -605,12 +571,7 @@ int leap_rank(int k, double rho, double eps) {
     if (leap_fail_probability(k, j, rho) <= eps) return j;
   return k;
 }
-struct LeapPlan {
-  int rounds = 0;   // 0: no leap
-  int rank = 0;
-  double per_round = 0.0;   // rows expected to beat the threshold per round and query: rank (rho - 1)
-};
-// The schedule: `rounds` rounds of equal growth behind the bootstrap, the one that minimises rounds x (c + rows per round),
+// The schedule (LeapPlan): `rounds` rounds of equal growth behind the bootstrap, the one that minimises rounds x (c + rows per round),
 // c = what a round costs beside the rows it logs, in rows per query: ~50 for a batch that fills the chip, ~120 for the
 // batches of <= 256 queries, whose rounds are launch latencies (interleaved sweeps, scripts/dev_leap_sweep.py, ABLATIONS R6.13:
 // 2032 queries: 4-5 rounds at 18M rows, 3 at 2.25M; <= 256 queries: 3 and 2).  The rows per round are capped by what the
@@ -670,10 +631,10 @@ LaunchGeom geometry(long long slab_rows, unsigned n_qtiles, bool single_stage, i
 
 CandidateStore store_of(const proqa_index* idx, unsigned nq_pad, unsigned n_qtiles, unsigned lane_cap, unsigned n_chunks) {
   CandidateStore st;
-  st.lane_log = idx->lane_log;
-  st.lane_cnt = idx->lane_cnt;
-  st.spill_log = idx->spill_log;
-  st.spill_cnt = idx->spill_cnt;
+  st.lane_log = (WaveRecord*)idx->lane_log.ptr;
+  st.lane_cnt = (unsigned*)idx->lane_cnt.ptr;
+  st.spill_log = (WaveRecord*)idx->spill_log.ptr;
+  st.spill_cnt = (unsigned*)idx->spill_cnt.ptr;
   st.nq_pad = nq_pad;
   st.n_qtiles = n_qtiles;
   st.lane_cap = lane_cap;
@@ -724,57 +685,95 @@ bool merge_stamps_dump(MergeArgs& ma, unsigned nq_pad, hipStream_t st) {
 }
 #endif
 
-int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, unsigned nq_pad, int k,
-              bool inclusive, bool dense, bool bounded, unsigned* overflow_word, hipStream_t st, hipEvent_t f0,
-              hipEvent_t f1, const RoundShape& shape = RoundShape()) {
+// row-split launches of the int8 scan (mips_filter_i8<SPLIT>), at most 128 queries: the 1 / 2 / 4 query blocks that hold
+// queries are replicated over the eight waves, which share the units of the stream (and the lists of their queries);
+// 0: more queries than that, the ordinary launch
+unsigned q_blocks_for(int64_t nq) { return nq > 128 ? 0u : nq <= 32 ? 1u : nq <= 64 ? 2u : 4u; }
+
+// an int8 launch over the rows of `slab` in the chunks of `g`, for the `nq` queries of the search, into the handle's store
+FilterArgsI8 filter_args_i8(const proqa_index* idx, const Slab& slab, const LaunchGeom& g, unsigned n_qtiles, unsigned nq_pad, int64_t nq,
+                            unsigned* overflow_word) {
+  FilterArgsI8 fa;
+  fa.xq8 = idx->xq8;
+  fa.xb8 = (const signed char*)idx->xb8.ptr;
+  fa.slab_row0 = slab.r0;
+  fa.slab_row1 = slab.r1;
+  fa.rows_per_chunk = g.rows_per_chunk;
+  fa.tau = idx->tau;
+  fa.qp = idx->qparams;
+  fa.blk = (const float2*)idx->blk8.ptr;
+  fa.store = store_of(idx, nq_pad, n_qtiles, kNominateLaneCap, round_up<unsigned>(g.chunks, 8));
+  fa.overflow = overflow_word;
+  fa.q_blocks = q_blocks_for(nq);
+  return fa;
+}
+
+// what every merge is told: the lists of `n_chunks` chunks it reads and the running lists it merges them into.  All else is
+// zero: the plain, exact-float32, nominating and compact merges set what they need.
+MergeArgs merge_args(const proqa_index* idx, const CandidateStore& store, unsigned n_chunks, int qw, int k, int sort_cap,
+                     unsigned* overflow_word) {
+  MergeArgs ma = {};
+  ma.store = store;
+  ma.n_chunks = n_chunks;
+  ma.qw = (unsigned)qw;
+  ma.run_keys = idx->run_keys;
+  ma.run_n = idx->run_n;
+  ma.tau = idx->tau;
+  ma.k = k;
+  ma.sort_cap = sort_cap;
+  ma.stat_candidates = idx->stat_dev;
+  ma.overflow = overflow_word;
+  return ma;
+}
+
+// developer (PROQA_DEBUG_CAND): waits for the stream, then the sum of a per-query statistic over its first `n` queries
+unsigned long long debug_stat_sum(const unsigned long long* stat, int64_t n, hipStream_t st) {
+  (void)hipStreamSynchronize(st);
+  std::vector<unsigned long long> per_query((size_t)n);
+  (void)hipMemcpy(per_query.data(), stat, (size_t)n * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+  unsigned long long sum = 0;
+  for (unsigned long long v : per_query) sum += v;
+  return sum;
+}
+
+// What a round is told beside its slab; the defaults are a forward round of the first page on the fp16 rows.
+struct Round {
+  bool inclusive = false;   // overflow-safe re-scan: scores >= the threshold, duplicates removed by the merge
+  bool dense = false;       // every row is logged (threshold still -inf, or a leaf of the re-scan)
+  bool bounded = false;     // a page behind the first
+  // the search was set up for the int8 copy (setup_nominate): its plain forward rounds scan it, for `nq` queries (the
+  // row-split launch), under the growth cap `growth` (the size of the nominating merge)
+  bool nominate = false;
+  int64_t nq = 0;
+  double growth = 0.0;
+  int next_rank = 0, leap_check = 0, round_bit = 0;   // leaping rounds: MergeArgs of the same names
+};
+
+int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, unsigned nq_pad, int k, const Round& rd,
+              unsigned* overflow_word, hipStream_t st, hipEvent_t f0 = nullptr, hipEvent_t f1 = nullptr,
+              const RoundShape& shape = RoundShape()) {
   // rounds of the plain search (strict threshold, first page, not dense, no shape of its own) scan the int8 copy when the
   // search was set up for it: two workgroups per CU, deep lane lists instead of a spill log
-  const bool nominate = idx->q8_active && !inclusive && !dense && !bounded && !shape.want_chunks && !shape.compact;
-  if (nominate) {
-    // at most 128 queries: row-split launch (mips_filter_i8<SPLIT>) -- the 1 / 2 / 4 query blocks that hold queries are
-    // replicated over the eight waves, which share the units of the stream (and the lists of their queries)
-    unsigned q_blocks = 0;
-    if (qw == 1 && idx->pending_nq <= 128) q_blocks = idx->pending_nq <= 32 ? 1u : (idx->pending_nq <= 64 ? 2u : 4u);
+  if (rd.nominate && !rd.inclusive && !rd.dense && !rd.bounded && !shape.want_chunks && !shape.compact) {
     const unsigned want = std::max<unsigned>(64u, (unsigned)(2 * device_cu_count() / (int)n_qtiles) / 8 * 8);
     const LaunchGeom g = geometry(slab.r1 - slab.r0, n_qtiles, false, k, want);
     if (int rc = ensure_store(idx, round_up<unsigned>(g.chunks, 8), n_qtiles, nq_pad, kNominateLaneCap)) return rc;
-    FilterArgsI8 fa;
-    fa.xq8 = idx->xq8;
-    fa.xb8 = idx->xb8;
-    fa.slab_row0 = slab.r0;
-    fa.slab_row1 = slab.r1;
-    fa.rows_per_chunk = g.rows_per_chunk;
-    fa.tau = idx->tau;
-    fa.qp = idx->qparams;
-    fa.blk = idx->blk8;
-    fa.store = store_of(idx, nq_pad, n_qtiles, kNominateLaneCap, round_up<unsigned>(g.chunks, 8));
-    fa.overflow = overflow_word;
-    fa.q_blocks = q_blocks;
+    const FilterArgsI8 fa = filter_args_i8(idx, slab, g, n_qtiles, nq_pad, rd.nq, overflow_word);
     if (f0) PROQA_HIP(hipEventRecord(f0, st));
     PROQA_HIP(launch_filter_i8(fa, qw, g.grid, st));
     if (f1) PROQA_HIP(hipEventRecord(f1, st));
-    MergeArgs ma = {};
-    ma.store = fa.store;
-    ma.n_chunks = g.chunks;
-    ma.qw = (unsigned)qw;
-    ma.run_keys = idx->run_keys;
-    ma.run_n = idx->run_n;
-    ma.tau = idx->tau;
-    ma.k = k;
-    ma.sort_cap = sort_capacity(k);
-    ma.stat_candidates = idx->stat_dev;
-    ma.overflow = overflow_word;
+    MergeArgs ma = merge_args(idx, fa.store, g.chunks, qw, k, sort_capacity(k), overflow_word);
     ma.xq16 = idx->xq_pad;
     ma.xb16 = idx->xb;
     ma.stat_nominated = idx->stat_nom;
     // a round nominates ~2 k x growth rows per query (N(0,1) data; a query's count varies by +-30 % around that): the
     // 1024-key merge (eight workgroups per CU) where that leaves a factor ~4 of headroom, else the 2048-key one
-    ma.nom_keys = idx->small_merge_ok && (double)k * idx->page_growth <= kSmallMergeLimit ? 1024 : 2048;
-    if (ma.nom_keys == 1024) idx->used_small_merge = true;
-    ma.next_rank = idx->round_next_rank;
-    ma.leap_check = idx->round_leap_check;
+    ma.nom_keys = idx->q8_auto.small_merge_ok && (double)k * rd.growth <= kSmallMergeLimit ? 1024 : 2048;
+    if (ma.nom_keys == 1024) idx->search.used_small_merge = true;
+    ma.next_rank = rd.next_rank;
+    ma.leap_check = rd.leap_check;
     ma.short_rounds = idx->short_rounds;
-    ma.round_bit = idx->round_bit;
+    ma.round_bit = rd.round_bit;
 #ifdef PROQA_MERGE_STAMPS
     if (merge_stamps_dump(ma, nq_pad, st)) return PROQA_OK;
 #endif
@@ -783,28 +782,25 @@ int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, uns
       (void)hipStreamSynchronize(st);
       const size_t n_cnt = (size_t)fa.store.nq_pad * fa.store.n_chunks * 2;
       std::vector<unsigned> cnt(n_cnt);
-      (void)hipMemcpy(cnt.data(), idx->lane_cnt, n_cnt * sizeof(unsigned), hipMemcpyDeviceToHost);
+      (void)hipMemcpy(cnt.data(), fa.store.lane_cnt, n_cnt * sizeof(unsigned), hipMemcpyDeviceToHost);
       unsigned long long recs = 0, fullest = 0;
       for (unsigned v : cnt) {
         recs += v;
         fullest = std::max<unsigned long long>(fullest, v);
       }
-      std::vector<unsigned long long> nomv(nq_pad), candv(nq_pad);
+      std::vector<unsigned long long> nomv(nq_pad);
       (void)hipMemcpy(nomv.data(), idx->stat_nom, nq_pad * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-      (void)hipMemcpy(candv.data(), idx->stat_dev, nq_pad * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-      unsigned long long nom = 0, cand = 0;
-      for (unsigned q = 0; q < nq_pad; ++q) {
-        nom += nomv[q];
-        cand += candv[q];
-      }
+      unsigned long long nom = 0;
+      for (unsigned long long v : nomv) nom += v;
       fprintf(stderr, "int8 round rows [%lld, %lld): %u chunks x %d rows, %llu records logged (fullest list %llu of %u), cumulative nominated %llu, "
-              "cumulative candidates %llu; nominated q0..7:", slab.r0, slab.r1, g.chunks, g.rows_per_chunk, recs, fullest, kNominateLaneCap, nom, cand);
+              "cumulative candidates %llu; nominated q0..7:", slab.r0, slab.r1, g.chunks, g.rows_per_chunk, recs, fullest, kNominateLaneCap, nom,
+              debug_stat_sum(idx->stat_dev, nq_pad, st));
       for (unsigned q = 0; q < 8 && q < nq_pad; ++q) fprintf(stderr, " %llu", nomv[q]);
       fprintf(stderr, "\n");
     }
     return PROQA_OK;
   }
-  const LaunchGeom g = geometry(slab.r1 - slab.r0, n_qtiles, dense, k, shape.want_chunks);
+  const LaunchGeom g = geometry(slab.r1 - slab.r0, n_qtiles, rd.dense, k, shape.want_chunks);
   const unsigned lane_cap = shape.lane_cap ? shape.lane_cap : lane_capacity(k);
   if (int rc = ensure_store(idx, round_up<unsigned>(g.chunks, 8), n_qtiles, nq_pad, lane_cap)) return rc;
   FilterArgs fa;
@@ -815,41 +811,29 @@ int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, uns
   fa.rows_per_chunk = g.rows_per_chunk;
   // exact-float32 mode: the fp16 filter tests against thresholds moved by the error margin
   fa.tau = idx->exact ? idx->tau_filter : idx->tau;
-  fa.ub = bounded ? (idx->exact ? idx->ub_filter : idx->ub) : nullptr;
+  fa.ub = rd.bounded ? (idx->exact ? idx->ub_filter : idx->ub) : nullptr;
   fa.store = store_of(idx, nq_pad, n_qtiles, lane_cap, round_up<unsigned>(g.chunks, 8));
   fa.overflow = overflow_word;
   fa.compact = shape.compact ? 1 : 0;
   if (f0) PROQA_HIP(hipEventRecord(f0, st));
-  PROQA_HIP(launch_filter(fa, qw, inclusive, g.grid, st));
+  PROQA_HIP(launch_filter(fa, qw, rd.inclusive, g.grid, st));
   if (f1) PROQA_HIP(hipEventRecord(f1, st));
 
-  MergeArgs ma;
-  ma.store = fa.store;
-  ma.n_chunks = g.chunks;
-  ma.qw = (unsigned)qw;
-  ma.run_keys = idx->run_keys;
-  ma.run_n = idx->run_n;
-  ma.tau = idx->tau;
-  ma.k = k;
-  ma.sort_cap = shape.sort_cap ? shape.sort_cap : sort_capacity(k);
-  ma.inclusive = inclusive ? 1 : 0;
-  ma.bound_keys = bounded ? idx->bound_keys : nullptr;
-  ma.stat_candidates = idx->stat_dev;
-  ma.overflow = overflow_word;
-  ma.xq32 = idx->exact ? idx->xq32 : nullptr;
-  ma.xb32 = idx->exact ? idx->xb32 : nullptr;
-  ma.margin = idx->exact ? idx->margin : nullptr;
-  ma.tau_filter = idx->exact ? idx->tau_filter : nullptr;
-  ma.dbg = nullptr;
-  ma.compact = shape.compact ? 1 : 0;
-  ma.xq16 = nullptr;
-  ma.xb16 = nullptr;
-  ma.stat_nominated = nullptr;
-  ma.nom_keys = 0;
-  ma.next_rank = inclusive ? 0 : idx->round_next_rank;
-  ma.leap_check = inclusive ? 0 : idx->round_leap_check;
+  MergeArgs ma = merge_args(idx, fa.store, g.chunks, qw, k, shape.sort_cap ? shape.sort_cap : sort_capacity(k), overflow_word);
+  ma.inclusive = rd.inclusive ? 1 : 0;
+  ma.bound_keys = rd.bounded ? idx->bound_keys : nullptr;
+  if (idx->exact) {
+    ma.xq32 = idx->xq32;
+    ma.xb32 = idx->xb32;
+    ma.margin = idx->margin;
+    ma.tau_filter = idx->tau_filter;
+  }
+  ma.compact = fa.compact;
+  // (the overflow-safe re-scan verifies no rank and leaves the k-th best as the threshold: its callers pass none)
+  ma.next_rank = rd.next_rank;
+  ma.leap_check = rd.leap_check;
   ma.short_rounds = idx->short_rounds;
-  ma.round_bit = idx->round_bit;
+  ma.round_bit = rd.round_bit;
 #ifdef PROQA_MERGE_STAMPS
   if (merge_stamps_dump(ma, nq_pad, st)) return PROQA_OK;
 #endif
@@ -861,16 +845,8 @@ int run_round(proqa_index* idx, const Slab& slab, int qw, unsigned n_qtiles, uns
 // rounds would have after those rows.  Its overflow word is the last-but-one (the last belongs to the overflow-safe
 // re-scans).
 int run_bootstrap(proqa_index* idx, long long rows, unsigned nq_pad, int k, hipStream_t st, int run_stride = 0, int tau_rank = 0) {
-  const size_t need = (size_t)idx->ws_nq_pad * round_up<long long>(rows, 32);
-  if (need > idx->boot_floats) {
-    PROQA_HIP(hipStreamSynchronize(st));
-    if (idx->boot_scores) PROQA_HIP(hipFree(idx->boot_scores));
-    idx->boot_scores = nullptr;
-    idx->boot_floats = 0;
-    PROQA_HIP(hipMalloc((void**)&idx->boot_scores, need * sizeof(float)));
-    idx->boot_floats = need;
-  }
-  PROQA_HIP(launch_bootstrap(idx->xb, idx->xq_pad, (int)rows, nq_pad, k, idx->boot_scores, idx->run_keys, idx->run_n, idx->tau,
+  PROQA_HIP(idx->boot_scores.grow((size_t)idx->ws_nq_pad * round_up<long long>(rows, 32) * sizeof(float), &st));
+  PROQA_HIP(launch_bootstrap(idx->xb, idx->xq_pad, (int)rows, nq_pad, k, (float*)idx->boot_scores.ptr, idx->run_keys, idx->run_n, idx->tau,
                              idx->stat_dev, idx->overflow + kMaxRounds - 2, st, run_stride, tau_rank));
   return PROQA_OK;
 }
@@ -902,6 +878,7 @@ int page_enqueue(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64_
   // k beyond the select kernel's bound, or an index too small to need it.
   // (rounds on the int8 copy nominate ~2 x the candidates of an fp16 round: growth_for gives them their own, smaller growth)
   const int gqw = qw;
+  const bool q8 = idx->search.q8_active;
   long long boot = 0;
   if (use_bootstrap && idx->bootstrap_rows > 0 && !bounded && !idx->exact && page_k <= kBootstrapMaxK &&
       page_k <= idx->bootstrap_rows / 4 && idx->n >= 4ll * idx->bootstrap_rows) {
@@ -912,40 +889,35 @@ int page_enqueue(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64_
     // costs what the round did)
     // (nominating rounds: always -- the rows of the larger bootstrap are rows no round nominates from)
     if (idx->bootstrap_auto && boot * 2 <= kBootstrapMaxRows && idx->n >= 8 * boot) {
-      const double cap = std::log(1.0 + growth_for(page_k, idx->growth, gqw, idx->q8_active));
+      const double cap = std::log(1.0 + growth_for(page_k, idx->growth, gqw, q8));
       const int r1 = (int)std::ceil(std::log((double)idx->n / (double)boot) / cap - 1e-9);
       const int r2 = (int)std::ceil(std::log((double)idx->n / (double)(2 * boot)) / cap - 1e-9);
-      if (r1 == r2 || idx->q8_active) boot *= 2;
+      if (r1 == r2 || q8) boot *= 2;
     }
   }
   // every row of the first slab is a candidate (threshold -inf): it must fit one merge pass
   // (big pages: as many rows as the merge holds -- their growth per round is small, so the rounds should start high)
   const int first_cap = (sort_capacity(page_k) - page_k) / kStageRows * kStageRows;
   const int first = page_k > kPageK ? first_cap : std::min<int>(idx->first_slab_rows, first_cap);
-  double page_growth = growth_for(page_k, idx->growth, gqw, idx->q8_active);
+  double page_growth = growth_for(page_k, idx->growth, gqw, q8);
   // leaping rounds (plan_leap): behind a bootstrap, on the default schedule, unless this index is pausing them
   LeapPlan leap;
   if (boot && !bounded && !idx->exact && idx->leap_mode && env_int("PROQA_LEAP", 1) != 0 && idx->growth == 0 && page_k <= kLeapMaxK) {
-    if (idx->leap_epoch != idx->rows_epoch) {
-      idx->leap_epoch = idx->rows_epoch;
-      idx->leap_pause = idx->leap_skip = idx->leap_strikes = 0;
+    if (idx->leap.epoch != idx->rows_epoch) {
+      idx->leap = {};
+      idx->leap.epoch = idx->rows_epoch;
     }
-    if (idx->leap_skip > 0)
-      --idx->leap_skip;
+    if (idx->leap.skip > 0)
+      --idx->leap.skip;
     else {
       // (the plan of the last search is kept: the same index, batch class and k ask again and again)
-      const long long key[6] = {idx->n, boot, page_k, qw, idx->q8_active ? 1 : 0,
+      const long long key[6] = {idx->n, boot, page_k, qw, q8 ? 1 : 0,
                                 env_int("PROQA_LEAP_ROUNDS", 0) * 1000 + env_int("PROQA_LEAP_RANK", 0)};
       if (std::memcmp(key, idx->leap_key, sizeof key) != 0 || getenv("PROQA_LEAP_EPS") || getenv("PROQA_LEAP_ROUND_COST")) {
         std::memcpy(idx->leap_key, key, sizeof key);
-        const LeapPlan lp = plan_leap(idx->n, boot, page_k, qw, idx->q8_active);
-        idx->leap_plan_rounds = lp.rounds;
-        idx->leap_plan_rank = lp.rank;
-        idx->leap_plan_per_round = lp.per_round;
+        idx->leap_plan = plan_leap(idx->n, boot, page_k, qw, q8);
       }
-      leap.rounds = idx->leap_plan_rounds;
-      leap.rank = idx->leap_plan_rank;
-      leap.per_round = idx->leap_plan_per_round;
+      leap = idx->leap_plan;
     }
   }
   if (leap.rounds) {
@@ -954,7 +926,7 @@ int page_enqueue(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64_
     plan->slabs = plan_slabs_equal(idx->n, boot, rho - 1.0 + 1e-6);
     page_growth = leap.per_round / page_k;
     plan->leap_rank = leap.rank;
-    idx->leap_active = true;
+    idx->search.leap_active = true;
     idx->stats.leap_rank = leap.rank;
     if (log_enabled() && idx->leap_logged != leap.rounds * 1000 + leap.rank) {
       idx->leap_logged = leap.rounds * 1000 + leap.rank;
@@ -964,43 +936,35 @@ int page_enqueue(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64_
   } else {
     plan->slabs = boot ? plan_slabs_equal(idx->n, boot, page_growth) : plan_slabs(idx->n, first, page_growth);
   }
-  idx->page_growth = page_growth;
   plan->boot = boot;
   const std::vector<Slab>& slabs = plan->slabs;
   if ((int)slabs.size() + 2 > kMaxRounds) return fail(PROQA_EINVAL, "search: too many rounds (%zu)", slabs.size());
   if (boot)
     if (int rc = run_bootstrap(idx, boot, (unsigned)nq_pad, page_k, st, 0, plan->leap_rank)) return rc;
   const bool prof = idx->profile && !bounded;  // the per-round brackets describe the first page
+  Round rd;
+  rd.bounded = bounded;
+  rd.nominate = q8;
+  rd.nq = nq;
+  rd.growth = page_growth;
+  rd.leap_check = plan->leap_rank ? 1 : 0;
   for (size_t r = 0; r < slabs.size(); ++r) {
     hipEvent_t f0 = prof ? idx->ev_filter[2 * r] : nullptr;
     hipEvent_t f1 = prof ? idx->ev_filter[2 * r + 1] : nullptr;
     // while fewer than page_k rows have been merged the threshold is still -inf: every row is logged
-    const bool dense = slabs[r].r0 < page_k;
+    rd.dense = slabs[r].r0 < page_k;
     // (a leaping round's merge verifies its threshold and leaves the next round's: the same rank, the k-th best after the last)
-    idx->round_leap_check = plan->leap_rank ? 1 : 0;
-    idx->round_next_rank = plan->leap_rank && r + 1 < slabs.size() ? plan->leap_rank : 0;
-    idx->round_bit = (int)r;
-    const int rc_round = run_round(idx, slabs[r], qw, n_qtiles, (unsigned)nq_pad, page_k, false, dense, bounded,
-                                   idx->overflow + r, st, f0, f1);
-    idx->round_leap_check = idx->round_next_rank = 0;
-    if (int rc = rc_round)
-      return rc;
-    if (kDebugCand) {
-      (void)hipStreamSynchronize(st);
-      std::vector<unsigned long long> per_query((size_t)nq);
-      (void)hipMemcpy(per_query.data(), idx->stat_dev, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-      unsigned long long c = 0;
-      for (int64_t i = 0; i < nq; ++i) c += per_query[i];
-      fprintf(stderr, "after round %zu: cumulative candidates %llu\n", r, c);
-    }
+    rd.next_rank = plan->leap_rank && r + 1 < slabs.size() ? plan->leap_rank : 0;
+    rd.round_bit = (int)r;
+    if (int rc = run_round(idx, slabs[r], qw, n_qtiles, (unsigned)nq_pad, page_k, rd, idx->overflow + r, st, f0, f1)) return rc;
+    if (kDebugCand) fprintf(stderr, "after round %zu: cumulative candidates %llu\n", r, debug_stat_sum(idx->stat_dev, nq, st));
   }
   // results are written optimistically before the one host sync of the page; they are rewritten
   // by page_complete only if a round overflowed and had to be re-scanned
   // (the finalize kernel also writes the overflow words and the candidate count into the pinned mirror and the status
   // word: no copy command between the search and what the caller enqueues behind it)
   PROQA_HIP(launch_finalize(idx->run_keys, idx->run_n, nq, page_k, out.idx_offset, out.D, out.I, out.out_stride,
-                            out.out_offset, idx->overflow, status_dev, idx->mirror, idx->stat_dev, st,
-                            idx->q8_active ? idx->stat_nom : nullptr));
+                            out.out_offset, idx->overflow, status_dev, idx->mirror, idx->stat_dev, st, q8 ? idx->stat_nom : nullptr));
   PROQA_HIP(hipEventRecord(idx->ev[1], st));
   return PROQA_OK;
 }
@@ -1029,7 +993,7 @@ int page_complete(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64
   // loose order -- are an HBM-bound small-batch search; all of them, on rows sorted against the queries, one more search on
   // ordinary rounds) instead of an fp16 pass over the flagged slabs for every query.
   bool rescued = false;
-  if (idx->leap_active && !bounded && kRescueMax > 0) {
+  if (idx->search.leap_active && !bounded && kRescueMax > 0) {
     unsigned bits = 0;
     for (size_t r = 0; r < slabs.size(); ++r) bits |= idx->mirror->overflow[r];
     if (bits == 8u) {
@@ -1040,21 +1004,22 @@ int page_complete(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64
       for (int64_t q = 0; q < nq && ids.size() <= (size_t)kRescueMax; ++q)
         if (flags[(size_t)q]) ids.push_back((int)q);
       if (!ids.empty() && ids.size() <= (size_t)kRescueMax) {
-        idx->overflow_bits |= 8u;
-        idx->rescue.ids.swap(ids);
-        idx->rescue.D = out.D + out.out_offset;
-        idx->rescue.I = out.I + out.out_offset;
-        idx->rescue.k = page_k;
-        idx->rescue.out_stride = out.out_stride;
-        idx->rescue.idx_offset = out.idx_offset;
-        idx->rescue.st = st;
+        idx->search.overflow_bits |= 8u;
+        proqa_index::Search::Rescue& rq = idx->search.rescue;
+        rq.ids.swap(ids);
+        rq.D = out.D + out.out_offset;
+        rq.I = out.I + out.out_offset;
+        rq.k = page_k;
+        rq.out_stride = out.out_stride;
+        rq.idx_offset = out.idx_offset;
+        rq.st = st;
         rescued = true;
       }
     }
   }
   for (size_t r = 0; r < slabs.size() && !rescued; ++r) {
     if (!idx->mirror->overflow[r]) continue;
-    idx->overflow_bits |= idx->mirror->overflow[r];
+    idx->search.overflow_bits |= idx->mirror->overflow[r];
     std::vector<Slab> todo;
     auto push_quarters = [&](const Slab& sl) {   // pushed in reverse: the stack pops them in row order
       const long long q = round_up<long long>(ceil_div<long long>(sl.r1 - sl.r0, 4), kStageRows);
@@ -1064,13 +1029,16 @@ int page_complete(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64
       }
     };
     push_quarters(slabs[r]);
+    Round rescan;
+    rescan.inclusive = true;
+    rescan.bounded = bounded;
     while (!todo.empty()) {
       const Slab sub = todo.back();
       todo.pop_back();
       const bool leaf = sub.r1 - sub.r0 <= leaf_rows;
       if (!leaf) PROQA_HIP(hipMemsetAsync(word, 0, sizeof(unsigned), st));
-      if (int rc = run_round(idx, sub, qw, n_qtiles, (unsigned)nq_pad, page_k, true, leaf, bounded, word, st, nullptr, nullptr))
-        return rc;
+      rescan.dense = leaf;
+      if (int rc = run_round(idx, sub, qw, n_qtiles, (unsigned)nq_pad, page_k, rescan, word, st)) return rc;
       ++*fallback_out;
       if (leaf) continue;
       PROQA_HIP(hipMemcpyAsync(&idx->mirror->overflow[kMaxRounds - 1], word, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -1081,7 +1049,7 @@ int page_complete(proqa_index* idx, int qw, unsigned n_qtiles, int64_t nq, int64
   if (*fallback_out != fallback_before) {
     PROQA_HIP(launch_finalize(idx->run_keys, idx->run_n, nq, page_k, out.idx_offset, out.D, out.I, out.out_stride,
                               out.out_offset, idx->overflow, nullptr, idx->mirror, idx->stat_dev, st,
-                              idx->q8_active ? idx->stat_nom : nullptr));
+                              idx->search.q8_active ? idx->stat_nom : nullptr));
     PROQA_HIP(hipEventRecord(idx->ev[1], st));
     PROQA_HIP(hipStreamSynchronize(st));
   }
@@ -1137,9 +1105,9 @@ struct OnePassPlan {
   double expected = 0.0;       // rows expected to beat the sampled threshold, per query
 };
 
-const bool kOnePass = !(getenv("PROQA_ONE_PASS") && atoi(getenv("PROQA_ONE_PASS")) == 0);   // developer A/B switch
-const bool kOnePassCompact = !(getenv("PROQA_ONE_PASS_COMPACT") && atoi(getenv("PROQA_ONE_PASS_COMPACT")) == 0);   // the same, for its compact lists
-const bool kOnePassTwoStep = !(getenv("PROQA_ONE_PASS_TWO_STEP") && atoi(getenv("PROQA_ONE_PASS_TWO_STEP")) == 0);   // the same, for its sample
+const bool kOnePass = env_int("PROQA_ONE_PASS", 1) != 0;   // developer A/B switch
+const bool kOnePassCompact = env_int("PROQA_ONE_PASS_COMPACT", 1) != 0;   // the same, for its compact lists
+const bool kOnePassTwoStep = env_int("PROQA_ONE_PASS_TWO_STEP", 1) != 0;   // the same, for its sample
 constexpr size_t kOnePassMaxStoreBytes = 24ull << 30;   // a batch whose store would be larger is searched in groups
 
 OnePassPlan plan_one_pass(const proqa_index* idx, int64_t nq_pad, int k, bool latency_bound) {
@@ -1180,8 +1148,8 @@ OnePassPlan plan_one_pass(const proqa_index* idx, int64_t nq_pad, int k, bool la
   }
   // queries one launch can take within the store budget (whole query tiles)
   const size_t per_query = (size_t)(p.want_chunks + 8) * 2 * p.lane_cap * sizeof(WaveRecord);
-  size_t budget = kOnePassMaxStoreBytes;
-  if (const char* v = getenv("PROQA_ONE_PASS_STORE_MB")) budget = (size_t)atoll(v) << 20;   // tests: force the grouping
+  const int budget_mb = env_int("PROQA_ONE_PASS_STORE_MB", -1);   // tests: force the grouping
+  const size_t budget = budget_mb >= 0 ? (size_t)budget_mb << 20 : kOnePassMaxStoreBytes;
   p.max_queries = (long long)(budget / per_query) / 512 * 512;
   if (p.max_queries < 512 && nq_pad > p.max_queries) return p;
   p.expected = expected;
@@ -1191,14 +1159,11 @@ OnePassPlan plan_one_pass(const proqa_index* idx, int64_t nq_pad, int k, bool la
 
 // steps (2) and (3) of search_one_pass: the thresholds stand, the sample's lists are forgotten; one launch over the shard,
 // one merge, the result written optimistically before the one host sync
-int one_pass_big_launch(proqa_index* idx, const OnePassPlan& pl, const RoundShape& shape, int qw, unsigned n_qtiles, int64_t nq,
-                        int64_t nq_pad, int k, const PageOut& out, hipStream_t st, int sample_rounds, bool* done) {
-  (void)pl;
+int one_pass_big_launch(proqa_index* idx, const RoundShape& shape, int qw, unsigned n_qtiles, int64_t nq, int64_t nq_pad, int k,
+                        const PageOut& out, hipStream_t st, int sample_rounds, bool* done) {
   PROQA_HIP(hipMemsetAsync(idx->run_n, 0, (size_t)idx->ws_nq_pad * sizeof(unsigned), st));
   unsigned* word = idx->overflow + 1;   // [1]: the pass overflowed, [2]: a query came back short
-  if (int rc = run_round(idx, Slab{0, idx->n}, qw, n_qtiles, (unsigned)nq_pad, k, false, false, false, word, st, nullptr, nullptr,
-                         shape))
-    return rc;
+  if (int rc = run_round(idx, Slab{0, idx->n}, qw, n_qtiles, (unsigned)nq_pad, k, Round(), word, st, nullptr, nullptr, shape)) return rc;
   PROQA_HIP(launch_flag_short_lists(idx->run_n, nq, (unsigned)k, word + 1, st));
   PROQA_HIP(launch_finalize(idx->run_keys, idx->run_n, nq, k, out.idx_offset, out.D, out.I, out.out_stride, 0, idx->overflow, nullptr,
                             idx->mirror, idx->stat_dev, st));
@@ -1209,6 +1174,13 @@ int one_pass_big_launch(proqa_index* idx, const OnePassPlan& pl, const RoundShap
   return PROQA_OK;
 }
 
+// the compact lists rescore_nominated_lists writes: `records` WaveRecords' worth of keys, `counts` list lengths
+int ensure_emit_lists(proqa_index* idx, size_t records, size_t counts, hipStream_t st) {
+  PROQA_HIP(idx->emit_log.grow(records * sizeof(WaveRecord), &st));
+  PROQA_HIP(idx->emit_cnt.grow(counts * sizeof(unsigned), &st));
+  return PROQA_OK;
+}
+
 // The big launch of a one-pass search for a FEW queries (one question with k = 5000, online_sampler.py:113) on the
 // int8 copy: such a launch is an HBM stream, and the int8 rows are half the bytes (18M rows: 0.68 -> ~0.37 ms).  The scan
 // logs {row0, nominee bits} records exactly as a nominating round does; rescore_nominated_lists re-scores the nominated rows
@@ -1216,12 +1188,12 @@ int one_pass_big_launch(proqa_index* idx, const OnePassPlan& pl, const RoundShap
 // which is why the batched large-k search stays on the fp16 scan) and writes the keys that beat the sampled threshold as
 // compact lists; the compact merge and everything behind it are the fp16 launch's.  *handled = false: not taken (no usable
 // copy, a shape the lists do not fit) -- the caller runs the fp16 launch.
-const bool kOnePassI8 = !(getenv("PROQA_ONE_PASS_I8") && atoi(getenv("PROQA_ONE_PASS_I8")) == 0);   // developer A/B switch
+const bool kOnePassI8 = env_int("PROQA_ONE_PASS_I8", 1) != 0;   // developer A/B switch
 // When it pays: the launch saves 128 B per row of the shard and costs a 256-byte gather (plus a share of an MFMA and of a merge)
 // per nominated row, ~3 x expected per query -- measured break-even near rows = 12 x queries x expected (18M rows, k = 5000:
 // -32 % for one question, -26 % for 64, -19 % for 128, -7 % for 256; 2.25M rows: -15 % for one, 0 for 32); taken from 16 x.
 // (developer override PROQA_ONE_PASS_I8_MAX_QUERIES: up to that many queries whatever the shard)
-const int kOnePassI8MaxQueries = getenv("PROQA_ONE_PASS_I8_MAX_QUERIES") ? atoi(getenv("PROQA_ONE_PASS_I8_MAX_QUERIES")) : 0;
+const int kOnePassI8MaxQueries = env_int("PROQA_ONE_PASS_I8_MAX_QUERIES", 0);
 int one_pass_big_launch_i8(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_qtiles, int64_t nq, int64_t nq_pad, int k,
                            const PageOut& out, hipStream_t st, int sample_rounds, bool* done, bool* handled) {
   *handled = false;
@@ -1231,7 +1203,7 @@ int one_pass_big_launch_i8(proqa_index* idx, const OnePassPlan& pl, int qw, unsi
     if (idx->nominate_mode == 1 && idx->q8_short_lived_builds >= 2) return PROQA_OK;   // rows that keep changing: see setup_nominate
     if (int rc = ensure_q8(idx, st)) return rc;
   }
-  if (!idx->q8_usable || (idx->q8_unprofitable && idx->nominate_mode != 2)) return PROQA_OK;
+  if (!idx->q8_usable || (idx->q8_auto.unprofitable && idx->nominate_mode != 2)) return PROQA_OK;
   // lists: ~8 records (of kNominateLaneCap = 32) per lane list of the scan at 3 nominated rows per passing row; ~24 keys (of
   // kCompactKeys = 64) per compact list
   const unsigned want = round_up<unsigned>((unsigned)std::ceil(3.0 * pl.expected / 16.0), 8);
@@ -1244,50 +1216,20 @@ int one_pass_big_launch_i8(proqa_index* idx, const OnePassPlan& pl, int qw, unsi
   const unsigned out_chunks = groups / 2, out_stride = round_up<unsigned>(out_chunks, 8);
   if (int rc = ensure_store(idx, round_up<unsigned>(g.chunks, 8), n_qtiles, nq_pad, kNominateLaneCap))
     return rc == PROQA_ENOMEM ? PROQA_OK : rc;
-  {
-    const size_t records = (size_t)out_chunks * nq_pad * 2 * kCompactLaneCap, counts = (size_t)nq_pad * out_stride * 2;
-    if (records > idx->emit_records || counts > idx->emit_counts) {
-      PROQA_HIP(hipStreamSynchronize(st));
-      if (idx->emit_log) (void)hipFree(idx->emit_log);
-      if (idx->emit_cnt) (void)hipFree(idx->emit_cnt);
-      idx->emit_log = nullptr;
-      idx->emit_cnt = nullptr;
-      idx->emit_records = idx->emit_counts = 0;
-      PROQA_HIP(hipMalloc((void**)&idx->emit_log, records * sizeof(WaveRecord)));
-      PROQA_HIP(hipMalloc((void**)&idx->emit_cnt, counts * sizeof(unsigned)));
-      idx->emit_records = records;
-      idx->emit_counts = counts;
-    }
-  }
+  if (int rc = ensure_emit_lists(idx, (size_t)out_chunks * nq_pad * 2 * kCompactLaneCap, (size_t)nq_pad * out_stride * 2, st)) return rc;
   *handled = true;
   // (the merge reads the list lengths of every padded query; the re-scoring writes those of the real ones)
-  PROQA_HIP(hipMemsetAsync(idx->emit_cnt, 0, (size_t)nq_pad * out_stride * 2 * sizeof(unsigned), st));
+  PROQA_HIP(hipMemsetAsync(idx->emit_cnt.ptr, 0, (size_t)nq_pad * out_stride * 2 * sizeof(unsigned), st));
   PROQA_HIP(launch_prep_queries_i8(idx->xq_pad, idx->ws_nq_pad, idx->col, idx->qstats, idx->xq8, idx->qparams, idx->stat_nom, st));
   PROQA_HIP(hipMemsetAsync(idx->run_n, 0, (size_t)idx->ws_nq_pad * sizeof(unsigned), st));
   unsigned* word = idx->overflow + 1;   // [1]: the pass overflowed, [2]: a query came back short
-  FilterArgsI8 fa;
-  fa.xq8 = idx->xq8;
-  fa.xb8 = idx->xb8;
-  fa.slab_row0 = 0;
-  fa.slab_row1 = idx->n;
-  fa.rows_per_chunk = g.rows_per_chunk;
-  fa.tau = idx->tau;
-  fa.qp = idx->qparams;
-  fa.blk = idx->blk8;
-  fa.store = store_of(idx, (unsigned)nq_pad, n_qtiles, kNominateLaneCap, round_up<unsigned>(g.chunks, 8));
-  fa.overflow = word;
-  // (row-split launch as in run_round: the 1 / 2 / 4 query blocks that hold queries, the eight waves share the units of the stream)
-  fa.q_blocks = nq <= 128 ? (nq <= 32 ? 1u : (nq <= 64 ? 2u : 4u)) : 0u;
+  const FilterArgsI8 fa = filter_args_i8(idx, Slab{0, idx->n}, g, n_qtiles, (unsigned)nq_pad, nq, word);
   PROQA_HIP(launch_filter_i8(fa, qw, g.grid, st));
-  CandidateStore emitted;
-  emitted.lane_log = idx->emit_log;
-  emitted.lane_cnt = idx->emit_cnt;
-  emitted.spill_log = idx->spill_log;   // (the merge reads a spill counter per chunk up front whatever the lists hold; compact
-  emitted.spill_cnt = idx->spill_cnt;   //  lists have no spill log and the value is not used: any valid counters do)
-  emitted.nq_pad = (unsigned)nq_pad;
-  emitted.n_qtiles = n_qtiles;
-  emitted.lane_cap = (unsigned)kCompactLaneCap;
-  emitted.n_chunks = out_stride;
+  // (the merge reads a spill counter per chunk up front whatever the lists hold; compact lists have no spill log and the
+  // value is not used: any valid counters do -- the emitted lists keep the store's)
+  CandidateStore emitted = store_of(idx, (unsigned)nq_pad, n_qtiles, (unsigned)kCompactLaneCap, out_stride);
+  emitted.lane_log = (WaveRecord*)idx->emit_log.ptr;
+  emitted.lane_cnt = (unsigned*)idx->emit_cnt.ptr;
   RescoreArgs ra;
   ra.in = fa.store;
   ra.in_lists = in_lists;
@@ -1299,17 +1241,9 @@ int one_pass_big_launch_i8(proqa_index* idx, const OnePassPlan& pl, int qw, unsi
   ra.overflow = word;
   ra.stat_nominated = idx->stat_nom;
   PROQA_HIP(launch_rescore_nominated_lists(ra, groups, (unsigned)nq, st));
-  MergeArgs ma = {};
-  ma.store = emitted;
-  ma.n_chunks = out_chunks;
-  ma.qw = (unsigned)qw;
-  ma.run_keys = idx->run_keys;
-  ma.run_n = idx->run_n;
-  ma.tau = idx->tau;
-  ma.k = k;
-  ma.sort_cap = pl.sort_cap;
-  ma.stat_candidates = idx->stat_dev;
-  ma.overflow = word;
+  // (the plan's own merge capacity, not sort_capacity(k); no nom_keys -- the keys are re-scored already -- and no
+  // short_rounds: nothing leaps here)
+  MergeArgs ma = merge_args(idx, emitted, out_chunks, qw, k, pl.sort_cap, word);
   ma.compact = 1;
   PROQA_HIP(launch_merge(ma, (unsigned)nq_pad, st));
   PROQA_HIP(launch_flag_short_lists(idx->run_n, nq, (unsigned)k, word + 1, st));
@@ -1345,7 +1279,7 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
       if (int rc8 = one_pass_big_launch_i8(idx, pl, qw, n_qtiles, nq, nq_pad, k, out, st, sample_rounds, done, &handled)) return rc8;
       if (handled) return PROQA_OK;
     }
-    int rc = one_pass_big_launch(idx, pl, shape, qw, n_qtiles, nq, nq_pad, k, out, st, sample_rounds, done);
+    int rc = one_pass_big_launch(idx, shape, qw, n_qtiles, nq, nq_pad, k, out, st, sample_rounds, done);
     if (rc || *done || !shape.compact || !idx->mirror->overflow[1]) return rc;
     RoundShape wide = shape;
     wide.want_chunks = round_up<unsigned>((unsigned)std::min<long long>(4ll * shape.want_chunks, idx->n / kStageRows), 8);
@@ -1353,7 +1287,7 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
     const LaunchGeom g = geometry(idx->n, n_qtiles, false, k, wide.want_chunks);
     if (ensure_store(idx, round_up<unsigned>(g.chunks, 8), n_qtiles, nq_pad, wide.lane_cap) != PROQA_OK) return PROQA_OK;   // no room: pages
     PROQA_HIP(hipMemsetAsync(idx->overflow + 1, 0, 2 * sizeof(unsigned), st));
-    return one_pass_big_launch(idx, pl, wide, qw, n_qtiles, nq, nq_pad, k, out, st, sample_rounds, done);
+    return one_pass_big_launch(idx, wide, qw, n_qtiles, nq, nq_pad, k, out, st, sample_rounds, done);
   };
   // (1) thresholds from the sample (the round words were zeroed by prep_queries).  Overflow in here is harmless: it loosens the estimate.
   const int r = pl.r;
@@ -1371,17 +1305,13 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
     // m rows is among the best r' of all m + 8192: with lambda = (r - r') 8192 / m head rows expected above that score,
     // a Poisson upper tail P(X >= r').  The smallest r' that puts it below 1e-12 per query.
     auto poisson_tail = [](double lambda, int at_least) {
-      double term = std::exp(-lambda), below = 0.0;   // P(X = 0)
-      for (int i = 0; i < at_least; ++i) {
-        below += term;
-        term *= lambda / (double)(i + 1);
-      }
-      double tail = 0.0;                                // sum the tail itself: 1 - below loses it to rounding
+      double term = std::exp(-lambda);   // P(X = 0)
+      for (int i = 0; i < at_least; ++i) term *= lambda / (double)(i + 1);
+      double tail = 0.0;                 // sum the tail itself: 1 - (the sum below it) loses it to rounding
       for (int i = at_least; i < at_least + 200; ++i) {
         tail += term;
         term *= lambda / (double)(i + 1);
       }
-      (void)below;
       return tail;
     };
     int r1 = 0;
@@ -1402,18 +1332,12 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
       sample_shape.want_chunks = round_up<unsigned>((unsigned)std::ceil(c / 8.0), 8);   // ~4 records per lane list
       sample_shape.lane_cap = (unsigned)kOnePassLaneCap;
       sample_shape.sort_cap = c * (1.0 + 5.0 / std::sqrt((double)r1)) + r1 <= (double)kMidSortKeys ? kMidSortKeys : kBigSortKeys;
-      if (int rc = run_round(idx, Slab{r0, r0 + m}, qw, n_qtiles, (unsigned)nq_pad, r, false, false, false, idx->overflow, st,
-                             nullptr, nullptr, sample_shape))
+      if (int rc = run_round(idx, Slab{r0, r0 + m}, qw, n_qtiles, (unsigned)nq_pad, r, Round(), idx->overflow, st, nullptr, nullptr,
+                             sample_shape))
         return rc;
-      if (kDebugCand) {
-        (void)hipStreamSynchronize(st);
-        std::vector<unsigned long long> per_query((size_t)nq);
-        (void)hipMemcpy(per_query.data(), idx->stat_dev, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-        unsigned long long tot = 0;
-        for (int64_t q = 0; q < nq; ++q) tot += per_query[q];
+      if (kDebugCand)
         fprintf(stderr, "two-step sample: bootstrap rank %d of %lld rows, then rows [%lld, %lld) for rank %d: %.0f candidates per query "
-                "(expected %.0f)\n", r1, boot_rows, r0, r0 + m, r, (double)tot / (double)nq, c);
-      }
+                "(expected %.0f)\n", r1, boot_rows, r0, r0 + m, r, (double)debug_stat_sum(idx->stat_dev, nq, st) / (double)nq, c);
       return big_launch_with_retry(2);
     }
   }
@@ -1436,13 +1360,9 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
     const long long key[4] = {pl.n_sample, boot, r, qw};
     if (std::memcmp(key, idx->leap_sample_key, sizeof key) != 0) {
       std::memcpy(idx->leap_sample_key, key, sizeof key);
-      const LeapPlan fresh = plan_leap(pl.n_sample, boot, r, qw, false, 256);
-      idx->leap_sample_rounds = fresh.rounds;
-      idx->leap_sample_rank = fresh.rank;
+      idx->leap_sample_plan = plan_leap(pl.n_sample, boot, r, qw, false, 256);
     }
-    LeapPlan lp;
-    lp.rounds = idx->leap_sample_rounds;
-    lp.rank = idx->leap_sample_rank;
+    const LeapPlan& lp = idx->leap_sample_plan;
     if (lp.rounds && lp.rounds < (int)slabs.size()) {
       const double rho = std::pow((double)pl.n_sample / (double)boot, 1.0 / lp.rounds);
       slabs = plan_slabs_equal(pl.n_sample, boot, rho - 1.0 + 1e-6);
@@ -1470,20 +1390,14 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
   }
   long long seen = boot;
   for (size_t i = 0; i < slabs.size(); ++i) {
+    Round rd;
     // while fewer than r rows have been merged the threshold is still -inf: every row is logged
-    idx->round_next_rank = leap_rank_sample && i + 1 < slabs.size() ? leap_rank_sample : 0;
-    const int rc_round = run_round(idx, slabs[i], qw, n_qtiles, (unsigned)nq_pad, r, false, seen < r, false, idx->overflow, st, nullptr,
-                                   nullptr);
-    idx->round_next_rank = 0;
-    if (int rc = rc_round)
-      return rc;
+    rd.dense = seen < r;
+    rd.next_rank = leap_rank_sample && i + 1 < slabs.size() ? leap_rank_sample : 0;
+    if (int rc = run_round(idx, slabs[i], qw, n_qtiles, (unsigned)nq_pad, r, rd, idx->overflow, st)) return rc;
     seen += slabs[i].r1 - slabs[i].r0;
     if (kDebugCand) {
-      (void)hipStreamSynchronize(st);
-      std::vector<unsigned long long> per_query((size_t)nq);
-      (void)hipMemcpy(per_query.data(), idx->stat_dev, (size_t)nq * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-      unsigned long long c = 0;
-      for (int64_t q = 0; q < nq; ++q) c += per_query[q];
+      const unsigned long long c = debug_stat_sum(idx->stat_dev, nq, st);
       unsigned ov = 0;
       (void)hipMemcpy(&ov, idx->overflow, sizeof ov, hipMemcpyDeviceToHost);
       fprintf(stderr, "sample round %zu: rows [%lld, %lld), rank %d, cumulative candidates %llu (%.0f per query), overflow word %u\n", i,
@@ -1499,24 +1413,26 @@ int search_one_pass(proqa_index* idx, const OnePassPlan& pl, int qw, unsigned n_
 constexpr int kProbeAfterFirst = 8, kProbeAfterMost = 64;
 int nomination_state_of(const proqa_index* idx) {   // proqa_search_stats::nomination_state
   if (idx->nominate_mode == 0 || idx->exact) return 0;
-  if (idx->q8_epoch == idx->rows_epoch && (!idx->q8_usable || (idx->q8_unprofitable && idx->nominate_mode != 2))) return 2;
+  if (idx->q8_epoch == idx->rows_epoch && (!idx->q8_usable || (idx->q8_auto.unprofitable && idx->nominate_mode != 2))) return 2;
   return 1;
 }
 void note_nomination(proqa_index* idx, int64_t nq) {
   idx->stats.nomination_state = nomination_state_of(idx);
-  if (!idx->q8_active) return;
-  idx->q8_active = false;
+  if (!idx->search.q8_active) return;
+  idx->search.q8_active = false;
+  proqa_index::Q8Auto& q8 = idx->q8_auto;
+  const unsigned overflow_bits = idx->search.overflow_bits;
   idx->stats.nomination = 1;
   idx->stats.nominated = (int64_t)idx->mirror->nominated;
   const double per_query = (double)idx->stats.nominated / (double)std::max<int64_t>(nq, 1);
   const double limit = std::max(4096.0, (double)idx->n / 2048.0);
   // (overflow bit 3 alone: a leaping round fell short -- note_leap's business, not a property of the int8 copy)
-  const bool bad = per_query > limit || (idx->stats.fallback_rounds > 0 && (idx->overflow_bits & ~8u) != 0);
-  if (bad && per_query <= limit && idx->used_small_merge && idx->small_merge_ok && (idx->overflow_bits & ~8u) == 2u) {
+  const bool bad = per_query > limit || (idx->stats.fallback_rounds > 0 && (overflow_bits & ~8u) != 0);
+  if (bad && per_query <= limit && idx->search.used_small_merge && q8.small_merge_ok && (overflow_bits & ~8u) == 2u) {
     // what overflowed was the capacity of the 1024-key merge alone (no lane list of the scan: bit 0), and the nominations
     // are within the limit: these rows nominate more per round than that merge is sized for -- the 2048-key merge from now
     // on, no suspension (if that overflows too, the next search suspends the rounds)
-    idx->small_merge_ok = false;
+    q8.small_merge_ok = false;
     log_line("index %p: a round's nominations overflowed the 1024-key merge (%.0f rows re-scored per query, %d overflow-safe rounds): "
              "2048-key merges from now on", (void*)idx, per_query, idx->stats.fallback_rounds);
     idx->stats.nomination_state = nomination_state_of(idx);
@@ -1525,18 +1441,18 @@ void note_nomination(proqa_index* idx, int64_t nq) {
   if (bad) {
     // One such batch may be an outlier (an adversarial or degenerate set of queries) on rows that quantise well: the
     // suspension is lifted by a later search that passes.  First probe after 8 eligible searches, then 16, 32, 64, 64, ...
-    idx->q8_probe_after = idx->q8_unprofitable ? std::min(2 * std::max(idx->q8_probe_after, kProbeAfterFirst), kProbeAfterMost)
+    q8.probe_after = q8.unprofitable ? std::min(2 * std::max(q8.probe_after, kProbeAfterFirst), kProbeAfterMost)
                                                : kProbeAfterFirst;
-    idx->q8_suspended_searches = 0;
+    q8.suspended_searches = 0;
     log_line("index %p: int8 nomination scan %s (%.0f rows re-scored per query against a limit of %.0f, %d overflow-safe rounds): "
-             "fp16 scan for the next %d eligible searches", (void*)idx, idx->q8_unprofitable ? "stays suspended" : "suspended", per_query,
-             limit, idx->stats.fallback_rounds, idx->q8_probe_after - 1);
-    idx->q8_unprofitable = true;
-  } else if (idx->q8_unprofitable && idx->nominate_mode != 2) {
+             "fp16 scan for the next %d eligible searches", (void*)idx, q8.unprofitable ? "stays suspended" : "suspended", per_query,
+             limit, idx->stats.fallback_rounds, q8.probe_after - 1);
+    q8.unprofitable = true;
+  } else if (q8.unprofitable && idx->nominate_mode != 2) {
     log_line("index %p: int8 nomination scan resumed (%.0f rows re-scored per query)", (void*)idx, per_query);
-    idx->q8_unprofitable = false;
-    idx->q8_suspended_searches = 0;
-    idx->q8_probe_after = 0;
+    q8.unprofitable = false;
+    q8.suspended_searches = 0;
+    q8.probe_after = 0;
   }
   idx->stats.nomination_state = nomination_state_of(idx);
 }
@@ -1544,65 +1460,60 @@ void note_nomination(proqa_index* idx, int64_t nq) {
 // after the host sync of a search that leapt: a round that fell short pauses the leaps of this index
 int leap_state_of(const proqa_index* idx) {   // proqa_search_stats::leap_state
   if (!idx->leap_mode || idx->exact) return 0;
-  return idx->leap_skip > 0 && idx->leap_epoch == idx->rows_epoch ? 2 : 1;
+  return idx->leap.skip > 0 && idx->leap.epoch == idx->rows_epoch ? 2 : 1;
 }
 void note_leap(proqa_index* idx) {
   idx->stats.leap_state = leap_state_of(idx);
-  if (!idx->leap_active) return;
-  idx->leap_active = false;
-  if (idx->overflow_bits) {
+  if (!idx->search.leap_active) return;
+  idx->search.leap_active = false;
+  proqa_index::LeapPause& lp = idx->leap;
+  const std::vector<int>& short_ids = idx->search.rescue.ids;
+  if (idx->search.overflow_bits) {
     // bit 3: a round fell short; any other: scores that tie in numbers (the rows a leap logs tie with more).  What it cost
-    // decides how soon the leaps pause: up to 256 short queries searched again by themselves (idx->rescue) are ~10 % of a
+    // decides how soon the leaps pause: up to 256 short queries searched again by themselves (idx->search.rescue) are ~10 % of a
     // search -- three strikes each, one taken back by every clean leap, a pause at eight: leaps go on while fewer than a
     // quarter of the searches fall short (they pay up to a half); more short queries (up to a whole second search) or the
     // slab re-scan for every query -- eight strikes, a pause at once
-    const bool cheap = !idx->rescue.ids.empty() && idx->rescue.ids.size() <= (size_t)kRescueCheap;
-    idx->leap_strikes = std::min(idx->leap_strikes + (cheap ? 3 : 8), 16);
-    if (idx->leap_strikes >= 8) {
-      idx->leap_pause = idx->leap_pause ? std::min(2 * idx->leap_pause, 1024) : 16;
-      idx->leap_skip = idx->leap_pause;
-      idx->leap_strikes = 4;
+    const bool cheap = !short_ids.empty() && short_ids.size() <= (size_t)kRescueCheap;
+    lp.strikes = std::min(lp.strikes + (cheap ? 3 : 8), 16);
+    if (lp.strikes >= 8) {
+      lp.pause = lp.pause ? std::min(2 * lp.pause, 1024) : 16;
+      lp.skip = lp.pause;
+      lp.strikes = 4;
       log_line("index %p: a leaping round found fewer than k rows above its threshold or overflowed (%d overflow-safe rounds, overflow "
-               "bits %u): ordinary rounds for the next %d searches", (void*)idx, idx->stats.fallback_rounds, idx->overflow_bits,
-               idx->leap_skip);
+               "bits %u): ordinary rounds for the next %d searches", (void*)idx, idx->stats.fallback_rounds, idx->search.overflow_bits,
+               lp.skip);
     } else {
       log_line("index %p: a leaping round found fewer than k rows above its threshold for %zu quer%s: leaps go on (%d strikes of 8)",
-               (void*)idx, idx->rescue.ids.size(), idx->rescue.ids.size() == 1 ? "y" : "ies", idx->leap_strikes);
+               (void*)idx, short_ids.size(), short_ids.size() == 1 ? "y" : "ies", lp.strikes);
     }
   } else {
-    if (idx->leap_strikes > 0) --idx->leap_strikes;
-    if (idx->leap_pause) {
+    if (lp.strikes > 0) --lp.strikes;
+    if (lp.pause) {
       log_line("index %p: leaping rounds resumed", (void*)idx);
-      idx->leap_pause = 0;
+      lp.pause = 0;
     }
   }
   idx->stats.leap_state = leap_state_of(idx);
 }
 
 int finish_pending(proqa_index* idx, int* rewritten);
-int search_device_impl(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset, float* D_dev,
-                       int64_t* I_dev, hipStream_t st, bool defer, uint32_t* status_dev);
+// (a search calls itself: for the groups of a batch too large for one one-pass launch, and for the queries below)
+int search_device(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset, float* D_dev, int64_t* I_dev,
+                  hipStream_t st, bool defer = false, uint32_t* status_dev = nullptr);
 
-// The queries page_complete listed in idx->rescue (leaping rounds left them short; every other query's result is verified):
+// The queries page_complete listed in idx->search.rescue (leaping rounds left them short; every other query's result is verified):
 // their padded fp16 rows are gathered into a batch of their own, searched on ordinary rounds with this handle's workspace
 // (the search that owned it is complete), and their result rows written over the optimistic ones.  Waits for the stream.
 int rescue_short_queries(proqa_index* idx) {
-  proqa_index::Rescue rq;
-  std::swap(rq, idx->rescue);
+  proqa_index::Search::Rescue rq;
+  std::swap(rq, idx->search.rescue);
   const int s = (int)rq.ids.size(), k = rq.k;
   if (s == 0) return PROQA_OK;
   const size_t off_xq = round_up<size_t>((size_t)s * sizeof(int), 256), off_d = off_xq + (size_t)s * kDim * 2,
                off_i = round_up<size_t>(off_d + (size_t)s * k * sizeof(float), 256), bytes = off_i + (size_t)s * k * sizeof(long long);
-  if (bytes > idx->rescue_bytes) {
-    if (idx->rescue_buf) (void)hipFree(idx->rescue_buf);
-  if (idx->emit_log) (void)hipFree(idx->emit_log);
-  if (idx->emit_cnt) (void)hipFree(idx->emit_cnt);
-    idx->rescue_buf = nullptr;
-    idx->rescue_bytes = 0;
-    PROQA_HIP(hipMalloc(&idx->rescue_buf, bytes));
-    idx->rescue_bytes = bytes;
-  }
-  char* base = (char*)idx->rescue_buf;
+  PROQA_HIP(idx->rescue_buf.grow(bytes));
+  char* base = (char*)idx->rescue_buf.ptr;
   int* ids_dev = (int*)base;
   float* D_tmp = (float*)(base + off_d);
   long long* I_tmp = (long long*)(base + off_i);
@@ -1613,15 +1524,10 @@ int rescue_short_queries(proqa_index* idx) {
   idx->leap_mode = 0;   // (ordinary rounds; the pause this search earned stays as note_leap left it)
   // the second search is part of the caller's ONE search: it does not count towards the automatic mode of the int8 scan
   // (a suspended scan's probe distance, the copy's searches), whose state is put back as the caller's search left it
-  const bool unprofitable = idx->q8_unprofitable, small_ok = idx->small_merge_ok;
-  const int suspended = idx->q8_suspended_searches, probe_after = idx->q8_probe_after, on_copy = idx->q8_searches_on_copy;
-  const int rc = search_device_impl(idx, base + off_xq, s, PROQA_F16, k, rq.idx_offset, D_tmp, (int64_t*)I_tmp, rq.st, false, nullptr);
+  const proqa_index::Q8Auto q8_auto = idx->q8_auto;
+  const int rc = search_device(idx, base + off_xq, s, PROQA_F16, k, rq.idx_offset, D_tmp, (int64_t*)I_tmp, rq.st);
   idx->leap_mode = mode;
-  idx->q8_unprofitable = unprofitable;
-  idx->small_merge_ok = small_ok;
-  idx->q8_suspended_searches = suspended;
-  idx->q8_probe_after = probe_after;
-  idx->q8_searches_on_copy = on_copy;
+  idx->q8_auto = q8_auto;
   if (rc) return rc;
   PROQA_HIP(launch_scatter_result_rows(D_tmp, I_tmp, ids_dev, s, k, rq.D, rq.I, rq.out_stride, rq.st));
   PROQA_HIP(hipStreamSynchronize(rq.st));
@@ -1638,42 +1544,12 @@ int rescue_short_queries(proqa_index* idx) {
   return PROQA_OK;
 }
 
-int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset, float* D_dev,
-                            int64_t* I_dev, hipStream_t st, bool defer, uint32_t* status_dev);
-
-// `defer`: a search of the one-page kind is only ENQUEUED (idx->pending describes it; finish_pending completes it);
+// `defer`: a search of the one-page kind is only ENQUEUED (idx->search.deferred describes it; finish_pending completes it);
 // every other kind runs to completion here.  `status_dev` (optional device word, written on the stream): 1 if the
 // completion will rewrite the result, else 0.
-int search_device(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset,
-                  float* D_dev, int64_t* I_dev, hipStream_t st, bool defer = false, uint32_t* status_dev = nullptr) {
-  const int rc = search_device_impl(idx, xq_dev, nq, dtype, k, idx_offset, D_dev, I_dev, st, defer, status_dev);
-#ifdef PROQA_FILTER_STAMPS
-  {
-    unsigned long long h[8];
-    read_filter_stamps(h);
-    if (h[4])
-      fprintf(stderr, "filter stamps (one wave per workgroup, %llu workgroups over all launches of the search): per unit MFMA section %.1f "
-              "ticks, test section %.1f ticks; units per wave %.0f, wave lifetime per unit %.1f ticks; int8 scan: barrier + DMA issue %.1f "
-              "ticks per unit, %.3f excursions per unit of %.1f ticks each\n", h[4], (double)h[0] / h[2],
-              (double)h[1] / h[2], (double)h[2] / h[4], (double)h[3] / h[2], (double)h[5] / h[2], (double)h[7] / h[2],
-              h[7] ? (double)h[6] / h[7] : 0.0);
-  }
-#endif
-  // a search that ran to completion has a final result: its status word is 0 (the deferred kind writes the word itself)
-  if (rc == PROQA_OK && status_dev && !idx->pending.active) PROQA_HIP(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), st));
-  return rc;
-}
-
-int search_device_impl(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset,
-                       float* D_dev, int64_t* I_dev, hipStream_t st, bool defer, uint32_t* status_dev) {
-  idx->rescue.ids.clear();
-  if (int rc = search_device_impl_body(idx, xq_dev, nq, dtype, k, idx_offset, D_dev, I_dev, st, defer, status_dev)) return rc;
-  return idx->rescue.ids.empty() ? PROQA_OK : rescue_short_queries(idx);
-}
-
-int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset,
-                            float* D_dev, int64_t* I_dev, hipStream_t st, bool defer, uint32_t* status_dev) {
-  if (idx->pending.active)   // a begun search nobody finished (an error path of the caller): complete it, drop its result
+int search_body(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset, float* D_dev, int64_t* I_dev,
+                hipStream_t st, bool defer, uint32_t* status_dev) {
+  if (idx->search.deferred.active)   // a begun search nobody finished (an error path of the caller): complete it, drop its result
     if (int rc = finish_pending(idx, nullptr)) return rc;
   if (nq < 0 || k <= 0) return fail(PROQA_EINVAL, "search: nq=%lld k=%d", (long long)nq, k);
   if (dtype != PROQA_F16 && dtype != PROQA_F32) return fail(PROQA_EINVAL, "search: bad dtype %d", dtype);
@@ -1681,11 +1557,7 @@ int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, in
   idx->stats = {};
   idx->stats.nomination_state = nomination_state_of(idx);
   idx->stats.leap_state = leap_state_of(idx);
-  idx->q8_active = false;
-  idx->pending_nq = nq;
-  idx->used_small_merge = false;
-  idx->overflow_bits = 0;
-  idx->leap_active = false;
+  idx->search = {};
   if (nq == 0) return PROQA_OK;
   PROQA_ON_DEVICE(idx->device);
 
@@ -1747,11 +1619,11 @@ int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, in
     if (idx->q8_epoch != idx->rows_epoch) {
       // rows that keep changing between searches (see q8_short_lived_builds): the first search after a change scans the fp16
       // rows, the copy is rebuilt once a second search finds the same rows (mode "always" rebuilds at once)
-      if (idx->q8_searches_on_copy > 1) idx->q8_short_lived_builds = 0;   // the stale copy earned its build
+      if (idx->q8_auto.searches_on_copy > 1) idx->q8_short_lived_builds = 0;   // the stale copy earned its build
       if (idx->nominate_mode == 1 && idx->q8_short_lived_builds >= 2 && idx->q8_seen_epoch != idx->rows_epoch) {
         idx->q8_seen_epoch = idx->rows_epoch;
         log_line("index %p: rows changed again after an int8 copy that served %d search(es): this search scans the fp16 rows, the "
-                 "copy is rebuilt when the rows stay", (void*)idx, idx->q8_searches_on_copy);
+                 "copy is rebuilt when the rows stay", (void*)idx, idx->q8_auto.searches_on_copy);
         return PROQA_OK;
       }
       idx->q8_seen_epoch = idx->rows_epoch;
@@ -1766,15 +1638,15 @@ int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, in
       if (int rc = ensure_q8(idx, st)) return rc;
     }
     if (!idx->q8_usable) return PROQA_OK;
-    if (idx->q8_unprofitable && idx->nominate_mode != 2) {
-      // suspended (note_nomination): every q8_probe_after-th eligible search tries the int8 rounds again
-      if (++idx->q8_suspended_searches < idx->q8_probe_after) return PROQA_OK;
+    if (idx->q8_auto.unprofitable && idx->nominate_mode != 2) {
+      // suspended (note_nomination): every probe_after-th eligible search tries the int8 rounds again
+      if (++idx->q8_auto.suspended_searches < idx->q8_auto.probe_after) return PROQA_OK;
       log_line("index %p: re-probing the int8 nomination scan after %d searches on the fp16 rows", (void*)idx,
-               idx->q8_suspended_searches);
+               idx->q8_auto.suspended_searches);
     }
     PROQA_HIP(launch_prep_queries_i8(idx->xq_pad, idx->ws_nq_pad, idx->col, idx->qstats, idx->xq8, idx->qparams, idx->stat_nom, st));
-    idx->q8_active = true;
-    ++idx->q8_searches_on_copy;
+    idx->search.q8_active = true;
+    ++idx->q8_auto.searches_on_copy;
     return PROQA_OK;
   };
   // ~670 <= k <= ~11700 on a shard much larger than k: one pass against sampled thresholds (search_one_pass)
@@ -1806,7 +1678,7 @@ int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, in
     if (int rc = page_enqueue(idx, qw, n_qtiles, nq, nq_pad, k, false, PageOut{D_dev, (long long*)I_dev, idx_offset, k, 0}, st, true,
                               &plan, status_dev))
       return rc;
-    proqa_index::Pending& pe = idx->pending;
+    proqa_index::Search::Deferred& pe = idx->search.deferred;
     pe.active = true;
     pe.qw = qw;
     pe.n_qtiles = n_qtiles;
@@ -1862,12 +1734,36 @@ int search_device_impl_body(proqa_index* idx, const void* xq_dev, int64_t nq, in
   return PROQA_OK;
 }
 
+// A whole search (arguments: search_body): its body, then the second search of the queries a leaping round left short, then
+// the status word.
+int search_device(proqa_index* idx, const void* xq_dev, int64_t nq, int dtype, int k, int64_t idx_offset, float* D_dev, int64_t* I_dev,
+                  hipStream_t st, bool defer, uint32_t* status_dev) {
+  int rc = search_body(idx, xq_dev, nq, dtype, k, idx_offset, D_dev, I_dev, st, defer, status_dev);
+  if (rc == PROQA_OK && !idx->search.rescue.ids.empty()) rc = rescue_short_queries(idx);
+#ifdef PROQA_FILTER_STAMPS
+  {
+    unsigned long long h[8];
+    read_filter_stamps(h);
+    if (h[4])
+      fprintf(stderr, "filter stamps (one wave per workgroup, %llu workgroups over all launches of the search): per unit MFMA section %.1f "
+              "ticks, test section %.1f ticks; units per wave %.0f, wave lifetime per unit %.1f ticks; int8 scan: barrier + DMA issue %.1f "
+              "ticks per unit, %.3f excursions per unit of %.1f ticks each\n", h[4], (double)h[0] / h[2],
+              (double)h[1] / h[2], (double)h[2] / h[4], (double)h[3] / h[2], (double)h[5] / h[2], (double)h[7] / h[2],
+              h[7] ? (double)h[6] / h[7] : 0.0);
+  }
+#endif
+  // a search that ran to completion has a final result: its status word is 0 (the deferred kind writes the word itself)
+  if (rc == PROQA_OK && status_dev && !idx->search.deferred.active) PROQA_HIP(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), st));
+  return rc;
+}
+
 // host-side completion of a deferred search: wait for the stream, re-scan what overflowed (rewriting D / I)
 int finish_pending(proqa_index* idx, int* rewritten) {
-  proqa_index::Pending& pe = idx->pending;
   if (rewritten) *rewritten = 0;
-  if (!pe.active) return PROQA_OK;
-  pe.active = false;
+  if (!idx->search.deferred.active) return PROQA_OK;
+  // (taken out of the handle: the search of the short queries below starts a search state of its own)
+  proqa_index::Search::Deferred pe;
+  std::swap(pe, idx->search.deferred);
   PROQA_ON_DEVICE(idx->device);
   PROQA_HIP(hipStreamSynchronize(pe.st));
   PagePlan plan;
@@ -1891,7 +1787,7 @@ int finish_pending(proqa_index* idx, int* rewritten) {
   note_nomination(idx, pe.nq);
   note_leap(idx);
   if (rewritten) *rewritten = fallback != 0;
-  if (!idx->rescue.ids.empty()) {   // (queries a leaping round left short: searched again, their rows rewritten)
+  if (!idx->search.rescue.ids.empty()) {   // (queries a leaping round left short: searched again, their rows rewritten)
     if (int rc = rescue_short_queries(idx)) return rc;
     if (rewritten) *rewritten = 1;
   }
@@ -1951,22 +1847,16 @@ int proqa_index_create(int d, int64_t capacity_rows, proqa_index** out) {
 
 int proqa_index_free(proqa_index* idx) {
   if (!idx) return PROQA_OK;
-  if (idx->pending.active) (void)hipStreamSynchronize(idx->pending.st);   // a begun search nobody finished
+  if (idx->search.deferred.active) (void)hipStreamSynchronize(idx->search.deferred.st);   // a begun search nobody finished
+  // everything the handle owns, in three lists: the workspace arrays, the buffers grown on demand, the fixed-size allocations
   free_workspace(idx);
-  if (idx->xb && idx->owns_xb) (void)hipFree(idx->xb);
-  if (idx->overflow) (void)hipFree(idx->overflow);
-  if (idx->inexact) (void)hipFree(idx->inexact);
-  if (idx->xb32) (void)hipFree(idx->xb32);
-  if (idx->norm_stats) (void)hipFree(idx->norm_stats);
+  for (GrowBuffer* b : {&idx->lane_log, &idx->lane_cnt, &idx->spill_log, &idx->spill_cnt, &idx->stage_dev, &idx->stage_pinned,
+                        &idx->boot_scores, &idx->xb8, &idx->blk8, &idx->emit_log, &idx->emit_cnt, &idx->rescue_buf})
+    (void)b->release();
+  for (void* p : {(void*)(idx->owns_xb ? idx->xb : nullptr), (void*)idx->xb32, (void*)idx->overflow, (void*)idx->inexact,
+                  (void*)idx->norm_stats, (void*)idx->col, (void*)idx->col_partial, (void*)idx->qstats})
+    if (p) (void)hipFree(p);
   if (idx->mirror) (void)hipHostFree(idx->mirror);
-  if (idx->stage_dev) (void)hipFree(idx->stage_dev);
-  if (idx->boot_scores) (void)hipFree(idx->boot_scores);
-  if (idx->xb8) (void)hipFree(idx->xb8);
-  if (idx->blk8) (void)hipFree(idx->blk8);
-  if (idx->col) (void)hipFree(idx->col);
-  if (idx->col_partial) (void)hipFree(idx->col_partial);
-  if (idx->qstats) (void)hipFree(idx->qstats);
-  if (idx->stage_pinned) (void)hipHostFree(idx->stage_pinned);
   if (idx->io_stream) (void)hipStreamDestroy(idx->io_stream);
   for (auto& e : idx->ev)
     if (e) (void)hipEventDestroy(e);
@@ -2025,7 +1915,7 @@ int proqa_index_configure_leap(proqa_index* idx, int mode) {
   if (!idx) return fail(PROQA_EINVAL, "index_configure_leap: NULL handle");
   if (mode < 0 || mode > 1) return fail(PROQA_EINVAL, "index_configure_leap: mode=%d (0 off, 1 automatic)", mode);
   idx->leap_mode = mode;
-  idx->leap_pause = idx->leap_skip = idx->leap_strikes = 0;
+  idx->leap.pause = idx->leap.skip = idx->leap.strikes = 0;
   return PROQA_OK;
 }
 
@@ -2044,7 +1934,7 @@ int proqa_leap_plan(int64_t rows, int64_t bootstrap_rows, int k, int64_t queries
 
 int proqa_index_prepare(proqa_index* idx, void* stream) {
   if (!idx) return fail(PROQA_EINVAL, "index_prepare: NULL handle");
-  if (idx->pending.active) return fail(PROQA_EINVAL, "index_prepare: a search begun on this handle has not been finished");
+  if (idx->search.deferred.active) return fail(PROQA_EINVAL, "index_prepare: a search begun on this handle has not been finished");
   PROQA_ON_DEVICE(idx->device);
   hipStream_t st = as_stream(stream);
   idx->q8_build_due = false;
@@ -2056,7 +1946,7 @@ int proqa_index_prepare(proqa_index* idx, void* stream) {
 
 int proqa_index_rows_changed(proqa_index* idx) {
   if (!idx) return fail(PROQA_EINVAL, "index_rows_changed: NULL handle");
-  if (idx->pending.active) return fail(PROQA_EINVAL, "index_rows_changed: a search begun on this handle has not been finished");
+  if (idx->search.deferred.active) return fail(PROQA_EINVAL, "index_rows_changed: a search begun on this handle has not been finished");
   if (idx->exact) return fail(PROQA_EINVAL, "index_rows_changed: the index keeps float32 copies of its rows (exact-float32 mode); "
                                             "reset it and add the rows again");
   ++idx->rows_epoch;
@@ -2301,17 +2191,11 @@ int proqa_index_search(proqa_index* idx, const void* xq, int64_t nq, int dtype, 
   const size_t i_bytes = (size_t)nq * k * sizeof(int64_t);
   const size_t total = q_bytes + d_bytes + i_bytes;
   if (int rc = ensure_stage(idx, total)) return rc;
-  if (total > idx->stage_pinned_bytes) {
-    if (idx->stage_pinned) PROQA_HIP(hipHostFree(idx->stage_pinned));
-    idx->stage_pinned = nullptr;
-    idx->stage_pinned_bytes = 0;
-    PROQA_HIP(hipHostMalloc(&idx->stage_pinned, total, hipHostMallocDefault));
-    idx->stage_pinned_bytes = total;
-  }
+  PROQA_HIP(idx->stage_pinned.grow(total));
   if (!idx->io_stream) PROQA_HIP(hipStreamCreateWithFlags(&idx->io_stream, hipStreamNonBlocking));
   hipStream_t st = idx->io_stream;
-  char* dev = (char*)idx->stage_dev;
-  char* host = (char*)idx->stage_pinned;
+  char* dev = (char*)idx->stage_dev.ptr;
+  char* host = (char*)idx->stage_pinned.ptr;
   memcpy(host, xq, (size_t)nq * kDim * esz);
   PROQA_HIP(hipMemcpyAsync(dev, host, (size_t)nq * kDim * esz, hipMemcpyHostToDevice, st));
   float* D_dev = (float*)(dev + q_bytes);

@@ -138,6 +138,41 @@ def test_a_few_short_queries_are_searched_again_by_themselves(gpu_device, nq, no
     assert states == [(True, "on"), (True, "paused"), (False, "paused")], states
 
 
+def test_one_handle_alternates_the_one_pass_int8_launch_and_the_second_search_of_short_queries(gpu_device):
+    """The compact lists of the one-pass int8 launch (k = 700 for 5 queries) and the buffer of the second search of short queries
+    are separate allocations of the handle: growing the one must leave the other alone.  One handle runs (a) the large-k
+    search, (b) 40 queries with one short query -- the second search's buffer is allocated --, (c) = (a), (d) 600 queries with
+    three short ones -- that buffer grows --, (e) = (a); every result is that of a fresh handle.
+    The five queries of (a) are queries 1 .. 5, none of them planted: a planted query's running list is final after the bootstrap,
+    so its leaping SAMPLE rounds fall short by construction, the sampled threshold stays too low (search_one_pass: "a round that
+    falls short leaves the sample's r-th best too LOW"), the launch over the shard overflows and the search goes page by page
+    (fallback_rounds = 1, with query 0 among the five) -- the one-pass launch this test is about would not be what answers."""
+    import torch
+    from proqa_amd.index import IndexFlatIP
+    rng = np.random.default_rng(600)
+    n, nq, k, big_k = 300000, 600, 80, 700
+    xb, xq = _planted(rng, n, nq, k, (0, 300, 599))
+    tq = torch.from_numpy(xq).cuda()
+    big = slice(1, 6)
+    Da, Ia, _, _ = _search(xb, xq[big], big_k, "auto", "off")
+    Db, Ib, _, _ = _search(xb, xq[:40], k, "off", "always")
+    Dd, Id, _, _ = _search(xb, xq, k, "off", "always")
+    ix = IndexFlatIP(128)
+    ix.configure_nomination("always")
+    ix.add(xb)
+    for step, (qs, kk, D0, I0) in zip("abcde", [(big, big_k, Da, Ia), (slice(0, 40), k, Db, Ib), (big, big_k, Da, Ia),
+                                                (slice(0, nq), k, Dd, Id), (big, big_k, Da, Ia)]):
+        D, I = ix.search_device(tq[qs], kk)
+        st = ix.last_stats()
+        if kk == big_k:
+            assert st["nomination"] and st["fallback_rounds"] == 0, (step, st)
+        else:
+            assert st["leap_rank"] > 0 and st["fallback_rounds"] > 0, (step, st)
+        np.testing.assert_array_equal(I.cpu().numpy(), I0, err_msg=f"step {step}")
+        np.testing.assert_array_equal(D.cpu().numpy().view(np.uint32), D0.view(np.uint32), err_msg=f"step {step}")
+    ix.close()
+
+
 def test_the_deferred_search_searches_its_short_queries_again(gpu_device):
     import torch
     from proqa_amd.index import PipelinedSearcher

@@ -607,3 +607,49 @@ def test_one_pass_large_k_for_a_few_queries_scans_the_int8_copy(gpu_device, n, n
     assert st0["fallback_rounds"] == 0 and st1["fallback_rounds"] == 0
     np.testing.assert_array_equal(I1, I0)
     np.testing.assert_array_equal(D1.view(np.uint32), D0.view(np.uint32))
+
+
+def test_closing_a_handle_returns_the_lists_of_the_one_pass_int8_launch(gpu_device):
+    """A handle that ran a large-k search for a few queries owns the compact lists the re-scoring writes for the merge
+    (one_pass_big_launch_i8) -- several MB; closing it must return them.  20 x {create, add, search, close}: free device memory
+    may not drop by more than half of 20 x those lists, i.e. the condition fails if even every second handle kept them."""
+    import torch
+    from proqa_amd.index import IndexFlatIP
+    n, nq, k = 200000, 5, 700
+    rng = np.random.default_rng(n + nq + k)
+    xb = rng.standard_normal((n, 128)).astype(np.float16)
+    tq = torch.from_numpy(rng.standard_normal((nq, 128)).astype(np.float16)).cuda()
+
+    def once():
+        ix = IndexFlatIP(128)
+        ix.add(xb)
+        ix.search_device(tq, k)
+        st = ix.last_stats()
+        ix.close()
+        return st
+
+    # the bytes of those lists, by the formulas of one_pass_big_launch_i8 (plan_one_pass: the sample's rank is 256 for this k)
+    ceil_div = lambda a, b: -(-a // b)               # noqa: E731
+    round_up = lambda a, b: ceil_div(a, b) * b       # noqa: E731
+    stage_rows, record_bytes, compact_lane_cap, nq_pad = 128, 80, 7, 256   # kStageRows, sizeof(WaveRecord), kCompactLaneCap, one query tile
+    expected = k / (1.0 - 5.5 / 256 ** 0.5)          # rows expected above the sampled threshold, per query
+    want = round_up(int(np.ceil(3.0 * expected / 16.0)), 8)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows_per_chunk = round_up(ceil_div(n, max(want, cus // 8 * 8)), stage_rows)
+    in_lists = 2 * ceil_div(n, rows_per_chunk)
+    groups = max(2, round_up(int(np.ceil(expected / 24.0)), 2))
+    groups = round_up(ceil_div(in_lists, ceil_div(in_lists, groups)), 2)
+    out_chunks = groups // 2
+    emit_bytes = out_chunks * nq_pad * 2 * compact_lane_cap * record_bytes + nq_pad * round_up(out_chunks, 8) * 2 * 4
+    assert emit_bytes > 4 << 20, emit_bytes           # (a bound of tens of MB below: far above what else may move)
+
+    st = once()                                       # warm-up: torch's allocator, the library's code objects
+    assert st["nomination"] and st["fallback_rounds"] == 0, st   # the int8 launch ran: the lists were allocated
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(20):
+        once()
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    print(f"emit lists {emit_bytes} B per handle; free memory fell by {free0 - free1} B over 20 handles")
+    assert free0 - free1 <= 20 * emit_bytes // 2, (free0, free1, emit_bytes)
