@@ -427,6 +427,62 @@ int proqa_pool_project_f16(const void* h, int batch, int seq_len, int hidden, co
                            void* pooled_ws, void* out, int out_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Backward operators of the tower and of the in-batch objective: what `loss.backward()` of retriever pre-training
+ * (retrieval/train_retriever.py:196-214) runs between the dense products.  Added WITHOUT a bump of PROQA_ABI_VERSION
+ * (purely additive).  Common rules: fp16 device operands in the packed token layout, every sum in fp32; a gradient of an
+ * fp16 activation is written as fp16, a parameter-vector or embedding-table gradient as fp32; every operator is linear in
+ * its incoming gradient and passes inf / NaN through (no data-dependent loop); no allocation, no host synchronisation;
+ * everything on `stream`.  The forward operators save nothing: each backward recomputes what it needs from the forward's
+ * own inputs.  Apart from d_word, every output is bit-identical from run to run.
+ * ws / ws_bytes: caller-owned device scratch of at least proqa_backward_workspace_bytes(cols) bytes (the attention:
+ * proqa_attention_backward_workspace_bytes), 16-byte aligned; contents undefined afterwards; calls that share a
+ * workspace must be ordered on one stream.
+ * ---------------------------------------------------------------------------------- */
+size_t proqa_backward_workspace_bytes(int cols);
+size_t proqa_attention_backward_workspace_bytes(int64_t n_tokens, int n_heads);
+/* out[c] = sum_r x[r, c]: x [rows, cols] fp16 -> out [cols] fp32, rows added in a fixed order (slabs of rows, then the slabs
+ * in ascending order).  The bias gradient of a dense layer whose bias a fused operator did not own (the Q|K|V bias:
+ * column sum of d_qkv).  cols a multiple of 8, <= 8192. */
+int proqa_colsum_f16(const void* x, int64_t rows, int cols, float* out, void* ws, size_t ws_bytes, void* stream);
+/* out = gelu_erf(x + bias), out of place (proqa_bias_gelu_f16 overwrites the operand its backward needs) */
+int proqa_bias_gelu_out_f16(const void* x, const void* bias, int64_t rows, int cols, void* out, void* stream);
+/* dx = dy * gelu'(x_pre + bias), gelu'(t) = Phi(t) + t phi(t) (the derivative of the erf form); dbias [cols] fp32 = column
+ * sum of dx before its rounding.  cols a multiple of 8, <= 8192. */
+int proqa_bias_gelu_backward_f16(const void* dy, const void* x_pre, const void* bias, int64_t rows, int cols, void* dx,
+                                 float* dbias, void* ws, size_t ws_bytes, void* stream);
+/* backward of out = LayerNorm(x + bias + residual) * gamma + beta: dz [rows, cols] fp16 is the gradient of x and of
+ * residual alike; dgamma, dbeta, dbias [cols] fp32 (dbias = column sum of dz before its rounding).  Mean and variance
+ * are recomputed from x + bias + residual in fp32.  cols a multiple of 8, <= 1024. */
+int proqa_bias_residual_layernorm_backward_f16(const void* dy, const void* x, const void* bias, const void* residual,
+                                               const void* gamma, float eps, int64_t rows, int cols, void* dz, float* dgamma,
+                                               float* dbeta, float* dbias, void* ws, size_t ws_bytes, void* stream);
+/* backward of proqa_embed_layernorm_varlen_f16: dy [n_tokens, hidden] packed, ids padded [batch, seq_len] (ids at or past a
+ * sequence's length contribute nothing), seq_len <= 512.  All five outputs are fp32 and ADDED INTO buffers the caller
+ * zeroed: dgamma, dbeta, d_type0 [hidden], d_pos [>= seq_len, hidden] (rows past the longest sequence stay untouched),
+ * d_word [vocab, hidden] (fp32 atomics: the one output whose bits depend on the order of execution). */
+int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids_dev, const int32_t* cu_seqlens_dev,
+                                              int batch, int seq_len, int hidden, int64_t n_tokens, const void* word_emb,
+                                              int64_t vocab, const void* pos_emb, const void* type_emb, const void* ln_gamma,
+                                              float eps, float* dgamma, float* dbeta, float* d_word, float* d_pos,
+                                              float* d_type0, void* ws, size_t ws_bytes, void* stream);
+/* backward of proqa_attention_ex_f16 on the packed layout (cls_only = 0): qkv [n_tokens, 3*hidden] (the GEMM output before
+ * the bias), qkv_bias [3*hidden] or NULL, d_ctx [n_tokens, hidden] -> d_qkv [n_tokens, 3*hidden], every element written.
+ * The probabilities are recomputed with the forward's conventions (query bias added, key bias dropped, scores / 8, fp32
+ * statistics); all five products run on v_mfma_f32_32x32x16_f16.  The gradient of qkv_bias is the column sum of d_qkv
+ * (proqa_colsum_f16); its key third is zero up to rounding.  max_seq_len <= 512, head_dim 64; n_tokens =
+ * cu_seqlens[batch]; a sequence whose offsets fall outside [0, n_tokens] is skipped. */
+int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx, const int32_t* cu_seqlens_dev,
+                                 int batch, int max_seq_len, int n_heads, int64_t n_tokens, void* d_qkv, void* ws,
+                                 size_t ws_bytes, void* stream);
+/* gradient of loss = mean_i (lse_i - s[i, target_i]), s = q c^T (CrossEntropyLoss(q @ c.T, target),
+ * retrieval/train_retriever.py:203-205): q [nq, 128], c [nc, 128], target as proqa_inbatch_eval_f16 (NULL = the diagonal;
+ * several questions may share a target; a target outside [0, nc) has no gold term), lse [nq] fp32 as that call produced
+ * it, grad_in: device pointer to the fp32 scalar incoming gradient.  dq [nq, 128], dc [nc, 128] fp16.  The score matrix
+ * exists one 32 x 32 tile at a time. */
+int proqa_inbatch_loss_grad_f16(const void* q, const void* c, const int32_t* target, const float* lse, const float* grad_in,
+                                int nq, int nc, int dim, void* dq, void* dc, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * k-means over passage embeddings.  Replaces faiss.Clustering.train + index.search(data, 1) of
  * retrieval/group_paras.py:20-53 (IndexFlatL2, IndexFlatIP when --spherical).  The Lloyd loop
  * (sampling, initialisation, empty-cluster splitting: faiss Clustering.cpp) runs on the host

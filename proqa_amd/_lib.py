@@ -145,6 +145,22 @@ SIGNATURES = {
                                                   c_float, c_int64, c_int, c_void_p, c_void_p]),
     "proqa_pool_project_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "proqa_backward_workspace_bytes": (c_size_t, [c_int]),
+    "proqa_attention_backward_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "proqa_colsum_f16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "proqa_bias_gelu_out_f16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "proqa_bias_gelu_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_size_t, c_void_p]),
+    "proqa_bias_residual_layernorm_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64,
+                                                           c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                           c_void_p]),
+    "proqa_embed_layernorm_varlen_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p,
+                                                          c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "proqa_attention_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p,
+                                             c_void_p, c_size_t, c_void_p]),
+    "proqa_inbatch_loss_grad_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                            c_void_p, c_void_p]),
     "proqa_kmeans_create": (c_int, [c_int, c_int64, c_int, ctypes.POINTER(c_void_p)]),
     "proqa_kmeans_free": (c_int, [c_void_p]),
     "proqa_kmeans_assign_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,

@@ -29,6 +29,7 @@ SOURCES = [
     "encoder.cpp",
     "reader_kernels.hip",
     "inbatch_kernels.hip",
+    "train_kernels.hip",
     "kmeans_kernels.hip",
     "ivf_index.cpp",
     "ivf_kernels.hip",

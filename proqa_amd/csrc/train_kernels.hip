@@ -1,0 +1,987 @@
+// Backward operators of the BERT tower and of the in-batch objective (proqa_*_backward_f16, proqa_inbatch_loss_grad_f16,
+// proqa_colsum_f16 in proqa_hip.h): what retriever pre-training (README section 3 of the reference,
+// retrieval/train_retriever.py:196-214) differentiates through.  The forward kernels (encoder_kernels.hip,
+// attention_kernel.hip, inbatch_kernels.hip) save nothing; every operator here recomputes what it needs from the forward's
+// own inputs.  Operands are fp16, every sum is fp32, activation gradients leave as fp16, parameter gradients as fp32.
+//
+// Determinism.  Column sums over rows (bias, gamma, beta gradients) are taken in a fixed order: a workgroup owns a
+// contiguous slab of rows, its partial sums go to the caller's workspace ([slab][k][cols] fp32), and reduce_slabs adds the
+// slabs in ascending order.  The attention backward has no cross-workgroup sum at all: one kernel owns query rows (softmax
+// statistics and dQ), a second owns key rows (dK, dV).  The only atomics are the fp32 adds into the word-embedding gradient.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "common.h"
+
+namespace proqa {
+namespace {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kMaxChunksPerLane = 2;   // row-wise kernels: one wave per row, cols <= 64 * 2 * 8 = 1024 (as the forward)
+constexpr int kMaxSlabs = 512;         // row slabs (workgroups) of a column sum
+constexpr int kMaxColChunks = 4;       // column-owning kernels: 256 threads x 4 x 8 columns = 8192
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+// ---- slabs -> sums ------------------------------------------------------------------------------------------------------
+// out_k[c] (+)= sum over the slabs, in ascending order, of ws[slab][k][c]; one thread per (k, column)
+__global__ __launch_bounds__(256) void reduce_slabs(const float* __restrict__ ws, int n_slabs, int n_k, int cols,
+                                                    float* out0, float* out1, float* out2, float* out3, int accumulate) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_k * cols) return;
+  const int k = t / cols, c = t - k * cols;
+  float* out = k == 0 ? out0 : (k == 1 ? out1 : out2);
+  // compensated (Kahan) sum: the slabs of a long batch are many and of one sign more often than not
+  float s = 0.f, comp = 0.f;
+  for (int b = 0; b < n_slabs; ++b) {
+    const float y = ws[((long long)b * n_k + k) * cols + c] - comp;
+    const float t = s + y;
+    comp = (t - s) - y;
+    s = t;
+  }
+  if (out) out[c] = accumulate ? out[c] + s : s;
+  if (k == 2 && out3) out3[c] = accumulate ? out3[c] + s : s;   // (embedding: the position partials are the type-0 gradient too)
+}
+
+// ---- LayerNorm backward of one register-resident row -------------------------------------------------------------------
+// z = the normalised operand (x + bias + residual, or the embedding sum); dz = rstd (a - mean(a) - xhat mean(a xhat)),
+// a = dy gamma; dgam += dy xhat, dbet += dy.  Lanes hold chunks lane, lane + 64 of the row (8 columns each).
+__device__ __forceinline__ void layernorm_backward_row(const float (&z)[kMaxChunksPerLane][8],
+                                                       const float (&dy)[kMaxChunksPerLane][8],
+                                                       const float (&gam)[kMaxChunksPerLane][8], int lane, int n_chunks,
+                                                       int cols, float eps, float (&dz)[kMaxChunksPerLane][8],
+                                                       float (&dgam)[kMaxChunksPerLane][8],
+                                                       float (&dbet)[kMaxChunksPerLane][8]) {
+  const float inv_n = 1.0f / (float)cols;
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c)
+    if (lane + 64 * c < n_chunks) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s += z[c][i];
+    }
+  const float mean = wave_sum(s) * inv_n;
+  float v = 0.f;
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c)
+    if (lane + 64 * c < n_chunks) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float d = z[c][i] - mean;
+        v += d * d;
+      }
+    }
+  const float rstd = rsqrtf(wave_sum(v) * inv_n + eps);
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c)
+    if (lane + 64 * c < n_chunks) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float xhat = (z[c][i] - mean) * rstd;
+        const float a = dy[c][i] * gam[c][i];
+        s1 += a;
+        s2 += a * xhat;
+      }
+    }
+  s1 = wave_sum(s1) * inv_n;
+  s2 = wave_sum(s2) * inv_n;
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c)
+    if (lane + 64 * c < n_chunks) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float xhat = (z[c][i] - mean) * rstd;
+        const float a = dy[c][i] * gam[c][i];
+        dz[c][i] = rstd * (a - s1 - xhat * s2);
+        dgam[c][i] += dy[c][i] * xhat;
+        dbet[c][i] += dy[c][i];
+      }
+    }
+}
+
+__device__ __forceinline__ void load8(const _Float16* p, float (&dst)[8]) {
+  const f16x8 v = *(const f16x8*)p;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) dst[i] = (float)v[i];
+}
+
+// the three per-wave column partials of a 4-wave workgroup -> ws[slab][0..2][cols], waves added in ascending order
+__device__ __forceinline__ void reduce_waves_to_slab(float (*red)[3][64 * kMaxChunksPerLane * 8],
+                                                     const float (&p0)[kMaxChunksPerLane][8],
+                                                     const float (&p1)[kMaxChunksPerLane][8],
+                                                     const float (&p2)[kMaxChunksPerLane][8], int lane, int wave,
+                                                     int n_chunks, int cols, float* __restrict__ slab,
+                                                     float (&total2)[kMaxChunksPerLane][8]) {
+  if (wave > 0) {
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          red[wave - 1][0][chunk * 8 + i] = p0[c][i];
+          red[wave - 1][1][chunk * 8 + i] = p1[c][i];
+          red[wave - 1][2][chunk * 8 + i] = p2[c][i];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float a = p0[c][i], b = p1[c][i], d = p2[c][i];
+          for (int w = 0; w < 3; ++w) {
+            a += red[w][0][chunk * 8 + i];
+            b += red[w][1][chunk * 8 + i];
+            d += red[w][2][chunk * 8 + i];
+          }
+          slab[chunk * 8 + i] = a;
+          slab[cols + chunk * 8 + i] = b;
+          slab[2 * cols + chunk * 8 + i] = d;
+          total2[c][i] = d;
+        }
+      }
+    }
+  }
+}
+
+// ---- bias + residual + LayerNorm backward ------------------------------------------------------------------------------
+// workgroup = slab of rows_per_slab rows, wave = one row at a time; partials (dgamma, dbeta, dbias) -> ws[slab][3][cols]
+__global__ __launch_bounds__(256) void bias_residual_layernorm_bwd(const _Float16* __restrict__ dy_in,
+                                                                   const _Float16* __restrict__ xin,
+                                                                   const _Float16* __restrict__ bias,
+                                                                   const _Float16* __restrict__ residual,
+                                                                   const _Float16* __restrict__ gamma, float eps,
+                                                                   long long rows, int cols, long long rows_per_slab,
+                                                                   _Float16* __restrict__ dz_out, float* __restrict__ ws) {
+  __shared__ float red[3][3][64 * kMaxChunksPerLane * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_chunks = cols >> 3;
+  float gam[kMaxChunksPerLane][8], bia[kMaxChunksPerLane][8];
+  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dbia[kMaxChunksPerLane][8];
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c) {
+    const int chunk = lane + 64 * c;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gam[c][i] = bia[c][i] = dgam[c][i] = dbet[c][i] = dbia[c][i] = 0.f;
+    if (chunk < n_chunks) {
+      load8(gamma + chunk * 8, gam[c]);
+      load8(bias + chunk * 8, bia[c]);
+    }
+  }
+  const long long row0 = (long long)blockIdx.x * rows_per_slab;
+  const long long row1 = row0 + rows_per_slab < rows ? row0 + rows_per_slab : rows;
+  for (long long row = row0 + wave; row < row1; row += 4) {
+    float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+        float a[8], r[8];
+        load8(xin + row * cols + chunk * 8, a);
+        load8(residual + row * cols + chunk * 8, r);
+        load8(dy_in + row * cols + chunk * 8, dy[c]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) z[c][i] = a[i] + bia[c][i] + r[i];
+      }
+    }
+    layernorm_backward_row(z, dy, gam, lane, n_chunks, cols, eps, dz, dgam, dbet);
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+        f16x8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          o[i] = (_Float16)dz[c][i];
+          dbia[c][i] += dz[c][i];
+        }
+        *(f16x8*)(dz_out + row * cols + chunk * 8) = o;
+      }
+    }
+  }
+  float unused[kMaxChunksPerLane][8];
+  reduce_waves_to_slab(red, dgam, dbet, dbia, lane, wave, n_chunks, cols, ws + (long long)blockIdx.x * 3 * cols, unused);
+}
+
+// ---- embedding + LayerNorm backward --------------------------------------------------------------------------------------
+// workgroup = position s, its waves take the sequences that are longer than s in turns: dx of token (b, s) goes to the word
+// row of its id (fp32 atomics, the one non-deterministic output) and into the position's own sum; d_pos[s] is final when
+// the workgroup ends, and (dgamma, dbeta, d_pos[s]) are slab s of the workspace: the type-0 gradient is the sum of the
+// position gradients.
+__global__ __launch_bounds__(256) void embed_layernorm_bwd(const _Float16* __restrict__ dy_in, const long long* __restrict__ ids,
+                                                           const int* __restrict__ cu_seqlens, int batch, int seq_len,
+                                                           int hidden, const _Float16* __restrict__ word, long long vocab,
+                                                           const _Float16* __restrict__ pos,
+                                                           const _Float16* __restrict__ type0,
+                                                           const _Float16* __restrict__ gamma, float eps, long long n_tokens,
+                                                           float* __restrict__ d_word, float* __restrict__ d_pos,
+                                                           float* __restrict__ ws) {
+  __shared__ float red[3][3][64 * kMaxChunksPerLane * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_chunks = hidden >> 3;
+  const int s = blockIdx.x;
+  float gam[kMaxChunksPerLane][8], base[kMaxChunksPerLane][8];   // base = pos[s] + type[0]
+  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dpos[kMaxChunksPerLane][8];
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c) {
+    const int chunk = lane + 64 * c;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gam[c][i] = base[c][i] = dgam[c][i] = dbet[c][i] = dpos[c][i] = 0.f;
+    if (chunk < n_chunks) {
+      float p[8], t[8];
+      load8(gamma + chunk * 8, gam[c]);
+      load8(pos + (long long)s * hidden + chunk * 8, p);
+      load8(type0 + chunk * 8, t);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) base[c][i] = p[i] + t[i];
+    }
+  }
+  for (int b = wave; b < batch; b += 4) {
+    const int first = cu_seqlens[b];
+    const long long row = (long long)first + s;
+    if (s >= cu_seqlens[b + 1] - first || row >= n_tokens) continue;   // wave-uniform
+    long long id = ids[(long long)b * seq_len + s];
+    if (id < 0 || id >= vocab) id = 0;   // the forward read row 0 for such an id
+    float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+        float w[8];
+        load8(word + id * hidden + chunk * 8, w);
+        load8(dy_in + row * hidden + chunk * 8, dy[c]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) z[c][i] = w[i] + base[c][i];
+      }
+    }
+    layernorm_backward_row(z, dy, gam, lane, n_chunks, hidden, eps, dz, dgam, dbet);
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          dpos[c][i] += dz[c][i];
+          atomicAdd(d_word + id * hidden + chunk * 8 + i, dz[c][i]);
+        }
+      }
+    }
+  }
+  float total[kMaxChunksPerLane][8];
+  reduce_waves_to_slab(red, dgam, dbet, dpos, lane, wave, n_chunks, hidden, ws + (long long)s * 3 * hidden, total);
+  if (wave == 0) {
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d_pos[(long long)s * hidden + chunk * 8 + i] += total[c][i];
+      }
+    }
+  }
+}
+
+// ---- column-owning kernels: column sum, bias + GELU backward --------------------------------------------------------------
+// workgroup = slab of rows, thread = up to kMaxColChunks 8-column pieces of every row of the slab, summed in row order:
+// no reduction inside the workgroup.  MODE 0: sum of x.  MODE 1: dx = dy gelu'(x_pre + bias), sum of dx.
+__device__ __forceinline__ float gelu_erf_grad(float t) {
+  // d/dt [t Phi(t)] = Phi(t) + t phi(t); exp(-t^2/2) underflows to 0 long before t^2 overflows
+  const float cdf = 0.5f * (1.0f + erff(t * 0.70710678118654752440f));
+  const float pdf = 0.39894228040143267794f * expf(-0.5f * t * t);
+  return cdf + t * pdf;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void column_kernel(const _Float16* __restrict__ x, const _Float16* __restrict__ dy_in,
+                                                     const _Float16* __restrict__ bias, long long rows, int cols,
+                                                     long long rows_per_slab, _Float16* __restrict__ dx_out,
+                                                     float* __restrict__ ws) {
+  const int n_chunks = cols >> 3;
+  float acc[kMaxColChunks][8], bia[kMaxColChunks][8];
+#pragma unroll
+  for (int c = 0; c < kMaxColChunks; ++c) {
+    const int chunk = threadIdx.x + 256 * c;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[c][i] = bia[c][i] = 0.f;
+    if (MODE == 1 && chunk < n_chunks) load8(bias + chunk * 8, bia[c]);
+  }
+  const long long row0 = (long long)blockIdx.x * rows_per_slab;
+  const long long row1 = row0 + rows_per_slab < rows ? row0 + rows_per_slab : rows;
+  for (long long row = row0; row < row1; ++row) {
+#pragma unroll
+    for (int c = 0; c < kMaxColChunks; ++c) {
+      const int chunk = threadIdx.x + 256 * c;
+      if (chunk < n_chunks) {
+        float v[8];
+        load8(x + row * cols + chunk * 8, v);
+        if (MODE == 1) {
+          float g[8];
+          load8(dy_in + row * cols + chunk * 8, g);
+          f16x8 o;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            v[i] = g[i] * gelu_erf_grad(v[i] + bia[c][i]);
+            o[i] = (_Float16)v[i];
+          }
+          *(f16x8*)(dx_out + row * cols + chunk * 8) = o;
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[c][i] += v[i];
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < kMaxColChunks; ++c) {
+    const int chunk = threadIdx.x + 256 * c;
+    if (chunk < n_chunks) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) ws[(long long)blockIdx.x * cols + chunk * 8 + i] = acc[c][i];
+    }
+  }
+}
+
+// out = gelu_erf(x + bias), out of place: the training forward keeps x (the backward's operand)
+__global__ __launch_bounds__(256) void bias_gelu_out(const _Float16* __restrict__ x, const _Float16* __restrict__ bias,
+                                                     long long n_chunks_total, int chunks_per_row,
+                                                     _Float16* __restrict__ out) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks_total; c += stride) {
+    const int col_chunk = (int)(c % chunks_per_row);
+    f16x8 v = *(const f16x8*)(x + c * 8);
+    const f16x8 b = *(const f16x8*)(bias + col_chunk * 8);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float t = (float)v[i] + (float)b[i];
+      v[i] = (_Float16)(0.5f * t * (1.0f + erff(t * 0.70710678118654752440f)));   // the forward kernel's expression
+    }
+    *(f16x8*)(out + c * 8) = v;
+  }
+}
+
+// ---- attention backward ---------------------------------------------------------------------------------------------------
+// With S = (Q + b_q) K^T / 8, P = softmax(S), ctx = P V (+ b_v):
+//   dP = d_ctx V^T,  delta_q = sum_k P dP,  dS = P (dP - delta),  dQ = dS K / 8,  dK = dS^T (Q + b_q) / 8,  dV = P^T d_ctx.
+// (b_v shifts dP and delta alike and drops out; the key bias never reached the scores.)
+// Both kernels use v_mfma_f32_32x32x16_f16 in the forward's orientation: the accumulator tile of a product has its column
+// on the lane and 16 rows in registers, and is the B operand of the next product as it stands (the k-order of a step is
+// free as long as both operands agree: A fragments gather rows {0-3, 8-11} + 4*half + 16*step of the transposed LDS copy).
+//   attention_bwd_dq   workgroup = 128 queries of a (sequence, head), wave = 32 queries, lane = one query.  Pass 1 over
+//                      the keys: S^T = K Q^T and dP^T = V dO^T -> running max, sum and sum of p dP (online softmax);
+//                      lse and delta go to the workspace.  Pass 2: the same two products again, dS^T in registers, and
+//                      dQ^T += K^T dS^T.  Five products.
+//   attention_bwd_dkv  workgroup = 128 keys, wave = 32 keys, lane = one key, queries in chunks of 64 through LDS (rows and
+//                      transposed): S = Q K^T, dP = dO V^T, then dV^T += dO^T P and dK^T += Q^T dS.  Four products.
+// Nine products where five are the minimum: the price of owning every output row in exactly one place (no atomics, no
+// second reduction pass over [T, hidden] partials).
+constexpr int kHeadDim = 64;
+constexpr int kRowStride = kHeadDim + 8;   // fp16 elements of a row-major LDS row (144 B: conflict-free b128)
+constexpr int kChunk = 128;                // rows a workgroup owns; keys per LDS stage of attention_bwd_dq
+constexpr int kTPad = 4;                   // transposed copies: rows are n + 4 elements long (as the forward's V^T)
+constexpr int kQChunk = 64;                // queries per LDS stage of attention_bwd_dkv
+constexpr float kExpScale = 0.125f * 1.4426950408889634f;   // log2(e) / sqrt(head_dim)
+
+// Row r (piece c: 8 of its 64 values) -> dst[d][r], d = 8c .. 8c + 7.  Rows r and r ^ 1 sit in lanes 8 apart (thread ->
+// (r, c) = (i >> 3, i & 7), i = tid + 256 * it); the even row's lane writes d = 8c .. 8c+3, the odd row's d = 8c+4 .. 8c+7,
+// each as 4-byte stores {row r & ~1, row r | 1} (the forward kernel's V^T staging).
+__device__ __forceinline__ void stage_transposed(f16x8 vv, int r, int c, _Float16* __restrict__ dst, int stride) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 w = __builtin_bit_cast(u32x4, vv);
+  const bool odd = (r & 1) != 0;
+  const unsigned s0 = odd ? w[0] : w[2], s1 = odd ? w[1] : w[3];
+  const unsigned g0 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s0, 0x128, 0xf, 0xf, false);
+  const unsigned g1 = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s1, 0x128, 0xf, 0xf, false);
+  const unsigned lo[2] = {odd ? g0 : w[0], odd ? g1 : w[1]};   // the d values of the EVEN row (low half of the store)
+  const unsigned hi[2] = {odd ? w[2] : g0, odd ? w[3] : g1};   // ... of the odd row
+  _Float16* p = dst + (c * 8 + (odd ? 4 : 0)) * stride + (r & ~1);
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    *(unsigned*)(p + (2 * t) * stride) = __builtin_amdgcn_perm(hi[t], lo[t], 0x05040100u);
+    *(unsigned*)(p + (2 * t + 1) * stride) = __builtin_amdgcn_perm(hi[t], lo[t], 0x07060302u);
+  }
+}
+
+// the A fragment of a step over rows k0 .. of a transposed copy: row `d`, elements {k0 .. k0+3, k0+8 .. k0+11}
+__device__ __forceinline__ f16x8 transposed_fragment(const _Float16* __restrict__ t_lds, int stride, int d, int k0) {
+  const _Float16* r = t_lds + d * stride + k0;
+  const f16x4 a = *(const f16x4*)r, b = *(const f16x4*)(r + 8);
+  f16x8 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    v[e] = a[e];
+    v[4 + e] = b[e];
+  }
+  return v;
+}
+
+// a wave's [32 rows][64] fp32 tile held transposed in two accumulators (lane = row, registers = columns) -> 16-byte
+// pieces of rows row0 .. row0 + 31 of `out` (row stride out_stride), through the wave's own LDS tile
+__device__ __forceinline__ void store_tile(const f32x16& o0, const f32x16& o1, float scale, _Float16* __restrict__ tile,
+                                           int lane, _Float16* __restrict__ out, long long out_stride, int row0,
+                                           int rows_valid) {
+  const int li = lane & 31, half = lane >> 5;
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    f16x4 a, c;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      a[e] = (_Float16)(o0[g * 4 + e] * scale);
+      c[e] = (_Float16)(o1[g * 4 + e] * scale);
+    }
+    *(f16x4*)(tile + li * kRowStride + g * 8 + 4 * half) = a;
+    *(f16x4*)(tile + li * kRowStride + 32 + g * 8 + 4 * half) = c;
+  }
+  // same wave writes and reads its tile: LDS ops of a wave complete in order
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int row = it * 8 + (lane >> 3), piece = lane & 7;
+    const f16x8 v = *(const f16x8*)(tile + row * kRowStride + piece * 8);
+    if (row0 + row < rows_valid) *(f16x8*)(out + (long long)(row0 + row) * out_stride + piece * 8) = v;
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void attention_bwd_dq(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
+                                                           const _Float16* __restrict__ dctx, const int* __restrict__ cu_seqlens,
+                                                           int max_seq_len, int n_heads, int n_qc, long long n_tokens,
+                                                           _Float16* __restrict__ dqkv, float* __restrict__ ws_lse,
+                                                           float* __restrict__ ws_delta) {
+  constexpr int t_stride = kChunk + kTPad;
+  __shared__ __attribute__((aligned(16))) _Float16 smem[2 * kChunk * kRowStride + kHeadDim * t_stride];
+  _Float16* k_lds = smem;                              // [128][72]
+  _Float16* v_lds = smem + kChunk * kRowStride;        // [128][72]
+  _Float16* kt_lds = smem + 2 * kChunk * kRowStride;   // [64][132]  K transposed
+  const int pair = blockIdx.x / n_qc, qc = blockIdx.x - pair * n_qc;
+  const int b = pair / n_heads, head = pair - b * n_heads;
+  const int hidden = n_heads * kHeadDim;
+  const long long row_stride = 3ll * hidden;
+  const long long tok0 = cu_seqlens[b];
+  int len = cu_seqlens[b + 1] - cu_seqlens[b];
+  len = len < 1 ? 1 : (len > max_seq_len ? max_seq_len : len);
+  if (tok0 < 0 || tok0 + len > n_tokens) return;       // offsets that do not describe the buffers: touch nothing
+  if (qc * kChunk >= len) return;                      // (the whole workgroup: no barrier has been met)
+  const _Float16* base = qkv + tok0 * row_stride + head * kHeadDim;
+  const int n_ktiles = (len + 31) >> 5;
+  const int n_kchunks = (n_ktiles + 3) >> 2;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, half = lane >> 5;
+  const int qb = qc * 4 + wave;
+  const bool active = qb * 32 < len;                   // wave-uniform: a wave without queries still stages and meets barriers
+  const int q = qb * 32 + li;
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f16x8 qf[4], dof[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    qf[j] = dof[j] = zero8;
+    if (q < len) {
+      qf[j] = *(const f16x8*)(base + q * row_stride + (2 * j + half) * 8);
+      if (qkv_bias) qf[j] = qf[j] + *(const f16x8*)(qkv_bias + head * kHeadDim + (2 * j + half) * 8);
+      dof[j] = *(const f16x8*)(dctx + (tok0 + q) * hidden + head * kHeadDim + (2 * j + half) * 8);
+    }
+  }
+
+  auto stage = [&](int kc) {
+    constexpr int kIters = kChunk * 8 / 256;
+    f16x8 kreg[kIters], vreg[kIters];
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int i = tid + it * 256;
+      const int row = kc * kChunk + (i >> 3), c = i & 7;
+      kreg[it] = vreg[it] = zero8;
+      if (row < len) {
+        const _Float16* src = base + row * row_stride + c * 8;
+        kreg[it] = *(const f16x8*)(src + hidden);
+        vreg[it] = *(const f16x8*)(src + 2 * hidden);
+      }
+    }
+#pragma unroll
+    for (int it = 0; it < kIters; ++it) {
+      const int i = tid + it * 256;
+      const int r = i >> 3, c = i & 7;
+      *(f16x8*)(k_lds + r * kRowStride + c * 8) = kreg[it];
+      *(f16x8*)(v_lds + r * kRowStride + c * 8) = vreg[it];
+      stage_transposed(kreg[it], r, c, kt_lds, t_stride);
+    }
+  };
+  // S^T and dP^T of key tile kt of the staged chunk: lane = query, registers = keys (r & 3) + 8 (r >> 2) + 4 half
+  auto products = [&](int kc, int kt, f32x16& st, f32x16& dp) {
+    const _Float16* krow = k_lds + (kt * 32 + li) * kRowStride + half * 8;
+    const _Float16* vrow = v_lds + (kt * 32 + li) * kRowStride + half * 8;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      st = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(krow + j * 16), qf[j], st, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(vrow + j * 16), dof[j], dp, 0, 0, 0);
+    }
+    const int key_base = (kc * 4 + kt) * 32;
+    if (key_base + 32 > len) {                         // wave-uniform: only the last tile of a sequence is masked
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = key_base + (r & 3) + 8 * (r >> 2) + 4 * half;
+        st[r] = key < len ? st[r] : -__builtin_inff();
+      }
+    }
+  };
+
+  // pass 1: the softmax statistics and delta = sum_k P dP, online
+  float m = -__builtin_inff(), l = 0.f, dsum = 0.f;
+  for (int kc = 0; kc < n_kchunks; ++kc) {
+    if (kc) __syncthreads();                           // every wave is done with the previous chunk
+    stage(kc);
+    __syncthreads();
+    if (!active) continue;
+    const int tiles_here = n_ktiles - kc * 4 < 4 ? n_ktiles - kc * 4 : 4;
+    for (int kt = 0; kt < tiles_here; ++kt) {
+      f32x16 st = {0}, dp = {0};
+      products(kc, kt, st, dp);
+      float mt = st[0];
+#pragma unroll
+      for (int r = 1; r < 16; ++r) mt = __builtin_fmaxf(mt, st[r]);
+      mt = __builtin_fmaxf(mt, __shfl_xor(mt, 32, 64));
+      const float m_new = __builtin_fmaxf(m, mt);
+      const float mc = m_new * kExpScale;
+      float rs = 0.f, rd = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -mc));
+        rs += p;
+        rd = __builtin_fmaf(p, dp[r], rd);
+      }
+      rs += __shfl_xor(rs, 32, 64);
+      rd += __shfl_xor(rd, 32, 64);
+      const float alpha = __builtin_amdgcn_exp2f((m - m_new) * kExpScale);   // 0 at the first tile (m = -inf)
+      l = l * alpha + rs;
+      dsum = dsum * alpha + rd;
+      m = m_new;
+    }
+  }
+  const float lse2 = m * kExpScale + __log2f(l);   // log2 of the softmax denominator, scores in log2 units
+  const float delta = dsum / l;
+  if (active && half == 0 && q < len) {
+    ws_lse[(long long)head * n_tokens + tok0 + q] = lse2;
+    ws_delta[(long long)head * n_tokens + tok0 + q] = delta;
+  }
+
+  // pass 2: dS^T = P^T (dP^T - delta) in registers, dQ^T += K^T dS^T
+  f32x16 o0 = {0}, o1 = {0};
+  for (int kc = 0; kc < n_kchunks; ++kc) {
+    if (n_kchunks > 1) {                               // (a single chunk is still staged)
+      __syncthreads();
+      stage(kc);
+      __syncthreads();
+    }
+    if (!active) continue;
+    const int tiles_here = n_ktiles - kc * 4 < 4 ? n_ktiles - kc * 4 : 4;
+    for (int kt = 0; kt < tiles_here; ++kt) {
+      f32x16 st = {0}, dp = {0};
+      products(kc, kt, st, dp);
+      f16x8 dsf[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -lse2));
+        dsf[r >> 3][r & 7] = (_Float16)(p * (dp[r] - delta));
+      }
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int key0 = kt * 32 + 16 * jj + 4 * half;
+        o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(kt_lds, t_stride, li, key0), dsf[jj], o0, 0, 0, 0);
+        o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(kt_lds, t_stride, 32 + li, key0), dsf[jj], o1, 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();                                     // the last chunk is dead: its K rows become the output staging tiles
+  if (!active) return;
+  store_tile(o0, o1, 0.125f, smem + wave * 32 * kRowStride, lane, dqkv + tok0 * row_stride + head * kHeadDim, row_stride,
+             qb * 32, len);
+}
+
+__global__ __launch_bounds__(256, 2) void attention_bwd_dkv(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
+                                                            const _Float16* __restrict__ dctx, const int* __restrict__ cu_seqlens,
+                                                            int max_seq_len, int n_heads, int n_kc, long long n_tokens,
+                                                            _Float16* __restrict__ dqkv, const float* __restrict__ ws_lse,
+                                                            const float* __restrict__ ws_delta) {
+  constexpr int t_stride = kQChunk + kTPad;
+  __shared__ __attribute__((aligned(16))) _Float16 smem[2 * kQChunk * kRowStride + 2 * kHeadDim * t_stride];
+  __shared__ float lse_lds[kQChunk], delta_lds[kQChunk];
+  _Float16* q_lds = smem;                                                   // [64][72]  Q + b_q
+  _Float16* do_lds = smem + kQChunk * kRowStride;                           // [64][72]  d_ctx
+  _Float16* qt_lds = smem + 2 * kQChunk * kRowStride;                       // [64][68]  (Q + b_q)^T
+  _Float16* dot_lds = smem + 2 * kQChunk * kRowStride + kHeadDim * t_stride; // [64][68]  d_ctx^T
+  const int pair = blockIdx.x / n_kc, kc = blockIdx.x - pair * n_kc;
+  const int b = pair / n_heads, head = pair - b * n_heads;
+  const int hidden = n_heads * kHeadDim;
+  const long long row_stride = 3ll * hidden;
+  const long long tok0 = cu_seqlens[b];
+  int len = cu_seqlens[b + 1] - cu_seqlens[b];
+  len = len < 1 ? 1 : (len > max_seq_len ? max_seq_len : len);
+  if (tok0 < 0 || tok0 + len > n_tokens) return;
+  if (kc * kChunk >= len) return;                      // (the whole workgroup: no barrier has been met)
+  const _Float16* base = qkv + tok0 * row_stride + head * kHeadDim;
+  const _Float16* dbase = dctx + tok0 * hidden + head * kHeadDim;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, half = lane >> 5;
+  const int kb = kc * 4 + wave;
+  const bool active = kb * 32 < len;                   // wave-uniform
+  const int key = kb * 32 + li;
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f16x8 kf[4], vf[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    kf[j] = vf[j] = zero8;
+    if (key < len) {
+      const _Float16* src = base + key * row_stride + (2 * j + half) * 8;
+      kf[j] = *(const f16x8*)(src + hidden);           // (no key bias: the forward drops it)
+      vf[j] = *(const f16x8*)(src + 2 * hidden);
+    }
+  }
+  f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
+  const int n_qchunks = (len + kQChunk - 1) / kQChunk;
+  for (int qc = 0; qc < n_qchunks; ++qc) {
+    if (qc) __syncthreads();                           // every wave is done with the previous chunk
+    {
+      constexpr int kIters = kQChunk * 8 / 256;
+      f16x8 qreg[kIters], dreg[kIters];
+#pragma unroll
+      for (int it = 0; it < kIters; ++it) {
+        const int i = tid + it * 256;
+        const int row = qc * kQChunk + (i >> 3), c = i & 7;
+        qreg[it] = dreg[it] = zero8;
+        if (row < len) {
+          qreg[it] = *(const f16x8*)(base + row * row_stride + c * 8);
+          if (qkv_bias) qreg[it] = qreg[it] + *(const f16x8*)(qkv_bias + head * kHeadDim + c * 8);
+          dreg[it] = *(const f16x8*)(dbase + (long long)row * hidden + c * 8);
+        }
+      }
+#pragma unroll
+      for (int it = 0; it < kIters; ++it) {
+        const int i = tid + it * 256;
+        const int r = i >> 3, c = i & 7;
+        *(f16x8*)(q_lds + r * kRowStride + c * 8) = qreg[it];
+        *(f16x8*)(do_lds + r * kRowStride + c * 8) = dreg[it];
+        stage_transposed(qreg[it], r, c, qt_lds, t_stride);
+        stage_transposed(dreg[it], r, c, dot_lds, t_stride);
+      }
+      if (tid < kQChunk) {
+        const int row = qc * kQChunk + tid;
+        // a query row that does not exist has P = exp2(s - inf) = 0
+        lse_lds[tid] = row < len ? ws_lse[(long long)head * n_tokens + tok0 + row] : __builtin_inff();
+        delta_lds[tid] = row < len ? ws_delta[(long long)head * n_tokens + tok0 + row] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (!active) continue;
+    const int rows_here = len - qc * kQChunk < kQChunk ? len - qc * kQChunk : kQChunk;
+    const int tiles_here = (rows_here + 31) >> 5;
+    for (int qt = 0; qt < tiles_here; ++qt) {
+      // S = Q K^T and dP = dO V^T of query tile qt: lane = key, registers = queries (r & 3) + 8 (r >> 2) + 4 half
+      f32x16 st = {0}, dp = {0};
+      const _Float16* qrow = q_lds + (qt * 32 + li) * kRowStride + half * 8;
+      const _Float16* drow = do_lds + (qt * 32 + li) * kRowStride + half * 8;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(qrow + j * 16), kf[j], st, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(drow + j * 16), vf[j], dp, 0, 0, 0);
+      }
+      f16x8 pf[2], dsf[2];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qi = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -lse_lds[qi]));
+        p = key < len ? p : 0.f;                       // a key row that does not exist was masked in the forward
+        pf[r >> 3][r & 7] = (_Float16)p;
+        dsf[r >> 3][r & 7] = (_Float16)(p * (dp[r] - delta_lds[qi]));
+      }
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int q0 = qt * 32 + 16 * jj + 4 * half;
+        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(dot_lds, t_stride, li, q0), pf[jj], dv0, 0, 0, 0);
+        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(dot_lds, t_stride, 32 + li, q0), pf[jj], dv1, 0, 0, 0);
+        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(qt_lds, t_stride, li, q0), dsf[jj], dk0, 0, 0, 0);
+        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(qt_lds, t_stride, 32 + li, q0), dsf[jj], dk1, 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();                                     // the last chunk is dead: Q and d_ctx rows become the output staging tiles
+  if (!active) return;
+  _Float16* tile = smem + wave * 32 * kRowStride;      // 4 x 32 x 72 = the two row-major arrays
+  _Float16* out = dqkv + tok0 * row_stride + head * kHeadDim;
+  store_tile(dk0, dk1, 0.125f, tile, lane, out + hidden, row_stride, kb * 32, len);
+  store_tile(dv0, dv1, 1.0f, tile, lane, out + 2 * hidden, row_stride, kb * 32, len);
+}
+
+// ---- in-batch loss gradient -------------------------------------------------------------------------------------------------
+// loss = mean_i (lse_i - s[i, t_i]), s = q c^T:  d s[i, j] = (g / nq) (exp(s[i, j] - lse_i) - [j == t_i]).
+// One wave owns 32 rows of the side it differentiates (X: q when BY_ROW, else c) and walks the other side (Y) in tiles of 32
+// through LDS (rows and transposed): G^T = Y X^T on the matrix pipe with lane = x and the 16 y of a step in registers, the
+// coefficients in registers as fp16, then dX^T += Y^T coeff.  The score matrix exists one 32 x 32 tile at a time.
+constexpr int kEmb = PROQA_EMBED_DIM;
+constexpr int kEmbStride = kEmb + 8;
+constexpr int kEmbTStride = 32 + kTPad;
+
+template <bool BY_ROW>
+__global__ __launch_bounds__(64) void inbatch_loss_grad(const _Float16* __restrict__ xs, int nx, const _Float16* __restrict__ ys,
+                                                        int ny, const int* __restrict__ target, const float* __restrict__ lse,
+                                                        const float* __restrict__ grad_in, int nq,
+                                                        _Float16* __restrict__ dx) {
+  __shared__ __attribute__((aligned(16))) _Float16 y_lds[32 * kEmbStride];     // [32 y][136]
+  __shared__ __attribute__((aligned(16))) _Float16 yt_lds[kEmb * kEmbTStride];  // [128 d][36]
+  __shared__ float lse_lds[32];
+  __shared__ int tgt_lds[32];
+  const int lane = threadIdx.x, li = lane & 31, half = lane >> 5;
+  const int x0 = blockIdx.x * 32, x = x0 + li;
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f16x8 xf[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) xf[j] = x < nx ? *(const f16x8*)(xs + (long long)x * kEmb + (2 * j + half) * 8) : zero8;
+  // BY_ROW: the statistics of the lane's own question
+  const float lse_x = BY_ROW && x < nx ? lse[x] : 0.f;
+  const int tgt_x = BY_ROW && x < nx ? (target ? target[x] : x) : -1;
+  f32x16 acc[4] = {{0}, {0}, {0}, {0}};
+  for (int y0 = 0; y0 < ny; y0 += 32) {
+    // stage 32 rows of Y: 32 x 16 pieces of 16 bytes, 8 per lane; (r, c) = (i >> 3, i & 7) of a 64-column half so that rows
+    // r and r ^ 1 sit 8 lanes apart (stage_transposed)
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+      const int i = lane + 64 * (it & 3), r = i >> 3, c = i & 7, hc = it >> 2;   // hc: columns 0-63 / 64-127
+      const int y = y0 + r;
+      const f16x8 v = y < ny ? *(const f16x8*)(ys + (long long)y * kEmb + hc * 64 + c * 8) : zero8;
+      *(f16x8*)(y_lds + r * kEmbStride + hc * 64 + c * 8) = v;
+      stage_transposed(v, r, c, yt_lds + hc * 64 * kEmbTStride, kEmbTStride);
+    }
+    if (!BY_ROW && lane < 32) {
+      const int y = y0 + lane;       // Y = the questions
+      lse_lds[lane] = y < ny ? lse[y] : __builtin_inff();
+      tgt_lds[lane] = y < ny ? (target ? target[y] : y) : -1;
+    }
+    __syncthreads();                 // (one wave: orders the LDS writes before the reads for the compiler)
+    f32x16 g = {0};
+    const _Float16* yrow = y_lds + li * kEmbStride + half * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) g = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(yrow + j * 16), xf[j], g, 0, 0, 0);
+    // the coefficients as fp16 hi + lo: p - 1 of a gold pair carries the whole gradient of a well-trained row
+    f16x8 cf[2], cl[2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int yi = (r & 3) + 8 * (r >> 2) + 4 * half, y = y0 + yi;
+      float p, hot;
+      if (BY_ROW) {
+        p = __expf(g[r] - lse_x);
+        hot = y == tgt_x ? 1.f : 0.f;
+      } else {
+        p = __expf(g[r] - lse_lds[yi]);
+        hot = tgt_lds[yi] == x ? 1.f : 0.f;
+      }
+      const float coef = y < ny ? p - hot : 0.f;
+      const _Float16 hi = (_Float16)coef;
+      cf[r >> 3][r & 7] = hi;
+      cl[r >> 3][r & 7] = (_Float16)(coef - (float)hi);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj) {
+      const int k0 = 16 * jj + 4 * half;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const f16x8 yt = transposed_fragment(yt_lds, kEmbTStride, 32 * t + li, k0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(yt, cf[jj], acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(yt, cl[jj], acc[t], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  // lane = x, registers of acc[t] = columns 32 t + (r & 3) + 8 (r >> 2) + 4 half: 8-byte pieces straight to the row
+  if (x >= nx) return;
+  const float scale = grad_in[0] / (float)nq;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) {
+      f16x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = (_Float16)(acc[t][gq * 4 + e] * scale);
+      *(f16x4*)(dx + (long long)x * kEmb + 32 * t + gq * 8 + 4 * half) = o;
+    }
+}
+
+int slabs_for(int64_t rows, int64_t min_rows_per_slab, int64_t* rows_per_slab) {
+  int64_t per = std::max<int64_t>(min_rows_per_slab, ceil_div<int64_t>(rows, kMaxSlabs));
+  per = round_up<int64_t>(per, 4);
+  *rows_per_slab = per;
+  return (int)ceil_div<int64_t>(rows, per);
+}
+
+int launch_reduce(const float* ws, int n_slabs, int n_k, int cols, float* o0, float* o1, float* o2, float* o3, int accumulate,
+                  hipStream_t st) {
+  hipLaunchKernelGGL(reduce_slabs, dim3((unsigned)ceil_div<int>(n_k * cols, 256)), dim3(256), 0, st, ws, n_slabs, n_k, cols,
+                     o0, o1, o2, o3, accumulate);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+}  // namespace
+}  // namespace proqa
+
+using namespace proqa;
+
+extern "C" {
+
+size_t proqa_backward_workspace_bytes(int cols) {
+  return cols > 0 ? (size_t)kMaxSlabs * 3 * (size_t)cols * sizeof(float) : 0;
+}
+
+size_t proqa_attention_backward_workspace_bytes(int64_t n_tokens, int n_heads) {
+  return n_tokens > 0 && n_heads > 0 ? (size_t)2 * (size_t)n_tokens * (size_t)n_heads * sizeof(float) : 0;
+}
+
+int proqa_colsum_f16(const void* x, int64_t rows, int cols, float* out, void* ws, size_t ws_bytes, void* stream) {
+  if (!x || !out || !ws) return fail(PROQA_EINVAL, "colsum: NULL argument");
+  if (rows < 0 || cols <= 0 || cols % 8 || cols > 256 * kMaxColChunks * 8)
+    return fail(PROQA_EINVAL, "colsum: cols=%d must be a multiple of 8 and <= %d", cols, 256 * kMaxColChunks * 8);
+  if (ws_bytes < proqa_backward_workspace_bytes(cols)) return fail(PROQA_EINVAL, "colsum: workspace too small");
+  hipStream_t st = as_stream(stream);
+  if (rows == 0) return hipMemsetAsync(out, 0, (size_t)cols * sizeof(float), st) == hipSuccess ? PROQA_OK : fail(PROQA_EHIP, "colsum: memset");
+  int64_t per;
+  const int n_slabs = slabs_for(rows, 16, &per);
+  hipLaunchKernelGGL(column_kernel<0>, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)x, (const _Float16*)nullptr,
+                     (const _Float16*)nullptr, (long long)rows, cols, (long long)per, (_Float16*)nullptr, (float*)ws);
+  PROQA_LAUNCH_CHECK();
+  return launch_reduce((const float*)ws, n_slabs, 1, cols, out, nullptr, nullptr, nullptr, 0, st);
+}
+
+int proqa_bias_gelu_out_f16(const void* x, const void* bias, int64_t rows, int cols, void* out, void* stream) {
+  if (!x || !bias || !out) return fail(PROQA_EINVAL, "bias_gelu_out: NULL argument");
+  if (rows < 0 || cols <= 0 || cols % 8) return fail(PROQA_EINVAL, "bias_gelu_out: cols=%d must be a multiple of 8", cols);
+  if (rows == 0) return PROQA_OK;
+  const long long n_chunks = rows * (long long)(cols / 8);
+  const unsigned grid = (unsigned)std::min<long long>(ceil_div<long long>(n_chunks, 256), (long long)device_cu_count() * 8);
+  hipLaunchKernelGGL(bias_gelu_out, dim3(grid), dim3(256), 0, as_stream(stream), (const _Float16*)x, (const _Float16*)bias,
+                     n_chunks, cols / 8, (_Float16*)out);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int proqa_bias_gelu_backward_f16(const void* dy, const void* x_pre, const void* bias, int64_t rows, int cols, void* dx,
+                                 float* dbias, void* ws, size_t ws_bytes, void* stream) {
+  if (!dy || !x_pre || !bias || !dx || !dbias || !ws) return fail(PROQA_EINVAL, "bias_gelu_backward: NULL argument");
+  if (rows < 0 || cols <= 0 || cols % 8 || cols > 256 * kMaxColChunks * 8)
+    return fail(PROQA_EINVAL, "bias_gelu_backward: cols=%d must be a multiple of 8 and <= %d", cols, 256 * kMaxColChunks * 8);
+  if (ws_bytes < proqa_backward_workspace_bytes(cols)) return fail(PROQA_EINVAL, "bias_gelu_backward: workspace too small");
+  hipStream_t st = as_stream(stream);
+  if (rows == 0)
+    return hipMemsetAsync(dbias, 0, (size_t)cols * sizeof(float), st) == hipSuccess ? PROQA_OK : fail(PROQA_EHIP, "bias_gelu_backward: memset");
+  int64_t per;
+  const int n_slabs = slabs_for(rows, 16, &per);
+  hipLaunchKernelGGL(column_kernel<1>, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)x_pre, (const _Float16*)dy,
+                     (const _Float16*)bias, (long long)rows, cols, (long long)per, (_Float16*)dx, (float*)ws);
+  PROQA_LAUNCH_CHECK();
+  return launch_reduce((const float*)ws, n_slabs, 1, cols, dbias, nullptr, nullptr, nullptr, 0, st);
+}
+
+int proqa_bias_residual_layernorm_backward_f16(const void* dy, const void* x, const void* bias, const void* residual,
+                                               const void* gamma, float eps, int64_t rows, int cols, void* dz, float* dgamma,
+                                               float* dbeta, float* dbias, void* ws, size_t ws_bytes, void* stream) {
+  if (!dy || !x || !bias || !residual || !gamma || !dz || !dgamma || !dbeta || !dbias || !ws)
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_backward: NULL argument");
+  if (rows < 0 || cols <= 0 || cols % 8 || cols > 64 * kMaxChunksPerLane * 8)
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_backward: cols=%d must be a multiple of 8 and <= %d", cols,
+                64 * kMaxChunksPerLane * 8);
+  if (ws_bytes < proqa_backward_workspace_bytes(cols))
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_backward: workspace too small");
+  hipStream_t st = as_stream(stream);
+  if (rows == 0) {
+    for (float* p : {dgamma, dbeta, dbias}) PROQA_HIP(hipMemsetAsync(p, 0, (size_t)cols * sizeof(float), st));
+    return PROQA_OK;
+  }
+  int64_t per;
+  const int n_slabs = slabs_for(rows, 16, &per);
+  hipLaunchKernelGGL(bias_residual_layernorm_bwd, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)dy,
+                     (const _Float16*)x, (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma, eps,
+                     (long long)rows, cols, (long long)per, (_Float16*)dz, (float*)ws);
+  PROQA_LAUNCH_CHECK();
+  return launch_reduce((const float*)ws, n_slabs, 3, cols, dgamma, dbeta, dbias, nullptr, 0, st);
+}
+
+int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids_dev, const int32_t* cu_seqlens_dev,
+                                              int batch, int seq_len, int hidden, int64_t n_tokens, const void* word_emb,
+                                              int64_t vocab, const void* pos_emb, const void* type_emb, const void* ln_gamma,
+                                              float eps, float* dgamma, float* dbeta, float* d_word, float* d_pos,
+                                              float* d_type0, void* ws, size_t ws_bytes, void* stream) {
+  if (!dy || !ids_dev || !cu_seqlens_dev || !word_emb || !pos_emb || !type_emb || !ln_gamma || !dgamma || !dbeta || !d_word ||
+      !d_pos || !d_type0 || !ws)
+    return fail(PROQA_EINVAL, "embed_layernorm_backward: NULL argument");
+  if (batch < 0 || seq_len <= 0 || seq_len > kMaxSlabs || vocab <= 0 || n_tokens < 0)
+    return fail(PROQA_EINVAL, "embed_layernorm_backward: bad sizes (seq_len <= %d)", kMaxSlabs);
+  if (hidden <= 0 || hidden % 8 || hidden > 64 * kMaxChunksPerLane * 8)
+    return fail(PROQA_EINVAL, "embed_layernorm_backward: hidden=%d must be a multiple of 8 and <= %d", hidden,
+                64 * kMaxChunksPerLane * 8);
+  if (ws_bytes < proqa_backward_workspace_bytes(hidden)) return fail(PROQA_EINVAL, "embed_layernorm_backward: workspace too small");
+  if (batch == 0 || n_tokens == 0) return PROQA_OK;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(embed_layernorm_bwd, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
+                     (const long long*)ids_dev, (const int*)cu_seqlens_dev, batch, seq_len, hidden, (const _Float16*)word_emb,
+                     (long long)vocab, (const _Float16*)pos_emb, (const _Float16*)type_emb, (const _Float16*)ln_gamma, eps,
+                     (long long)n_tokens, d_word, d_pos, (float*)ws);
+  PROQA_LAUNCH_CHECK();
+  return launch_reduce((const float*)ws, seq_len, 3, hidden, dgamma, dbeta, nullptr, d_type0, 1, st);
+}
+
+int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx, const int32_t* cu_seqlens_dev,
+                                 int batch, int max_seq_len, int n_heads, int64_t n_tokens, void* d_qkv, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  if (!qkv || !d_ctx || !cu_seqlens_dev || !d_qkv || !ws) return fail(PROQA_EINVAL, "attention_backward: NULL argument");
+  if (batch < 0 || max_seq_len <= 0 || max_seq_len > 512 || n_heads <= 0 || n_tokens < 0)
+    return fail(PROQA_EINVAL, "attention_backward: bad sizes (max_seq_len <= 512)");
+  if (ws_bytes < proqa_attention_backward_workspace_bytes(n_tokens, n_heads))
+    return fail(PROQA_EINVAL, "attention_backward: workspace too small");
+  if (batch == 0 || n_tokens == 0) return PROQA_OK;
+  hipStream_t st = as_stream(stream);
+  const int n_c = (max_seq_len + kChunk - 1) / kChunk;
+  const unsigned grid = (unsigned)batch * (unsigned)n_heads * (unsigned)n_c;
+  float* ws_lse = (float*)ws;
+  float* ws_delta = ws_lse + n_tokens * n_heads;
+  hipLaunchKernelGGL(attention_bwd_dq, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                     (_Float16*)d_qkv, ws_lse, ws_delta);
+  PROQA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attention_bwd_dkv, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                     (_Float16*)d_qkv, (const float*)ws_lse, (const float*)ws_delta);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int proqa_inbatch_loss_grad_f16(const void* q, const void* c, const int32_t* target, const float* lse, const float* grad_in,
+                                int nq, int nc, int dim, void* dq, void* dc, void* stream) {
+  if (nq < 0 || nc < 0) return fail(PROQA_EINVAL, "inbatch_loss_grad: negative size");
+  if (dim != kEmb) return fail(PROQA_EINVAL, "inbatch_loss_grad: dim=%d must be %d", dim, kEmb);
+  if (nq == 0) {
+    if (nc > 0 && dc) PROQA_HIP(hipMemsetAsync(dc, 0, (size_t)nc * kEmb * sizeof(_Float16), as_stream(stream)));
+    return PROQA_OK;
+  }
+  if (nc == 0) return fail(PROQA_EINVAL, "inbatch_loss_grad: nc == 0 with nq > 0");
+  if (!q || !c || !lse || !grad_in || !dq || !dc) return fail(PROQA_EINVAL, "inbatch_loss_grad: NULL argument");
+  if (!target && nq > nc) return fail(PROQA_EINVAL, "inbatch_loss_grad: the implicit target i needs nq <= nc");
+  if (nq > (1 << 24) || nc > (1 << 24)) return fail(PROQA_EINVAL, "inbatch_loss_grad: more than 2^24 rows");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(inbatch_loss_grad<true>, dim3((unsigned)ceil_div<int>(nq, 32)), dim3(64), 0, st, (const _Float16*)q, nq,
+                     (const _Float16*)c, nc, (const int*)target, lse, grad_in, nq, (_Float16*)dq);
+  PROQA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(inbatch_loss_grad<false>, dim3((unsigned)ceil_div<int>(nc, 32)), dim3(64), 0, st, (const _Float16*)c, nc,
+                     (const _Float16*)q, nq, (const int*)target, lse, grad_in, nq, (_Float16*)dc);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,432 @@
+"""Trainable dual-tower retriever on MI355X: the towers of proqa_amd.retriever with gradients.
+
+`TrainableRetriever` is a torch.nn.Module with the reference's parameter names (retrieval/retriever.py:10-31), so the
+reference's training loop (retrieval/train_retriever.py:196-214) runs with the model class swapped, and the checkpoint it
+saves loads into get_embed.py, eval_retrieval.py and train_retriever.py --do_predict unchanged.
+
+Every operator between the dense products is a torch.autograd.Function over a pair of hand-written HIP kernels of
+libproqa_hip.so -- the forward operator the inference path uses and its backward (csrc/train_kernels.hip): embedding +
+LayerNorm, attention, bias + GELU, bias + residual + LayerNorm, and the in-batch loss.  The forward kernels save
+nothing; each backward recomputes what it needs from the forward's inputs, which autograd keeps.
+
+WHERE TORCH COMPUTES.  The dense products go through torch.nn.functional.linear on fp16 tensors, forward and backward:
+the same rocBLAS / hipBLASLt the inference path calls from csrc/encoder.cpp.  This file is the one place in proqa_amd/
+where torch computes; the products move behind the C ABI in a follow-up.  Biases of the encoder layers are NOT passed to
+linear: the fused operators add them and return their gradients.  The pooler and the projection (two [B, hidden]
+products and a tanh) are torch as a whole, biases included.
+
+Precision: fp32 master parameters, cast to fp16 once per step and tower (apex O1 semantics; the reference trains with
+--fp16); activations and their gradients fp16, every sum inside a kernel fp32, gradients of parameter vectors and embedding
+tables fp32.  Use a loss scale (a fixed one or torch.amp.GradScaler): every backward operator is linear in its incoming
+gradient and passes inf / NaN through.
+
+Deviation: NO DROPOUT.  The reference trains with transformers' dropout of 0.1 on hidden states and attention
+probabilities; this module trains without, and refuses any other setting.  There is no CPU path.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import _lib
+from ._lib import EMBED_DIM
+from .inbatch import inbatch_eval
+from .retriever import config_from_dict, tower_keys
+
+_WORKSPACES = {}
+
+
+def _workspace(device, nbytes):
+    """Device scratch of the backward operators: one buffer per device, grown on demand (calls are ordered on the
+    current stream)."""
+    key = (device.type, device.index)
+    t = _WORKSPACES.get(key)
+    if t is None or t.numel() < nbytes:
+        t = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        _WORKSPACES[key] = t
+    return t
+
+
+def _f16(x, name):
+    if not x.is_cuda or x.dtype != torch.float16:
+        raise ValueError(f"{name} must be a float16 CUDA tensor, got {x.dtype} on {x.device}")
+    return x.contiguous()
+
+
+def _call(fn, dev, *args):
+    with torch.cuda.device(dev):
+        _lib.check(fn(*args, _lib.current_stream_ptr()))
+
+
+# ---- the operators, tensor in / tensor out (no autograd) -------------------------------------------------------------------
+
+def colsum(x):
+    """[rows, cols] fp16 -> [cols] fp32, rows added in a fixed order (proqa_colsum_f16)."""
+    lib = _lib.load()
+    x = _f16(x, "x")
+    rows, cols = x.shape
+    out = torch.empty(cols, dtype=torch.float32, device=x.device)
+    ws = _workspace(x.device, lib.proqa_backward_workspace_bytes(cols))
+    _call(lib.proqa_colsum_f16, x.device, x.data_ptr(), rows, cols, out.data_ptr(), ws.data_ptr(), ws.numel())
+    return out
+
+
+def bias_gelu(x_pre, bias):
+    lib = _lib.load()
+    x_pre, bias = _f16(x_pre, "x_pre"), _f16(bias, "bias")
+    rows, cols = x_pre.shape
+    out = torch.empty_like(x_pre)
+    _call(lib.proqa_bias_gelu_out_f16, x_pre.device, x_pre.data_ptr(), bias.data_ptr(), rows, cols, out.data_ptr())
+    return out
+
+
+def bias_gelu_backward(dy, x_pre, bias):
+    """-> (dx fp16 [rows, cols], dbias fp32 [cols])"""
+    lib = _lib.load()
+    dy, x_pre, bias = _f16(dy, "dy"), _f16(x_pre, "x_pre"), _f16(bias, "bias")
+    rows, cols = x_pre.shape
+    dx = torch.empty_like(x_pre)
+    dbias = torch.empty(cols, dtype=torch.float32, device=dy.device)
+    ws = _workspace(dy.device, lib.proqa_backward_workspace_bytes(cols))
+    _call(lib.proqa_bias_gelu_backward_f16, dy.device, dy.data_ptr(), x_pre.data_ptr(), bias.data_ptr(), rows, cols,
+          dx.data_ptr(), dbias.data_ptr(), ws.data_ptr(), ws.numel())
+    return dx, dbias
+
+
+def bias_residual_layernorm(x, bias, residual, gamma, beta, eps):
+    lib = _lib.load()
+    x, residual = _f16(x, "x"), _f16(residual, "residual")
+    rows, cols = x.shape
+    out = torch.empty_like(x)
+    _call(lib.proqa_bias_residual_layernorm_f16, x.device, x.data_ptr(), _f16(bias, "bias").data_ptr(), residual.data_ptr(),
+          _f16(gamma, "gamma").data_ptr(), _f16(beta, "beta").data_ptr(), float(eps), rows, cols, out.data_ptr())
+    return out
+
+
+def bias_residual_layernorm_backward(dy, x, bias, residual, gamma, eps):
+    """-> (dz fp16 [rows, cols]: the gradient of x and of residual, dgamma, dbeta, dbias fp32 [cols])"""
+    lib = _lib.load()
+    dy, x, residual = _f16(dy, "dy"), _f16(x, "x"), _f16(residual, "residual")
+    bias, gamma = _f16(bias, "bias"), _f16(gamma, "gamma")
+    rows, cols = x.shape
+    dz = torch.empty_like(x)
+    dgamma, dbeta, dbias = (torch.empty(cols, dtype=torch.float32, device=x.device) for _ in range(3))
+    ws = _workspace(x.device, lib.proqa_backward_workspace_bytes(cols))
+    _call(lib.proqa_bias_residual_layernorm_backward_f16, x.device, dy.data_ptr(), x.data_ptr(), bias.data_ptr(),
+          residual.data_ptr(), gamma.data_ptr(), float(eps), rows, cols, dz.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+          dbias.data_ptr(), ws.data_ptr(), ws.numel())
+    return dz, dgamma, dbeta, dbias
+
+
+def embed_layernorm(ids, cu_seqlens, n_tokens, word, pos, type0, gamma, beta, eps):
+    """ids int64 [batch, seq_len] right-padded, cu_seqlens int32 [batch + 1] -> packed [n_tokens, hidden] fp16"""
+    lib = _lib.load()
+    batch, seq_len = ids.shape
+    hidden = word.shape[1]
+    out = torch.empty((n_tokens, hidden), dtype=torch.float16, device=ids.device)
+    _call(lib.proqa_embed_layernorm_varlen_f16, ids.device, ids.data_ptr(), cu_seqlens.data_ptr(), batch, seq_len, hidden,
+          _f16(word, "word").data_ptr(), word.shape[0], _f16(pos, "pos").data_ptr(), _f16(type0, "type0").data_ptr(),
+          _f16(gamma, "gamma").data_ptr(), _f16(beta, "beta").data_ptr(), float(eps), out.data_ptr())
+    return out
+
+
+def embed_layernorm_backward(dy, ids, cu_seqlens, word, pos, type0, gamma, eps):
+    """-> fp32 (dgamma [hidden], dbeta [hidden], d_word [vocab, hidden], d_pos [positions, hidden], d_type0 [hidden])"""
+    lib = _lib.load()
+    dy = _f16(dy, "dy")
+    batch, seq_len = ids.shape
+    n_tokens, hidden = dy.shape
+    if seq_len > pos.shape[0]:
+        raise ValueError(f"sequence length {seq_len} exceeds the {pos.shape[0]} positions of the table")
+    dev = dy.device
+    dgamma, dbeta, d_type0 = (torch.zeros(hidden, dtype=torch.float32, device=dev) for _ in range(3))
+    d_word = torch.zeros(word.shape, dtype=torch.float32, device=dev)
+    d_pos = torch.zeros(pos.shape, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.proqa_backward_workspace_bytes(hidden))
+    _call(lib.proqa_embed_layernorm_varlen_backward_f16, dev, dy.data_ptr(), ids.data_ptr(), cu_seqlens.data_ptr(), batch,
+          seq_len, hidden, n_tokens, _f16(word, "word").data_ptr(), word.shape[0], _f16(pos, "pos").data_ptr(),
+          _f16(type0, "type0").data_ptr(), _f16(gamma, "gamma").data_ptr(), float(eps), dgamma.data_ptr(), dbeta.data_ptr(),
+          d_word.data_ptr(), d_pos.data_ptr(), d_type0.data_ptr(), ws.data_ptr(), ws.numel())
+    return dgamma, dbeta, d_word, d_pos, d_type0
+
+
+def attention(qkv, qkv_bias, cu_seqlens, batch, max_seq_len, n_heads):
+    """qkv packed [T, 3*hidden] fp16 (before the bias), qkv_bias [3*hidden] fp16 or None -> ctx [T, hidden]"""
+    lib = _lib.load()
+    qkv = _f16(qkv, "qkv")
+    out = torch.empty((qkv.shape[0], n_heads * 64), dtype=torch.float16, device=qkv.device)
+    _call(lib.proqa_attention_ex_f16, qkv.device, qkv.data_ptr(), _f16(qkv_bias, "qkv_bias").data_ptr() if qkv_bias is not None
+          else None, None, cu_seqlens.data_ptr(), batch, max_seq_len, n_heads, 0, out.data_ptr())
+    return out
+
+
+def attention_backward(qkv, qkv_bias, d_ctx, cu_seqlens, batch, max_seq_len, n_heads):
+    """-> d_qkv [T, 3*hidden] fp16; the gradient of qkv_bias is colsum(d_qkv)"""
+    lib = _lib.load()
+    qkv, d_ctx = _f16(qkv, "qkv"), _f16(d_ctx, "d_ctx")
+    n_tokens = qkv.shape[0]
+    if qkv.shape[1] != 3 * n_heads * 64 or d_ctx.shape != (n_tokens, n_heads * 64):
+        raise ValueError(f"attention_backward: qkv {tuple(qkv.shape)} / d_ctx {tuple(d_ctx.shape)} do not fit {n_heads} heads of 64")
+    d_qkv = torch.empty_like(qkv)
+    ws = _workspace(qkv.device, lib.proqa_attention_backward_workspace_bytes(n_tokens, n_heads))
+    _call(lib.proqa_attention_backward_f16, qkv.device, qkv.data_ptr(), _f16(qkv_bias, "qkv_bias").data_ptr() if qkv_bias is not None
+          else None, d_ctx.data_ptr(), cu_seqlens.data_ptr(), batch, max_seq_len, n_heads, n_tokens, d_qkv.data_ptr(),
+          ws.data_ptr(), ws.numel())
+    return d_qkv
+
+
+def inbatch_loss_grad(q, c, target, lse, grad_in):
+    """Gradient of mean_i (lse_i - s[i, target_i]) times the device scalar grad_in -> (dq, dc) fp16"""
+    lib = _lib.load()
+    q, c = _f16(q, "q"), _f16(c, "c")
+    t = None if target is None else target.to(device=q.device, dtype=torch.int32).contiguous()
+    lse = lse.to(torch.float32).contiguous()
+    g = grad_in.to(device=q.device, dtype=torch.float32).reshape(1).contiguous()
+    dq, dc = torch.empty_like(q), torch.empty_like(c)
+    _call(lib.proqa_inbatch_loss_grad_f16, q.device, q.data_ptr(), c.data_ptr(), t.data_ptr() if t is not None else None,
+          lse.data_ptr(), g.data_ptr(), q.shape[0], c.shape[0], q.shape[1], dq.data_ptr(), dc.data_ptr())
+    return dq, dc
+
+
+# ---- autograd: each forward operator with its backward ---------------------------------------------------------------------
+# Parameters enter as the fp32 masters and are cast inside forward, so that their gradients leave as fp32.
+
+class _EmbedLayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ids, cu_seqlens, n_tokens, word, pos, types, gamma, beta, eps):
+        w16, p16, t16, g16 = word.half(), pos.half(), types[0].half().contiguous(), gamma.half()
+        ctx.save_for_backward(ids, cu_seqlens, w16, p16, t16, g16)
+        ctx.eps, ctx.n_types = eps, types.shape[0]
+        return embed_layernorm(ids, cu_seqlens, n_tokens, w16, p16, t16, g16, beta.half(), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        ids, cu, w16, p16, t16, g16 = ctx.saved_tensors
+        dgamma, dbeta, d_word, d_pos, d_type0 = embed_layernorm_backward(dy, ids, cu, w16, p16, t16, g16, ctx.eps)
+        d_types = torch.zeros((ctx.n_types, d_type0.shape[0]), dtype=torch.float32, device=dy.device)
+        d_types[0] = d_type0          # token_type_ids are never passed: row 0 only
+        return None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None
+
+
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, qkv_bias, cu_seqlens, batch, max_seq_len, n_heads):
+        b16 = qkv_bias.half()
+        ctx.save_for_backward(qkv, b16, cu_seqlens)
+        ctx.dims = (batch, max_seq_len, n_heads)
+        return attention(qkv, b16, cu_seqlens, batch, max_seq_len, n_heads)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_ctx):
+        qkv, b16, cu = ctx.saved_tensors
+        d_qkv = attention_backward(qkv, b16, d_ctx, cu, *ctx.dims)
+        return d_qkv, colsum(d_qkv), None, None, None, None
+
+
+class _BiasGelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x_pre, bias):
+        b16 = bias.half()
+        ctx.save_for_backward(x_pre, b16)
+        return bias_gelu(x_pre, b16)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x_pre, b16 = ctx.saved_tensors
+        return bias_gelu_backward(dy, x_pre, b16)
+
+
+class _BiasResidualLayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, bias, residual, gamma, beta, eps):
+        b16, g16 = bias.half(), gamma.half()
+        ctx.save_for_backward(x, b16, residual, g16)
+        ctx.eps = eps
+        return bias_residual_layernorm(x, b16, residual, g16, beta.half(), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, b16, residual, g16 = ctx.saved_tensors
+        dz, dgamma, dbeta, dbias = bias_residual_layernorm_backward(dy, x, b16, residual, g16, ctx.eps)
+        return dz, dbias, dz, dgamma, dbeta, None
+
+
+class _InBatchLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, c, target):
+        out = inbatch_eval(q, c, target)
+        ctx.save_for_backward(q, c, out["lse"])
+        ctx.target = target
+        return (out["lse"] - out["gold"]).mean()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, c, lse = ctx.saved_tensors
+        dq, dc = inbatch_loss_grad(q, c, ctx.target, lse, grad_out)
+        return dq, dc, None
+
+
+def inbatch_loss(q, c, target=None):
+    """CrossEntropyLoss(q @ c.T, target) (target None: arange) as an fp32 scalar with gradients, without the [nq, nc]
+    product in memory: the forward value is proqa_inbatch_eval_f16's mean(lse - gold), the backward
+    proqa_inbatch_loss_grad_f16.  q, c: fp16 [n, 128] device tensors."""
+    return _InBatchLoss.apply(q, c, target)
+
+
+# ---- the module -----------------------------------------------------------------------------------------------------------
+
+def state_dict_keys(config):
+    """The reference checkpoint's keys (BertForRetriever.state_dict_keys), without a GPU."""
+    cfg = config if not isinstance(config, dict) else config_from_dict(config)
+    n = cfg.num_hidden_layers
+    return (tower_keys("bert_q", n) + tower_keys("bert_c", n) + ["proj_q.weight", "proj_q.bias", "proj_c.weight", "proj_c.bias"])
+
+
+def _parameter_shapes(cfg):
+    H, I = cfg.hidden_size, cfg.intermediate_size
+    shapes = {}
+    for key in state_dict_keys(cfg):
+        if key.startswith("proj_"):
+            shapes[key] = (EMBED_DIM, H) if key.endswith("weight") else (EMBED_DIM,)
+        elif "word_embeddings" in key:
+            shapes[key] = (cfg.vocab_size, H)
+        elif "position_embeddings" in key:
+            shapes[key] = (cfg.max_position_embeddings, H)
+        elif "token_type_embeddings" in key:
+            shapes[key] = (cfg.type_vocab_size, H)
+        elif "LayerNorm" in key:
+            shapes[key] = (H,)
+        elif "intermediate.dense" in key:
+            shapes[key] = (I, H) if key.endswith("weight") else (I,)
+        elif ".output.dense.weight" in key and "attention" not in key:
+            shapes[key] = (H, I)
+        else:
+            shapes[key] = (H, H) if key.endswith("weight") else (H,)
+    return shapes
+
+
+class _Node(torch.nn.Module):
+    """A container: the dotted reference names are paths through these."""
+
+
+class TrainableRetriever(torch.nn.Module):
+    """BertForRetriever with gradients.  forward(batch) takes a re_collate batch (input_ids_q / input_mask_q / input_ids_c /
+    input_mask_c, right-padded) and returns {'q': [B, 128], 'c': [B, 128]} in fp16 with gradients."""
+
+    def __init__(self, config, device=None, dropout=0.0):
+        super().__init__()
+        cfg = config if not isinstance(config, dict) else config_from_dict(config)
+        if dropout != 0:
+            raise ValueError("TrainableRetriever trains without dropout (DESIGN.md section 3e); dropout must be 0")
+        dev = torch.device(device) if device is not None else torch.device("cuda")
+        if dev.type != "cuda":
+            raise RuntimeError("proqa_amd.TrainableRetriever runs on MI355X only; there is no CPU path")
+        if cfg.hidden_size != cfg.num_attention_heads * 64:
+            raise ValueError("the attention kernels are built for head_dim 64 (bert-base/large geometry)")
+        if getattr(cfg, "hidden_act", "gelu") != "gelu":
+            raise ValueError("only hidden_act='gelu' (erf) is implemented, as in bert-base-uncased")
+        if cfg.hidden_size > 1024 or cfg.intermediate_size > 8192:
+            raise ValueError("hidden_size <= 1024 and intermediate_size <= 8192")
+        _lib.load()
+        _lib.require_gpu()
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.config = cfg
+        self.device = dev
+        self._flat = {}
+        g = torch.Generator().manual_seed(0)
+        for key, shape in _parameter_shapes(cfg).items():      # transformers' initialisation: N(0, 0.02), LayerNorm (1, 0), biases 0
+            if key.endswith("LayerNorm.weight"):
+                value = torch.ones(shape)
+            elif key.endswith(".bias"):
+                value = torch.zeros(shape)
+            else:
+                value = 0.02 * torch.randn(shape, generator=g)
+            node = self
+            *path, leaf = key.split(".")
+            for name in path:
+                if name not in node._modules:
+                    node.add_module(name, _Node())
+                node = node._modules[name]
+            p = torch.nn.Parameter(value.to(dev))
+            node.register_parameter(leaf, p)
+            self._flat[key] = p
+
+    # -- reference-compatible surface -----------------------------------------------------
+    def state_dict_keys(self):
+        return state_dict_keys(self.config)
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        """Accepts the reference checkpoint layout: a 'module.' prefix (DataParallel) is stripped, `position_ids` buffers
+        of newer transformers are ignored."""
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+        return super().load_state_dict(sd, strict=strict, **kwargs)
+
+    def _apply(self, fn, *args, **kwargs):
+        probe = fn(torch.empty(0, dtype=torch.float32, device=self.device))
+        if probe.device.type != "cuda":
+            raise RuntimeError("proqa_amd.TrainableRetriever runs on MI355X only; there is no CPU path")
+        if probe.dtype != torch.float32:
+            raise RuntimeError("the parameters are the fp32 masters; the module casts them to fp16 itself")
+        if probe.device != self.device:
+            self.device = probe.device
+        return super()._apply(fn, *args, **kwargs)
+
+    # -- forward ----------------------------------------------------------------------------
+    def forward(self, batch):
+        return {"q": self._tower("bert_q", "proj_q", batch["input_ids_q"], batch["input_mask_q"]),
+                "c": self._tower("bert_c", "proj_c", batch["input_ids_c"], batch["input_mask_c"])}
+
+    def get_embed(self, batch, is_query_embed):
+        """The reference's get_embed (retriever.py:33-43); call it under torch.no_grad() for evaluation."""
+        tower, proj = ("bert_q", "proj_q") if is_query_embed else ("bert_c", "proj_c")
+        return {"embed": self._tower(tower, proj, batch["input_ids"], batch["input_mask"])}
+
+    def _tower(self, tower, proj, input_ids, input_mask):
+        cfg, P = self.config, self._flat
+        if not input_ids.is_cuda:
+            raise RuntimeError("TrainableRetriever expects CUDA tensors (the reference feeds move_to_cuda(batch))")
+        B, S = input_ids.shape
+        if S > cfg.max_position_embeddings or S > 512:
+            raise ValueError(f"sequence length {S} exceeds max_position_embeddings {cfg.max_position_embeddings} (or 512)")
+        if B == 0:
+            return torch.empty((0, EMBED_DIM), dtype=torch.float16, device=self.device)
+        ids = input_ids.contiguous().to(torch.int64)
+        mask = input_mask.to(torch.bool)
+        # as BertForRetriever.encode: a row without a valid token is evaluated as its first token; the mask of every row
+        # must be a prefix of ones (re_collate pads on the right); one host round trip for the check and the sizes
+        lens = mask.sum(dim=1).clamp_(min=1).to(torch.int32)
+        bad = (mask[:, 1:] & ~mask[:, :-1]).any() if S > 1 else torch.zeros((), dtype=torch.bool, device=mask.device)
+        probe = torch.stack([bad.to(torch.int64), lens.sum(dtype=torch.int64), lens.max().to(torch.int64)]).cpu()
+        if bool(probe[0]):
+            raise ValueError("input_mask must be right-padded (a prefix of True per row), as re_collate produces")
+        n_tokens, max_len = int(probe[1]), int(probe[2])
+        cu = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
+        cu[1:] = torch.cumsum(lens, 0)
+        eps, n_heads = float(cfg.layer_norm_eps), cfg.num_attention_heads
+
+        e = f"{tower}.embeddings"
+        h = _EmbedLayerNorm.apply(ids, cu, n_tokens, P[f"{e}.word_embeddings.weight"], P[f"{e}.position_embeddings.weight"],
+                                  P[f"{e}.token_type_embeddings.weight"], P[f"{e}.LayerNorm.weight"],
+                                  P[f"{e}.LayerNorm.bias"], eps)
+        for i in range(cfg.num_hidden_layers):
+            p = f"{tower}.encoder.layer.{i}"
+            qkv_w = torch.cat([P[f"{p}.attention.self.{n}.weight"] for n in ("query", "key", "value")], 0)
+            qkv_b = torch.cat([P[f"{p}.attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
+            qkv = F.linear(h, qkv_w.half())
+            ctx = _Attention.apply(qkv, qkv_b, cu, B, max_len, n_heads)
+            a = F.linear(ctx, P[f"{p}.attention.output.dense.weight"].half())
+            h1 = _BiasResidualLayerNorm.apply(a, P[f"{p}.attention.output.dense.bias"], h,
+                                              P[f"{p}.attention.output.LayerNorm.weight"],
+                                              P[f"{p}.attention.output.LayerNorm.bias"], eps)
+            f = _BiasGelu.apply(F.linear(h1, P[f"{p}.intermediate.dense.weight"].half()), P[f"{p}.intermediate.dense.bias"])
+            o = F.linear(f, P[f"{p}.output.dense.weight"].half())
+            h = _BiasResidualLayerNorm.apply(o, P[f"{p}.output.dense.bias"], h1, P[f"{p}.output.LayerNorm.weight"],
+                                             P[f"{p}.output.LayerNorm.bias"], eps)
+        cls = h.index_select(0, cu[:-1].to(torch.int64))
+        pooled = torch.tanh(F.linear(cls, P[f"{tower}.pooler.dense.weight"].half(), P[f"{tower}.pooler.dense.bias"].half()))
+        return F.linear(pooled, P[f"{proj}.weight"].half(), P[f"{proj}.bias"].half())

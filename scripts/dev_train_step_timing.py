@@ -1,0 +1,183 @@
+"""Time of one forward + backward step of proqa_amd.trainable.TrainableRetriever (dev), bert-base on seeded synthetic
+batches at the reference's --train_batch_size 640 (retrieval/train_retriever_single.sh) and at 64.
+
+    python scripts/dev_train_step_timing.py [--out DIR] [--batches 640,64] [--steps 5] [--skip-trace]
+
+Three measurements, each in a fresh child process of this script:
+  events   forward + backward + zero_grad per step between CUDA events, median of --steps after 2 warm-up steps;
+  torch    the same step by torch autograd over an fp16 restatement of the tower on the same GPU (padded layout,
+           torch.softmax attention): what a user had before this module;
+  trace    `rocprofv3 --kernel-trace` (a run of its own: no counters, no other tracing) over the module's steps: time per
+           kernel name and step, and the attention backward's fraction of the fp16 dense peak from the flops its shapes
+           imply (five products of 2 L^2 64 per (sequence, head); the kernels execute nine).
+Questions have 5-30 tokens (--max_query_length 30), paragraphs 60-220.  Prints one JSON line.
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import shutil
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+WARMUP = 2
+PEAK_TFLOPS = 2500.0      # fp16 dense, MI355X
+
+
+def make_batch(pairs, seed, dev):
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    lq = torch.randint(5, 31, (pairs,), generator=g)
+    lc = torch.randint(60, 221, (pairs,), generator=g)
+    out = {}
+    for side, lens in (("q", lq), ("c", lc)):
+        S = int(lens.max())
+        ids = torch.randint(1000, 30000, (pairs, S), generator=g)
+        mask = torch.arange(S)[None] < lens[:, None]
+        out[f"input_ids_{side}"] = (ids * mask).to(dev)
+        out[f"input_mask_{side}"] = mask.to(dev)
+    return out, lq.tolist(), lc.tolist()
+
+
+def attention_flops(lens, n_heads, n_layers):
+    return sum(5 * 2.0 * n * n * 64 for n in lens) * n_heads * n_layers
+
+
+class TorchTower:
+    """fp16 restatement on torch (padded layout): the baseline, not a product path"""
+
+    def __init__(self, model):
+        self.model = model
+
+    def tower(self, tower, proj, ids, mask):
+        import torch
+        import torch.nn.functional as F
+        P, cfg = self.model._flat, self.model.config
+        h16 = lambda k: P[k].half()
+        B, S = ids.shape
+        e = f"{tower}.embeddings"
+        x = h16(f"{e}.word_embeddings.weight")[ids] + h16(f"{e}.position_embeddings.weight")[:S][None] \
+            + h16(f"{e}.token_type_embeddings.weight")[0]
+        H = x.shape[-1]
+        h = F.layer_norm(x, (H,), h16(f"{e}.LayerNorm.weight"), h16(f"{e}.LayerNorm.bias"), cfg.layer_norm_eps)
+        add = torch.where(mask, 0.0, -65504.0).half()[:, None, None, :]
+        nh = cfg.num_attention_heads
+        for i in range(cfg.num_hidden_layers):
+            p = f"{tower}.encoder.layer.{i}"
+            lin = lambda name, t: F.linear(t, h16(f"{p}.{name}.weight"), h16(f"{p}.{name}.bias"))
+            q, k, v = (lin(f"attention.self.{n}", h).view(B, S, nh, 64).transpose(1, 2) for n in ("query", "key", "value"))
+            probs = torch.softmax(q @ k.transpose(-1, -2) * 0.125 + add, -1)
+            ctx = (probs @ v).transpose(1, 2).reshape(B, S, H)
+            h1 = F.layer_norm(lin("attention.output.dense", ctx) + h, (H,), h16(f"{p}.attention.output.LayerNorm.weight"),
+                              h16(f"{p}.attention.output.LayerNorm.bias"), cfg.layer_norm_eps)
+            f = F.gelu(lin("intermediate.dense", h1))
+            h = F.layer_norm(lin("output.dense", f) + h1, (H,), h16(f"{p}.output.LayerNorm.weight"),
+                             h16(f"{p}.output.LayerNorm.bias"), cfg.layer_norm_eps)
+        pooled = torch.tanh(F.linear(h[:, 0], h16(f"{tower}.pooler.dense.weight"), h16(f"{tower}.pooler.dense.bias")))
+        return F.linear(pooled, h16(f"{proj}.weight"), h16(f"{proj}.bias"))
+
+    def __call__(self, batch):
+        return {"q": self.tower("bert_q", "proj_q", batch["input_ids_q"], batch["input_mask_q"]),
+                "c": self.tower("bert_c", "proj_c", batch["input_ids_c"], batch["input_mask_c"])}
+
+
+def child(mode, batches, steps):
+    sys.path.insert(0, ROOT)
+    import torch
+    import torch.nn.functional as F
+    from proqa_amd.retriever import BERT_BASE
+    from proqa_amd.trainable import TrainableRetriever, inbatch_loss
+    dev = torch.device("cuda", 0)
+    model = TrainableRetriever(BERT_BASE, device=dev)
+    result = {}
+    for pairs in batches:
+        batch, lq, lc = make_batch(pairs, pairs, dev)
+        forward = TorchTower(model) if mode == "torch" else model
+        times = []
+        for step in range(WARMUP + steps):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            out = forward(batch)
+            if mode == "torch":
+                loss = F.cross_entropy((out["q"] @ out["c"].t()).float(), torch.arange(pairs, device=dev))
+            else:
+                loss = inbatch_loss(out["q"], out["c"])
+            (loss * 1024.0).backward()
+            model.zero_grad(set_to_none=True)
+            t1.record()
+            torch.cuda.synchronize()
+            times.append(t0.elapsed_time(t1))
+        result[str(pairs)] = {"step_ms_median": statistics.median(times[WARMUP:]), "step_ms_min": min(times[WARMUP:]),
+                              "loss": float(loss), "tokens": sum(lq) + sum(lc),
+                              "attention_backward_flops": attention_flops(lq, 12, 12) + attention_flops(lc, 12, 12)}
+    print("RESULT " + json.dumps(result))
+
+
+def run_child(mode, args, prefix=()):
+    cmd = list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", mode, "--batches", args.batches, "--steps", str(args.steps)]
+    out = subprocess.run(cmd, check=True, timeout=900, capture_output=True, text=True).stdout
+    return json.loads([l for l in out.splitlines() if l.startswith("RESULT ")][-1][len("RESULT "):])
+
+
+def read_trace(out_dir):
+    rows = []
+    for path in glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path, newline="") as f:
+            for r in csv.DictReader(f):
+                rows.append((r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
+    rows.sort(key=lambda r: r[1])
+    return rows
+
+
+def short(name):
+    name = name.split("(")[0]
+    for tag in ("attention_bwd_dq", "attention_bwd_dkv", "attention_fwd", "bias_residual_layernorm_bwd", "bias_residual_layernorm",
+                "embed_layernorm_bwd", "embed_layernorm", "column_kernel", "reduce_slabs", "bias_gelu_out", "inbatch_loss_grad",
+                "inbatch_eval"):
+        if tag in name:
+            return tag
+    return "gemm (library)" if ("Cijk" in name or "gemm" in name.lower()) else "torch: " + name[-60:]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--child", default=None, choices=["events", "torch", "trace"])
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--batches", default="640,64")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--skip-trace", action="store_true")
+    args = ap.parse_args()
+    batches = [int(b) for b in args.batches.split(",")]
+    if args.child:
+        return child(args.child, batches, args.steps)
+    result = {"rocm": open("/opt/rocm/.info/version").read().strip() if os.path.exists("/opt/rocm/.info/version") else "",
+              "module": run_child("events", args), "torch_autograd_fp16": run_child("torch", args)}
+    if not args.skip_trace:
+        prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+        if args.out is None:
+            import tempfile
+            args.out = tempfile.mkdtemp(prefix="train_step_timing_")
+        per_batch = {}
+        for b in batches:      # one traced run per batch size, so that the kernels of a size are the whole trace
+            d = os.path.join(args.out, str(b))
+            os.makedirs(d, exist_ok=True)
+            one = argparse.Namespace(batches=str(b), steps=args.steps)
+            info = run_child("trace", one, prefix=[prof, "--kernel-trace", "--output-format", "csv", "-d", d, "--"])[str(b)]
+            per = {}
+            for name, s, e in read_trace(d):
+                per[short(name)] = per.get(short(name), 0) + (e - s)
+            n = WARMUP + args.steps
+            table = {k: v / n / 1e3 for k, v in sorted(per.items(), key=lambda kv: -kv[1])}      # us per step (warm-up included)
+            att_us = table.get("attention_bwd_dq", 0.0) + table.get("attention_bwd_dkv", 0.0)
+            per_batch[str(b)] = {"kernel_us_per_step": dict(list(table.items())[:16]), "kernels_us_per_step_total": sum(table.values()),
+                                 "attention_backward_us_per_step": att_us,
+                                 "attention_backward_fraction_of_fp16_peak": info["attention_backward_flops"] / (att_us * 1e-6) / 1e12 / PEAK_TFLOPS if att_us else None}
+        result["trace"] = per_batch
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
