@@ -483,6 +483,79 @@ int proqa_inbatch_loss_grad_f16(const void* q, const void* c, const int32_t* tar
                                 int nq, int nc, int dim, void* dq, void* dc, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The optimizer step of retriever training: what retrieval/train_retriever.py:207-214 runs between loss.backward() and the
+ * next forward (amp's unscale and overflow check, clip_grad_norm_, transformers.AdamW.step) as three launches over all
+ * parameter tensors at once.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive).  Rules of the backward block:
+ * caller-owned workspace and state, no allocation, no host synchronisation, everything on `stream`.
+ *
+ * All tensors are contiguous fp32 in HBM, 4-byte aligned; a tensor whose p, g, m and v are all 16-byte aligned takes the
+ * 16-byte path.  One workgroup owns one fixed chunk of PROQA_ADAMW_CHUNK elements of one tensor in both passes; the chunk
+ * map depends on the sizes only and is built once (proqa_adamw_chunk_map).  The tensor table and the chunk map are DEVICE
+ * arrays: the caller refreshes the table's g / lr / weight_decay each step with an asynchronous copy on `stream` (from
+ * pinned memory it does not reuse before that copy has run), so the host never waits.
+ *
+ * One step (proqa_adamw_step), with s = the loss scale in the state:
+ *   1. partial[c] = sum over chunk c of (g / s)^2 in fp32 (unscaled before squaring), a fixed order, no atomics;
+ *   2. one workgroup adds the partials in ascending chunk order in double (256 contiguous runs, then the runs in order):
+ *      norm = sqrt(sum) is what clip_grad_norm_ returns; found_inf = norm is not finite;
+ *      clip = min(1, max_grad_norm / (norm + 1e-6)) (exactly 1 below the limit or without one);
+ *      found_inf: skipped += 1 and (dynamic scale) s *= backoff_factor, clean_steps = 0;
+ *      otherwise: step += 1, bias corrections 1 - beta^step in double, and (dynamic scale) clean_steps += 1, at
+ *      growth_interval: s *= growth_factor, clean_steps = 0 (apex amp's scaler, which the reference trains with);
+ *   3. found_inf: nothing is written.  Otherwise per element, fp32, g' = g * (clip / s):
+ *        m = beta1 m + (1 - beta1) g';  v = beta2 v + (1 - beta2) g'^2
+ *        reference (transformers.AdamW, correct_bias): p -= lr sqrt(bc2) / bc1 * m / (sqrt(v) + eps);  p -= lr wd p
+ *        torch_semantics (torch.optim.AdamW):          p *= 1 - lr wd;  p -= lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps)
+ *      A tensor with g = NULL is skipped in 1 and 3 (p, m, v untouched).  ONE step count for all tensors (both originals
+ *      count per parameter; they differ only for a parameter that had no gradient in some step).
+ * Without clipping (max_grad_norm <= 0) and without a scale (PROQA_ADAMW_SCALE_NONE) launches 1 and 2 are skipped, the
+ * state is not touched (state_dev, ws may be NULL) and the step number is the caller's host_step.
+ * Results are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------- */
+#define PROQA_ADAMW_CHUNK 16384
+#define PROQA_ADAMW_SCALE_NONE 0      /* gradients are not scaled (the state's scale is 1) */
+#define PROQA_ADAMW_SCALE_FIXED 1     /* the state's scale never changes */
+#define PROQA_ADAMW_SCALE_DYNAMIC 2
+typedef struct proqa_adamw_tensor {
+  void* p;            /* [n] parameter */
+  const void* g;      /* [n] gradient, or NULL: the tensor is skipped */
+  void* m;            /* [n] exp_avg */
+  void* v;            /* [n] exp_avg_sq */
+  int64_t n;
+  double lr;
+  double weight_decay;
+} proqa_adamw_tensor;
+typedef struct proqa_adamw_chunk {
+  int32_t tensor;     /* row of the tensor table */
+  int32_t index;      /* elements [index * PROQA_ADAMW_CHUNK, ...) of that tensor */
+} proqa_adamw_chunk;
+typedef struct proqa_adamw_hyper {
+  double beta1, beta2, eps;
+  float max_grad_norm;       /* <= 0: no clipping */
+  int32_t torch_semantics;
+  int32_t scale_mode;        /* PROQA_ADAMW_SCALE_* */
+  float backoff_factor;      /* dynamic scale: 0.5 */
+  float growth_factor;       /* dynamic scale: 2 */
+  int32_t growth_interval;   /* dynamic scale: 2000 */
+  int64_t host_step;         /* used only when launches 1 and 2 are skipped: the number of this step, >= 1 */
+} proqa_adamw_hyper;
+/* Device scalars of the optimizer, PROQA_ADAMW_STATE_BYTES of caller-owned device memory (8-byte aligned), written by
+ * proqa_adamw_state_init and by every step.  Byte offsets: 0 int64 step; 8 int64 skipped steps; 16 int64 clean steps;
+ * 24 float loss scale; 28 float norm of the last step (unscaled, before clipping); 32 int32 found_inf of the last step;
+ * 36 float gradient factor clip / scale; 40, 48 double bias corrections; 56 float clip coefficient; 60 reserved. */
+#define PROQA_ADAMW_STATE_BYTES 64
+/* chunks of the tensors of these sizes, in table order (host arrays; a size-0 tensor has none).  Returns the number of
+ * chunks, or a negative error; out = NULL only counts, otherwise out holds `capacity` entries. */
+int64_t proqa_adamw_chunk_map(const int64_t* sizes, int n_tensors, proqa_adamw_chunk* out, int64_t capacity);
+size_t proqa_adamw_workspace_bytes(int64_t n_chunks);
+/* (re)start the state: step counts and the loss scale (> 0, finite; 1 for PROQA_ADAMW_SCALE_NONE; apex starts a dynamic
+ * scale at 65536).  One tiny launch on `stream`. */
+int proqa_adamw_state_init(void* state_dev, int64_t step, float loss_scale, int64_t clean_steps, int64_t skipped_steps,
+                           void* stream);
+int proqa_adamw_step(const proqa_adamw_tensor* table_dev, int n_tensors, const proqa_adamw_chunk* chunks_dev, int64_t n_chunks,
+                     const proqa_adamw_hyper* hyper, void* state_dev, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * k-means over passage embeddings.  Replaces faiss.Clustering.train + index.search(data, 1) of
  * retrieval/group_paras.py:20-53 (IndexFlatL2, IndexFlatIP when --spherical).  The Lloyd loop
  * (sampling, initialisation, empty-cluster splitting: faiss Clustering.cpp) runs on the host

@@ -62,6 +62,29 @@ class BertWeights(ctypes.Structure):
                 ("pool_w", c_void_p), ("pool_b", c_void_p), ("proj_w", c_void_p), ("proj_b", c_void_p)]
 
 
+class AdamwTensor(ctypes.Structure):
+    """proqa_adamw_tensor"""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64),
+                ("lr", ctypes.c_double), ("weight_decay", ctypes.c_double)]
+
+
+class AdamwChunk(ctypes.Structure):
+    """proqa_adamw_chunk"""
+    _fields_ = [("tensor", ctypes.c_int32), ("index", ctypes.c_int32)]
+
+
+class AdamwHyper(ctypes.Structure):
+    """proqa_adamw_hyper"""
+    _fields_ = [("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("max_grad_norm", c_float), ("torch_semantics", ctypes.c_int32), ("scale_mode", ctypes.c_int32),
+                ("backoff_factor", c_float), ("growth_factor", c_float), ("growth_interval", ctypes.c_int32),
+                ("host_step", c_int64)]
+
+
+ADAMW_CHUNK = 16384
+ADAMW_STATE_BYTES = 64
+ADAMW_SCALE_NONE, ADAMW_SCALE_FIXED, ADAMW_SCALE_DYNAMIC = 0, 1, 2
+
 ENC_CLS_ONLY_LAST = 1
 ENC_PACKED = 2
 
@@ -161,6 +184,11 @@ SIGNATURES = {
                                              c_void_p, c_size_t, c_void_p]),
     "proqa_inbatch_loss_grad_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_void_p]),
+    "proqa_adamw_chunk_map": (c_int64, [c_void_p, c_int, c_void_p, c_int64]),
+    "proqa_adamw_workspace_bytes": (c_size_t, [c_int64]),
+    "proqa_adamw_state_init": (c_int, [c_void_p, c_int64, c_float, c_int64, c_int64, c_void_p]),
+    "proqa_adamw_step": (c_int, [c_void_p, c_int, c_void_p, c_int64, ctypes.POINTER(AdamwHyper), c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
     "proqa_kmeans_create": (c_int, [c_int, c_int64, c_int, ctypes.POINTER(c_void_p)]),
     "proqa_kmeans_free": (c_int, [c_void_p]),
     "proqa_kmeans_assign_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,

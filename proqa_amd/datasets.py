@@ -1,7 +1,8 @@
 """Inference datasets + collates of the encode path and of the retriever's dev evaluation.
 
 Mirrors /root/reference/retrieval/datasets.py: collate_tokens (:29-45), EmDataset (:257-295),
-em_collate (:298-305), ReDataset (:153-209), re_collate (:231-240).  Tokenisation is transformers' BertTokenizer, exactly
+em_collate (:298-305), ReDataset (:153-209), re_collate (:231-240), and the training loop's ReSampler (:212-229),
+ClusterDataset (:48-112) and ClusterSampler (:115-150).  Tokenisation is transformers' BertTokenizer, exactly
 as in the reference.
 
 `EmDataset` + `em_collate` are the reference's per-item shapes.  `get_embed.py` feeds the GPU through `EmTextView` +
@@ -12,10 +13,11 @@ that a worker ships three arrays per batch instead of 2 x 512 small tensors and 
 """
 import json
 import os
+import random
 
 import numpy as np
 import torch
-from torch.utils.data import Dataset
+from torch.utils.data import Dataset, Sampler
 
 
 def collate_tokens(values, pad_idx, eos_idx=None, left_pad=False, move_eos_to_beginning=False):
@@ -428,6 +430,126 @@ class ReDataset(Dataset):
             sample["Paragraph"], max_length=self.max_length - self.max_query_length, truncation=True))
         return {"input_ids_q": question_ids, "input_mask_q": torch.ones(question_ids.shape).bool(),
                 "input_ids_c": paragraph_ids, "input_mask_c": torch.ones(paragraph_ids.shape).bool()}
+
+
+class ReSampler(Sampler):
+    """Index order of one epoch over a ReDataset (retrieval/datasets.py:212-229): each of the three strided index groups is
+    shuffled with random.shuffle -- in place, as the reference does, so the dataset's group_indexs carry the order over to
+    the next sampler -- and the groups are concatenated.  Same calls to `random` in the same order: for a given
+    random.seed() the order is the reference's."""
+
+    def __init__(self, data_source):
+        sample_indice = []
+        for group in data_source.group_indexs:
+            random.shuffle(group)
+            sample_indice += group
+        self.sample_indice = sample_indice
+
+    def __len__(self):
+        return len(self.sample_indice)
+
+    def __iter__(self):
+        return iter(self.sample_indice)
+
+
+def _load_cluster_file(job):
+    """one file of a ClusterDataset folder (module level: it runs in the loading pool's processes)"""
+    path, keep_filtered = job
+    with open(path) as f:
+        data = [json.loads(line) for line in f.readlines()]
+    if keep_filtered:
+        data = [item for item in data if _filter_sample(item)]
+    return data
+
+
+def _filter_sample(item):
+    from .qa_utils import normalize_answer
+    if len(item["Paragraph"].split()) < 20:
+        return False
+    if normalize_answer(item["Answer"]) in normalize_answer(item["Question"]):
+        return False
+    return True
+
+
+class ClusterDataset(Dataset):
+    """A folder of JSON-lines files, one per paragraph cluster (retrieval/datasets.py:48-112): items as ReDataset's,
+    index_clusters[f] = the indices of file f's items.  Two deviations from the reference: the folder is read in
+    sorted(os.listdir(...)) order (the reference takes whatever order the file system returns, so its indices are not
+    reproducible from one machine to the next), and the loading pool has min(30, usable CPUs, number of files) processes,
+    not 30 (a single file is read in this process)."""
+
+    def __init__(self, tokenizer, data_folder, max_query_length, max_length, filter=False):
+        super().__init__()
+        self.tokenizer = tokenizer
+        self.filter = filter
+        self.max_query_length = max_query_length
+        self.max_length = max_length
+        print(f"Loading data splits from {data_folder}")
+        file_lists = [os.path.join(data_folder, f) for f in sorted(os.listdir(data_folder))]
+        jobs = [(path, bool(filter)) for path in file_lists]
+        try:
+            usable = len(os.sched_getaffinity(0))
+        except AttributeError:
+            usable = os.cpu_count() or 1
+        n_proc = min(30, usable, len(jobs))
+        if n_proc > 1:
+            from multiprocessing import Pool as ProcessPool
+            with ProcessPool(processes=n_proc) as pool:
+                file_datas = pool.map(_load_cluster_file, jobs)
+        else:
+            file_datas = [_load_cluster_file(job) for job in jobs]
+        self.data, self.index_clusters = [], []
+        for file_data in file_datas:
+            indice = len(self.data) + np.arange(len(file_data))
+            self.index_clusters.append(list(indice))
+            self.data.extend(file_data)
+        print(f"Total {len(self.data)} loaded")
+
+    def filter_sample(self, item):
+        return _filter_sample(item)
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, index):
+        sample = self.data[index]
+        question_ids = torch.LongTensor(self.tokenizer.encode(
+            sample["Question"], max_length=self.max_query_length, truncation=True))
+        paragraph_ids = torch.LongTensor(self.tokenizer.encode(
+            sample["Paragraph"], max_length=self.max_length - self.max_query_length, truncation=True))
+        return {"input_ids_q": question_ids, "input_mask_q": torch.ones(question_ids.shape).bool(),
+                "input_ids_c": paragraph_ids, "input_mask_c": torch.ones(paragraph_ids.shape).bool()}
+
+
+class ClusterSampler(Sampler):
+    """Index order of one epoch over a ClusterDataset (retrieval/datasets.py:115-150): inside each cluster the three
+    strided groups (adjacent items share a paragraph) are shuffled and each group's items are shuffled (random.shuffle),
+    the clusters are concatenated, and the batch-sized slices of that sequence are visited in an np.random.shuffle'd order
+    -- so a batch comes from one cluster wherever a cluster boundary does not cut it, and neighbouring batches do not
+    always come from the same cluster.  Same calls to `random` and `np.random` in the same order as the reference."""
+
+    def __init__(self, data_source, batch_size):
+        print(f"Sample with batch size {batch_size}")
+        sample_indice = []
+        num_group = 3
+        for cluster in data_source.index_clusters:
+            groups = [cluster[i::num_group] for i in range(num_group)]
+            random.shuffle(groups)
+            for g in groups:
+                random.shuffle(g)
+                sample_indice += g
+        self.sample_indice = []
+        batch_starts = np.arange(0, len(data_source), batch_size)
+        np.random.shuffle(batch_starts)
+        for batch_start in batch_starts:
+            self.sample_indice += sample_indice[batch_start:batch_start + batch_size]
+        assert len(self.sample_indice) == len(data_source)
+
+    def __len__(self):
+        return len(self.sample_indice)
+
+    def __iter__(self):
+        return iter(self.sample_indice)
 
 
 def re_collate(samples):
