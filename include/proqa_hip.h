@@ -481,6 +481,22 @@ int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const vo
  * exists one 32 x 32 tile at a time. */
 int proqa_inbatch_loss_grad_f16(const void* q, const void* c, const int32_t* target, const float* lse, const float* grad_in,
                                 int nq, int nc, int dim, void* dq, void* dc, void* stream);
+/* The weight gradient of a linear layer y = x w^T, on a kernel of our own (csrc/linear_kernels.hip) so that it never
+ * passes through fp16: fp16 operands, ONE fp32 sum over the whole token axis on v_mfma_f32_32x32x16_f16, fp32 output
+ * written or accumulated straight into the caller's buffer.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive).
+ * dw[N, K] (fp32, row-major, contiguous) = (accumulate ? dw : 0) + sum_t dy[t, n] * x[t, k]
+ * dy [T, N], x [T, K]: fp16, row-major, contiguous, 16-byte aligned (dw and ws too).  T >= 0, N % 8 == 0, K % 8 == 0.
+ * T == 0 writes zeros, or leaves dw alone when accumulate is set.  The token axis is cut into `splits` slices
+ * (proqa_linear_wgrad_plan with the device's compute-unit count); with splits > 1 the partial tiles go through ws
+ * (at least the plan's ws_bytes; contents undefined afterwards, nothing of its previous contents is read) and are added
+ * in ascending slice order, the existing dw last.  No atomics: bit-identical from run to run.  Rows of dw whose dy column
+ * holds an inf / NaN come out non-finite, every other row is untouched by it (likewise columns and x). */
+int proqa_linear_wgrad_f16(const void* dy, const void* x, int64_t T, int N, int K, float* dw, int accumulate,
+                           void* ws, size_t ws_bytes, void* stream);
+/* Pure host function, no GPU needed: how many slices of the token axis a launch on n_cus compute units uses, and the
+ * workspace it needs (0 when splits == 1, else splits * N * K * 4).  Slice boundaries are multiples of the kernel's
+ * contraction step of 32 tokens; no slice is empty. */
+int proqa_linear_wgrad_plan(int64_t T, int N, int K, int n_cus, int* splits, size_t* ws_bytes);
 
 /* ------------------------------------------------------------------------------------
  * The optimizer step of retriever training: what retrieval/train_retriever.py:207-214 runs between loss.backward() and the

@@ -184,7 +184,10 @@ SIGNATURES = {
                                              c_void_p, c_size_t, c_void_p]),
     "proqa_inbatch_loss_grad_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_void_p]),
-    "proqa_adamw_chunk_map": (c_int64, [c_void_p, c_int, c_void_p, c_int64]),
+    "proqa_linear_wgrad_f16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                                       c_void_p]),
+    "proqa_linear_wgrad_plan": (c_int, [c_int64, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_size_t)]),
+    "proqa_adamw_chunk_map":(c_int64, [c_void_p, c_int, c_void_p, c_int64]),
     "proqa_adamw_workspace_bytes": (c_size_t, [c_int64]),
     "proqa_adamw_state_init": (c_int, [c_void_p, c_int64, c_float, c_int64, c_int64, c_void_p]),
     "proqa_adamw_step": (c_int, [c_void_p, c_int, c_void_p, c_int64, ctypes.POINTER(AdamwHyper), c_void_p, c_void_p, c_size_t,

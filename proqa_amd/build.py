@@ -30,6 +30,7 @@ SOURCES = [
     "reader_kernels.hip",
     "inbatch_kernels.hip",
     "train_kernels.hip",
+    "linear_kernels.hip",
     "optim_kernels.hip",
     "kmeans_kernels.hip",
     "ivf_index.cpp",

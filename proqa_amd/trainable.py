@@ -9,20 +9,27 @@ libproqa_hip.so -- the forward operator the inference path uses and its backward
 LayerNorm, attention, bias + GELU, bias + residual + LayerNorm, and the in-batch loss.  The forward kernels save
 nothing; each backward recomputes what it needs from the forward's inputs, which autograd keeps.
 
-WHERE TORCH COMPUTES.  The dense products go through torch.nn.functional.linear on fp16 tensors, forward and backward:
-the same rocBLAS / hipBLASLt the inference path calls from csrc/encoder.cpp.  This file is the one place in proqa_amd/
-where torch computes; the products move behind the C ABI in a follow-up.  Biases of the encoder layers are NOT passed to
-linear: the fused operators add them and return their gradients.  The pooler and the projection (two [B, hidden]
-products and a tanh) are torch as a whole, biases included.
+Every linear layer, the pooler and the projection included, is `_Linear`: its weight gradient dW = dY^T X is
+proqa_linear_wgrad_f16 (csrc/linear_kernels.hip), fp16 operands summed over all tokens in fp32 in a fixed order and
+written as fp32 straight into the buffer whose row slices become the gradients of the masters.  No weight gradient
+passes through fp16; a bias gradient is the fp32 column sum of dY.
+
+WHERE TORCH COMPUTES.  The forward products (torch.nn.functional.linear, inside _Linear.forward only) and the input
+gradients dX = dY W run on fp16 tensors through the same rocBLAS / hipBLASLt the inference path calls from
+csrc/encoder.cpp; so do the pooler's tanh and the casts of the masters.  This file is the one place in proqa_amd/ where
+torch computes.  Biases of the encoder layers are NOT passed to linear: the fused operators add them and return their
+gradients.
 
 Precision: fp32 master parameters, cast to fp16 once per step and tower (apex O1 semantics; the reference trains with
---fp16); activations and their gradients fp16, every sum inside a kernel fp32, gradients of parameter vectors and embedding
-tables fp32.  Use a loss scale (a fixed one or torch.amp.GradScaler): every backward operator is linear in its incoming
-gradient and passes inf / NaN through.
+--fp16); activations and their gradients fp16, every sum inside a kernel fp32, every parameter gradient fp32 (weight
+matrices, vectors and embedding tables alike).  Use a loss scale (a fixed one or torch.amp.GradScaler): every backward
+operator is linear in its incoming gradient and passes inf / NaN through.
 
 Deviation: NO DROPOUT.  The reference trains with transformers' dropout of 0.1 on hidden states and attention
 probabilities; this module trains without, and refuses any other setting.  There is no CPU path.
 """
+import ctypes
+
 import torch
 import torch.nn.functional as F
 
@@ -173,6 +180,30 @@ def attention_backward(qkv, qkv_bias, d_ctx, cu_seqlens, batch, max_seq_len, n_h
     return d_qkv
 
 
+def linear_wgrad(dy, x, out=None, accumulate=False):
+    """dw [N, K] fp32 = (out if accumulate else 0) + dy^T x: dy [T, N], x [T, K] fp16 (proqa_linear_wgrad_f16).  The sum
+    over the T tokens is one fp32 sum in a fixed order; nothing passes through fp16.  out: a contiguous fp32 [N, K]
+    tensor to write or add into (required when accumulate is set)."""
+    lib = _lib.load()
+    dy, x = _f16(dy, "dy"), _f16(x, "x")
+    if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0]:
+        raise ValueError(f"linear_wgrad: dy {tuple(dy.shape)} and x {tuple(x.shape)} must be [T, N] and [T, K]")
+    (T, N), K = dy.shape, x.shape[1]
+    if out is None:
+        if accumulate:
+            raise ValueError("linear_wgrad: accumulate needs an `out` to add into")
+        out = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+    elif out.dtype != torch.float32 or out.shape != (N, K) or not out.is_contiguous() or out.device != dy.device:
+        raise ValueError(f"linear_wgrad: out must be a contiguous float32 [{N}, {K}] tensor on {dy.device}")
+    splits, need = ctypes.c_int(0), ctypes.c_size_t(0)
+    n_cus = torch.cuda.get_device_properties(dy.device).multi_processor_count
+    _lib.check(lib.proqa_linear_wgrad_plan(T, N, K, n_cus, ctypes.byref(splits), ctypes.byref(need)))
+    ws = _workspace(dy.device, need.value)
+    _call(lib.proqa_linear_wgrad_f16, dy.device, dy.data_ptr(), x.data_ptr(), T, N, K, out.data_ptr(), int(bool(accumulate)),
+          ws.data_ptr(), ws.numel())
+    return out
+
+
 def inbatch_loss_grad(q, c, target, lse, grad_in):
     """Gradient of mean_i (lse_i - s[i, target_i]) times the device scalar grad_in -> (dq, dc) fp16"""
     lib = _lib.load()
@@ -251,6 +282,41 @@ class _BiasResidualLayerNorm(torch.autograd.Function):
         x, b16, residual, g16 = ctx.saved_tensors
         dz, dgamma, dbeta, dbias = bias_residual_layernorm_backward(dy, x, b16, residual, g16, ctx.eps)
         return dz, dbias, dz, dgamma, dbeta, None
+
+
+class _Linear(torch.autograd.Function):
+    """y = x [w_0; w_1; ...]^T (+ bias) over the fp32 masters w_i [N_i, K]: the Q / K / V layer is three masters and one
+    product.  The forward and dx = dy w go through torch (rocBLAS / hipBLASLt); the weight gradient is linear_wgrad, one
+    call into an fp32 [sum N_i, K] buffer whose row slices are the gradients of the masters."""
+
+    @staticmethod
+    def forward(ctx, x, bias, *weights):
+        w16 = torch.empty((sum(w.shape[0] for w in weights), weights[0].shape[1]), dtype=torch.float16, device=x.device)
+        r = 0
+        for w in weights:
+            w16[r:r + w.shape[0]].copy_(w)         # the cast, straight into its row slice
+            r += w.shape[0]
+        ctx.save_for_backward(x, w16)
+        ctx.rows = [w.shape[0] for w in weights]
+        return F.linear(x, w16, bias.half() if bias is not None else None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w16 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy = dy.contiguous()
+        dx = dy @ w16 if need[0] else None
+        dbias = colsum(dy) if need[1] else None
+        dws = [None] * len(ctx.rows)
+        if any(need[2:]):
+            dw = linear_wgrad(dy, x)
+            r = 0
+            for i, n in enumerate(ctx.rows):
+                if need[2 + i]:
+                    dws[i] = dw[r:r + n]
+                r += n
+        return (dx, dbias, *dws)
 
 
 class _InBatchLoss(torch.autograd.Function):
@@ -415,18 +481,17 @@ class TrainableRetriever(torch.nn.Module):
                                   P[f"{e}.LayerNorm.bias"], eps)
         for i in range(cfg.num_hidden_layers):
             p = f"{tower}.encoder.layer.{i}"
-            qkv_w = torch.cat([P[f"{p}.attention.self.{n}.weight"] for n in ("query", "key", "value")], 0)
             qkv_b = torch.cat([P[f"{p}.attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
-            qkv = F.linear(h, qkv_w.half())
+            qkv = _Linear.apply(h, None, *(P[f"{p}.attention.self.{n}.weight"] for n in ("query", "key", "value")))
             ctx = _Attention.apply(qkv, qkv_b, cu, B, max_len, n_heads)
-            a = F.linear(ctx, P[f"{p}.attention.output.dense.weight"].half())
+            a = _Linear.apply(ctx, None, P[f"{p}.attention.output.dense.weight"])
             h1 = _BiasResidualLayerNorm.apply(a, P[f"{p}.attention.output.dense.bias"], h,
                                               P[f"{p}.attention.output.LayerNorm.weight"],
                                               P[f"{p}.attention.output.LayerNorm.bias"], eps)
-            f = _BiasGelu.apply(F.linear(h1, P[f"{p}.intermediate.dense.weight"].half()), P[f"{p}.intermediate.dense.bias"])
-            o = F.linear(f, P[f"{p}.output.dense.weight"].half())
+            f = _BiasGelu.apply(_Linear.apply(h1, None, P[f"{p}.intermediate.dense.weight"]), P[f"{p}.intermediate.dense.bias"])
+            o = _Linear.apply(f, None, P[f"{p}.output.dense.weight"])
             h = _BiasResidualLayerNorm.apply(o, P[f"{p}.output.dense.bias"], h1, P[f"{p}.output.LayerNorm.weight"],
                                              P[f"{p}.output.LayerNorm.bias"], eps)
         cls = h.index_select(0, cu[:-1].to(torch.int64))
-        pooled = torch.tanh(F.linear(cls, P[f"{tower}.pooler.dense.weight"].half(), P[f"{tower}.pooler.dense.bias"].half()))
-        return F.linear(pooled, P[f"{proj}.weight"].half(), P[f"{proj}.bias"].half())
+        pooled = torch.tanh(_Linear.apply(cls, P[f"{tower}.pooler.dense.bias"], P[f"{tower}.pooler.dense.weight"]))
+        return _Linear.apply(pooled, P[f"{proj}.bias"], P[f"{proj}.weight"])
