@@ -474,6 +474,57 @@ int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids
 int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx, const int32_t* cu_seqlens_dev,
                                  int batch, int max_seq_len, int n_heads, int64_t n_tokens, void* d_qkv, void* ws,
                                  size_t ws_bytes, void* stream);
+/* ------------------------------------------------------------------------------------
+ * Dropout of the towers in training (transformers' hidden_dropout_prob and attention_probs_dropout_prob), inside the fused
+ * operators.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive); the rules of the backward block above hold.
+ * A mask is never stored: it is a pure function of (seed, site, call, coordinates) -- Philox4x32-10 with key
+ * (seed & 0xffffffff, seed >> 32), csrc/dropout_rng.h -- and every kernel regenerates the bits it needs, the backward
+ * kernels the same bits as the forward.  An element is kept iff its 16 bits >= thr = min(65535, floor(p * 65536 + 0.5));
+ * the effective rate is thr / 65536 and the survivors are multiplied by 1 / (1 - thr / 65536) (fp32).  p in [0, 1).
+ * site in [0, 255]: 0 the embeddings, 1 + 3 * layer + {0: attention probabilities, 1: attention output, 2: FFN output};
+ * call: the caller's count of tower passes, 24 bits (it wraps).
+ *   hidden element (row, col) of a [rows, cols] matrix: counter (col >> 3, row, 0, site | call << 8),
+ *                                                       word (col & 7) >> 1, half col & 1;  rows < 2^32
+ *   probability (b, head, query i, key j):              counter (j >> 2, i >> 1, b * n_heads + head, site | call << 8),
+ *                                                       word j & 3, half i & 1
+ * ---------------------------------------------------------------------------------- */
+#define PROQA_DROPOUT_HIDDEN 0
+#define PROQA_DROPOUT_PROBS 1
+/* Pure host function, no GPU needed: keep[t] = 1 if the element is kept, else 0, for n consecutive values c0 .. c0 + n - 1
+ * of the last coordinate.  PROQA_DROPOUT_HIDDEN: a = row, b ignored, c = column.  PROQA_DROPOUT_PROBS: a = b * n_heads +
+ * head, b = query, c = key. */
+int proqa_dropout_keep_host(int kind, double p, uint64_t seed, int site, uint32_t call, int64_t a, int64_t b, int64_t c0,
+                            int64_t n, uint8_t* keep);
+/* out = x * keep * factor on [rows, cols] fp16 (the product in fp32, rounded once; a dropped element is +0).  The
+ * embeddings: transformers drops after the embedding LayerNorm.  Its backward is the same call on dy.  cols % 8 == 0. */
+int proqa_dropout_f16(const void* x, int64_t rows, int cols, double p, uint64_t seed, int site, uint32_t call, void* out,
+                      void* stream);
+/* out = LayerNorm(dropout(x + bias) + residual) * gamma + beta: transformers' order, the dense bias inside the dropout.
+ * Otherwise proqa_bias_residual_layernorm_f16. */
+int proqa_bias_residual_layernorm_dropout_f16(const void* x, const void* bias, const void* residual, const void* gamma,
+                                              const void* beta, float eps, int64_t rows, int cols, double p, uint64_t seed,
+                                              int site, uint32_t call, void* out, void* stream);
+/* its backward: dresidual [rows, cols] fp16 = dz, dx = dz * keep * factor, dbias = the fp32 column sum of dx before its
+ * rounding; dgamma, dbeta and every rule as proqa_bias_residual_layernorm_backward_f16. */
+int proqa_bias_residual_layernorm_dropout_backward_f16(const void* dy, const void* x, const void* bias, const void* residual,
+                                                       const void* gamma, float eps, int64_t rows, int cols, double p,
+                                                       uint64_t seed, int site, uint32_t call, void* dx, void* dresidual,
+                                                       float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes,
+                                                       void* stream);
+/* proqa_attention_ex_f16 on the packed layout with dropout of the probabilities: ctx = (P D)(V + b_v), D = factor where
+ * kept and 0 elsewhere.  The softmax statistics run over all keys; dropped probabilities are zero in the fp16 operand of
+ * P V and the factor enters once, with 1 / l.  The rows of P D do not sum to 1: the value bias is weighted by
+ * factor * l_kept / l (l_kept = the fp32 sum of the kept probabilities).  The key bias is still dropped. */
+int proqa_attention_dropout_f16(const void* qkv, const void* qkv_bias, const int32_t* cu_seqlens_dev, int batch,
+                                int max_seq_len, int n_heads, double p, uint64_t seed, int site, uint32_t call, void* ctx_out,
+                                void* stream);
+/* its backward, as proqa_attention_backward_f16 (same workspace): dV = (P D)^T dO, dP = D (dO (V + b_v)^T) -- the value
+ * bias does not drop out of dP here --, delta = sum_k P dP, dS = P (dP - delta).  The gradient of qkv_bias is still the
+ * column sum of d_qkv. */
+int proqa_attention_dropout_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx,
+                                         const int32_t* cu_seqlens_dev, int batch, int max_seq_len, int n_heads,
+                                         int64_t n_tokens, double p, uint64_t seed, int site, uint32_t call, void* d_qkv,
+                                         void* ws, size_t ws_bytes, void* stream);
 /* gradient of loss = mean_i (lse_i - s[i, target_i]), s = q c^T (CrossEntropyLoss(q @ c.T, target),
  * retrieval/train_retriever.py:203-205): q [nq, 128], c [nc, 128], target as proqa_inbatch_eval_f16 (NULL = the diagonal;
  * several questions may share a target; a target outside [0, nc) has no gold term), lse [nq] fp32 as that call produced

@@ -19,6 +19,9 @@ c_void_p = ctypes.c_void_p
 c_int = ctypes.c_int
 c_int64 = ctypes.c_int64
 c_float = ctypes.c_float
+c_double = ctypes.c_double
+c_uint32 = ctypes.c_uint32
+c_uint64 = ctypes.c_uint64
 c_size_t = ctypes.c_size_t
 c_char_p = ctypes.c_char_p
 
@@ -182,6 +185,19 @@ SIGNATURES = {
                                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "proqa_attention_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p,
                                              c_void_p, c_size_t, c_void_p]),
+    "proqa_dropout_keep_host": (c_int, [c_int, c_double, c_uint64, c_int, c_uint32, c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "proqa_dropout_f16": (c_int, [c_void_p, c_int64, c_int, c_double, c_uint64, c_int, c_uint32, c_void_p, c_void_p]),
+    "proqa_bias_residual_layernorm_dropout_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64,
+                                                          c_int, c_double, c_uint64, c_int, c_uint32, c_void_p, c_void_p]),
+    "proqa_bias_residual_layernorm_dropout_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                                                   c_int64, c_int, c_double, c_uint64, c_int, c_uint32,
+                                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                                   c_size_t, c_void_p]),
+    "proqa_attention_dropout_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_uint64, c_int,
+                                            c_uint32, c_void_p, c_void_p]),
+    "proqa_attention_dropout_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64,
+                                                     c_double, c_uint64, c_int, c_uint32, c_void_p, c_void_p, c_size_t,
+                                                     c_void_p]),
     "proqa_inbatch_loss_grad_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_void_p]),
     "proqa_linear_wgrad_f16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,

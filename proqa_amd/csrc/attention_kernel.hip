@@ -19,6 +19,7 @@
 
 #include "attention.h"
 #include "common.h"
+#include "dropout_rng.h"
 
 namespace proqa {
 namespace {
@@ -57,10 +58,15 @@ __device__ __forceinline__ f16x8 add_bias8(f16x8 v, const _Float16* __restrict__
 // layer at 64 x 512 x 12 heads against 106 us in this form; 108 against 91 us at 512 x 128.)
 constexpr int kLongChunk = 128;
 constexpr float kExpScale = 0.125f * 1.4426950408889634f;   // log2(e) / sqrt(head_dim)
-__global__ __launch_bounds__(256, 4) void attention_fwd(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
-                                                          const int* __restrict__ seq_lens, const int* __restrict__ cu_seqlens,
-                                                          int seq_len, int n_heads, int n_pairs, int n_qc,
-                                                          _Float16* __restrict__ ctx) {
+// DROP (training, proqa_attention_dropout_f16): the probabilities are dropped by the mask of dropout_rng.h.  The softmax
+// statistics run over ALL keys (l sums the undropped p); a dropped probability is zero in the fp16 operand of P V; the
+// survivors' factor enters once, with 1 / l.  The rows of the dropped matrix no longer sum to 1, so the value bias is
+// weighted by factor * l_kept / l, l_kept = the fp32 sum of the kept p.
+template <bool DROP>
+__device__ __forceinline__ void attention_fwd_body(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
+                                                   const int* __restrict__ seq_lens, const int* __restrict__ cu_seqlens,
+                                                   int seq_len, int n_heads, int n_pairs, int n_qc,
+                                                   _Float16* __restrict__ ctx, const DropoutParams& drop) {
   constexpr int vt_stride = kLongChunk + kVtPad;
   __shared__ __attribute__((aligned(16))) _Float16 smem[kLongChunk * kKStride + kHeadDim * vt_stride];
   _Float16* k_lds = smem;                             // [128][kKStride]
@@ -101,6 +107,7 @@ __global__ __launch_bounds__(256, 4) void attention_fwd(const _Float16* __restri
   }
   float m = -__builtin_inff();
   float l = 0.f;
+  float l_kept = 0.f;                                  // (DROP only)
   f32x16 o0 = {0}, o1 = {0};
 
   // the K / V pieces of a chunk travel through registers: all eight loads of a thread are requested back to back and waited
@@ -181,16 +188,36 @@ __global__ __launch_bounds__(256, 4) void attention_fwd(const _Float16* __restri
       const float mc = m_new * kExpScale;
       float rs = 0.f;
       f16x8 pf[2];
+      float rk = 0.f;
+      if constexpr (DROP) {
+        // registers 4g .. 4g+3 are four consecutive keys of the lane's query: one generator call
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -mc));
-        rs += p;
-        pf[r >> 3][r & 7] = (_Float16)p;
+        for (int g = 0; g < 4; ++g) {
+          const Philox4 bits = dropout_prob_call(drop, (uint32_t)pair, (uint32_t)(q >> 1), (uint32_t)((key_base + 8 * g + 4 * half) >> 2));
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = 4 * g + e;
+            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -mc));
+            const float kept = dropout_prob_keep(drop, bits, q, e) ? p : 0.f;
+            rs += p;
+            rk += kept;
+            pf[r >> 3][r & 7] = (_Float16)kept;
+          }
+        }
+        rk += __shfl_xor(rk, 32, 64);
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -mc));
+          rs += p;
+          pf[r >> 3][r & 7] = (_Float16)p;
+        }
       }
       rs += __shfl_xor(rs, 32, 64);
       if (__any(m_new != m)) {                         // the running maximum moved for some query of the wave: rescale
         const float alpha = __builtin_amdgcn_exp2f((m - m_new) * kExpScale);
         l *= alpha;
+        if constexpr (DROP) l_kept *= alpha;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           o0[r] *= alpha;
@@ -198,6 +225,7 @@ __global__ __launch_bounds__(256, 4) void attention_fwd(const _Float16* __restri
         }
       }
       l += rs;
+      if constexpr (DROP) l_kept += rk;
       m = m_new;
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
@@ -222,7 +250,8 @@ __global__ __launch_bounds__(256, 4) void attention_fwd(const _Float16* __restri
   __syncthreads();                                     // the last chunk is dead: its K rows become the output staging tiles
   if (!active) return;
   _Float16* out_lds = smem + wave * 32 * kOutStride;   // 4 x 32 x 72 fp16 = the K chunk's 18 KB
-  const float inv = 1.0f / l;
+  const float inv = DROP ? drop.factor / l : 1.0f / l;
+  const float bias_weight = drop.factor * l_kept / l;  // (DROP only) what is left of the row sum of the probabilities
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
     f16x4 a, c;
@@ -240,9 +269,34 @@ __global__ __launch_bounds__(256, 4) void attention_fwd(const _Float16* __restri
     const int row = it * 8 + (lane >> 3), piece = lane & 7;   // 8 lanes x 16 B = one 128-byte row
     const int qq = qb * 32 + row;
     f16x8 v = *(const f16x8*)(out_lds + row * kOutStride + piece * 8);
-    if (bias_v) v = v + *(const f16x8*)(bias_v + piece * 8);
+    if constexpr (DROP) {
+      const float w = __shfl(bias_weight, row, 64);    // lane `row` (half 0) owns query `row` of the block
+      if (bias_v) {
+        const f16x8 bv = *(const f16x8*)(bias_v + piece * 8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (_Float16)((float)v[i] + (float)bv[i] * w);
+      }
+    } else {
+      if (bias_v) v = v + *(const f16x8*)(bias_v + piece * 8);
+    }
     if (qq < rows_avail) *(f16x8*)(ctx + (tok0 + qq) * hidden + head * kHeadDim + piece * 8) = v;
   }
+}
+
+__global__ __launch_bounds__(256, 4) void attention_fwd(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
+                                                          const int* __restrict__ seq_lens, const int* __restrict__ cu_seqlens,
+                                                          int seq_len, int n_heads, int n_pairs, int n_qc,
+                                                          _Float16* __restrict__ ctx) {
+  attention_fwd_body<false>(qkv, qkv_bias, seq_lens, cu_seqlens, seq_len, n_heads, n_pairs, n_qc, ctx, DropoutParams{});
+}
+
+// (three workgroups per CU: the generator state does not fit the 128 registers of four)
+__global__ __launch_bounds__(256, 3) void attention_dropout_fwd(const _Float16* __restrict__ qkv,
+                                                                  const _Float16* __restrict__ qkv_bias,
+                                                                  const int* __restrict__ cu_seqlens, int seq_len, int n_heads,
+                                                                  int n_pairs, int n_qc, _Float16* __restrict__ ctx,
+                                                                  DropoutParams drop) {
+  attention_fwd_body<true>(qkv, qkv_bias, nullptr, cu_seqlens, seq_len, n_heads, n_pairs, n_qc, ctx, drop);
 }
 
 // Attention of the [CLS] query only (row 0 of every sequence): the last encoder layer feeds nothing
@@ -369,9 +423,32 @@ int launch_attention_cls(const void* qkv, const void* qkv_bias, const int32_t* s
   return PROQA_OK;
 }
 
+int launch_attention_dropout(const void* qkv, const void* qkv_bias, const int32_t* cu_seqlens_dev, int batch, int seq_len,
+                             int n_heads, const DropoutParams& drop, void* ctx_out, void* stream) {
+  if (!qkv || !ctx_out || !cu_seqlens_dev) return fail(PROQA_EINVAL, "attention_dropout: NULL argument (packed layout only)");
+  if (batch < 0 || seq_len <= 0 || n_heads <= 0) return fail(PROQA_EINVAL, "attention_dropout: bad sizes");
+  if (batch == 0) return PROQA_OK;
+  const int n_pairs = batch * n_heads, n_qc = (seq_len + kLongChunk - 1) / kLongChunk;
+  const unsigned grid = (unsigned)((n_pairs + 7) / 8 * 8) * (unsigned)n_qc;
+  hipLaunchKernelGGL(attention_dropout_fwd, dim3(grid), dim3(256), 0, as_stream(stream), (const _Float16*)qkv,
+                     (const _Float16*)qkv_bias, (const int*)cu_seqlens_dev, seq_len, n_heads, n_pairs, n_qc, (_Float16*)ctx_out,
+                     drop);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
 }  // namespace proqa
 
 using namespace proqa;
+
+extern "C" int proqa_attention_dropout_f16(const void* qkv, const void* qkv_bias, const int32_t* cu_seqlens_dev, int batch,
+                                           int max_seq_len, int n_heads, double p, uint64_t seed, int site, uint32_t call,
+                                           void* ctx_out, void* stream) {
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "attention_dropout: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
+  return launch_attention_dropout(qkv, qkv_bias, cu_seqlens_dev, batch, max_seq_len, n_heads, drop, ctx_out, stream);
+}
 
 extern "C" int proqa_attention_f16(const void* qkv, const int32_t* seq_lens_dev, int batch, int seq_len,
                                    int n_heads, void* ctx_out, void* stream) {

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "dropout_rng.h"
 
 namespace proqa {
 namespace {
@@ -112,14 +113,16 @@ __global__ __launch_bounds__(256) void embed_layernorm(const long long* __restri
   layernorm_store(x, lane, n_chunks, hidden, gamma, beta, eps, out + out_row * hidden);
 }
 
-// BertSelfOutput / BertOutput: LN(dense_out + bias + residual)
-__global__ __launch_bounds__(256) void bias_residual_layernorm(const _Float16* __restrict__ xin,
-                                                               const _Float16* __restrict__ bias,
-                                                               const _Float16* __restrict__ residual,
-                                                               const _Float16* __restrict__ gamma,
-                                                               const _Float16* __restrict__ beta, float eps,
-                                                               long long rows, int cols,
-                                                               _Float16* __restrict__ out) {
+// BertSelfOutput / BertOutput: LN(dense_out + bias + residual); DROP (training): LN(dropout(dense_out + bias) + residual),
+// transformers' order, the mask regenerated from its coordinates (dropout_rng.h)
+template <bool DROP>
+__device__ __forceinline__ void bias_residual_layernorm_body(const _Float16* __restrict__ xin,
+                                                             const _Float16* __restrict__ bias,
+                                                             const _Float16* __restrict__ residual,
+                                                             const _Float16* __restrict__ gamma,
+                                                             const _Float16* __restrict__ beta, float eps,
+                                                             long long rows, int cols, _Float16* __restrict__ out,
+                                                             const DropoutParams& drop) {
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -134,11 +137,58 @@ __global__ __launch_bounds__(256) void bias_residual_layernorm(const _Float16* _
       const f16x8 a = *(const f16x8*)(xr + chunk * 8);
       const f16x8 r = *(const f16x8*)(rr + chunk * 8);
       const f16x8 b = *(const f16x8*)(bias + chunk * 8);
+      if constexpr (DROP) {
+        const Philox4 bits = dropout_hidden_call(drop, (uint32_t)row, (uint32_t)chunk);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) x[c][i] = (float)a[i] + (float)b[i] + (float)r[i];
+        for (int i = 0; i < 8; ++i)
+          x[c][i] = (dropout_hidden_keep(drop, bits, i) ? ((float)a[i] + (float)b[i]) * drop.factor : 0.f) + (float)r[i];
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[c][i] = (float)a[i] + (float)b[i] + (float)r[i];
+      }
     }
   }
   layernorm_store(x, lane, n_chunks, cols, gamma, beta, eps, out + row * cols);
+}
+
+__global__ __launch_bounds__(256) void bias_residual_layernorm(const _Float16* __restrict__ xin,
+                                                               const _Float16* __restrict__ bias,
+                                                               const _Float16* __restrict__ residual,
+                                                               const _Float16* __restrict__ gamma,
+                                                               const _Float16* __restrict__ beta, float eps,
+                                                               long long rows, int cols,
+                                                               _Float16* __restrict__ out) {
+  bias_residual_layernorm_body<false>(xin, bias, residual, gamma, beta, eps, rows, cols, out, DropoutParams{});
+}
+
+__global__ __launch_bounds__(256) void bias_residual_layernorm_dropout(const _Float16* __restrict__ xin,
+                                                                       const _Float16* __restrict__ bias,
+                                                                       const _Float16* __restrict__ residual,
+                                                                       const _Float16* __restrict__ gamma,
+                                                                       const _Float16* __restrict__ beta, float eps,
+                                                                       long long rows, int cols,
+                                                                       _Float16* __restrict__ out, DropoutParams drop) {
+  bias_residual_layernorm_body<true>(xin, bias, residual, gamma, beta, eps, rows, cols, out, drop);
+}
+
+// out = x * keep * factor on [rows, cols] (the embeddings: transformers drops AFTER the embedding LayerNorm); its own
+// backward on dy.  A dropped element is +0.
+__global__ __launch_bounds__(256) void dropout_rows(const _Float16* __restrict__ x, long long n_chunks_total,
+                                                    int chunks_per_row, _Float16* __restrict__ out, DropoutParams drop) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < n_chunks_total; c += stride) {
+    const long long row = c / chunks_per_row;
+    const Philox4 bits = dropout_hidden_call(drop, (uint32_t)row, (uint32_t)(c - row * chunks_per_row));
+    f16x8 v = *(const f16x8*)(x + c * 8);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float t = (float)v[i] * drop.factor;
+      // the product as an fp32 value of its own: fused with the conversion (v_fma_mixlo_f16 x, f, +0) a kept -0 came out +0
+      asm volatile("" : "+v"(t));
+      v[i] = dropout_hidden_keep(drop, bits, i) ? (_Float16)t : (_Float16)0.f;
+    }
+    *(f16x8*)(out + c * 8) = v;
+  }
 }
 
 // BertIntermediate: x = gelu(x + bias), exact erf form (hidden_act = 'gelu')
@@ -402,6 +452,63 @@ int proqa_bias_residual_layernorm_f16(const void* x, const void* bias, const voi
                      (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma,
                      (const _Float16*)beta, eps, (long long)rows, cols, (_Float16*)out);
   PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int proqa_bias_residual_layernorm_dropout_f16(const void* x, const void* bias, const void* residual, const void* gamma,
+                                              const void* beta, float eps, int64_t rows, int cols, double p, uint64_t seed,
+                                              int site, uint32_t call, void* out, void* stream) {
+  if (!x || !bias || !residual || !gamma || !beta || !out)
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout: NULL argument");
+  if (rows < 0 || rows > 0xffffffffll || cols <= 0 || cols % 8 || cols > 64 * kMaxChunksPerLane * 8)
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout: cols=%d must be a multiple of 8 and <= %d, rows < 2^32", cols,
+                64 * kMaxChunksPerLane * 8);
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
+  if (rows == 0) return PROQA_OK;
+  const unsigned grid = (unsigned)ceil_div<int64_t>(rows, kRowsPerBlock);
+  hipLaunchKernelGGL(bias_residual_layernorm_dropout, dim3(grid), dim3(256), 0, as_stream(stream), (const _Float16*)x,
+                     (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma, (const _Float16*)beta, eps,
+                     (long long)rows, cols, (_Float16*)out, drop);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int proqa_dropout_f16(const void* x, int64_t rows, int cols, double p, uint64_t seed, int site, uint32_t call, void* out,
+                      void* stream) {
+  if (!x || !out) return fail(PROQA_EINVAL, "dropout: NULL argument");
+  if (rows < 0 || rows > 0xffffffffll || cols <= 0 || cols % 8)
+    return fail(PROQA_EINVAL, "dropout: cols=%d must be a multiple of 8, rows < 2^32", cols);
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "dropout: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
+  if (rows == 0) return PROQA_OK;
+  const long long n_chunks = rows * (long long)(cols / 8);
+  const unsigned grid = (unsigned)std::min<long long>(ceil_div<long long>(n_chunks, 256), (long long)device_cu_count() * 8);
+  hipLaunchKernelGGL(dropout_rows, dim3(grid), dim3(256), 0, as_stream(stream), (const _Float16*)x, n_chunks, cols / 8,
+                     (_Float16*)out, drop);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int proqa_dropout_keep_host(int kind, double p, uint64_t seed, int site, uint32_t call, int64_t a, int64_t b, int64_t c0,
+                            int64_t n, uint8_t* keep) {
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "dropout_keep_host: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
+  if ((kind != PROQA_DROPOUT_HIDDEN && kind != PROQA_DROPOUT_PROBS) || a < 0 || b < 0 || c0 < 0 || n < 0 || (n > 0 && !keep))
+    return fail(PROQA_EINVAL, "dropout_keep_host: bad argument");
+  for (int64_t t = 0; t < n; ++t) {
+    const int64_t c = c0 + t;
+    if (kind == PROQA_DROPOUT_HIDDEN) {
+      const Philox4 bits = dropout_hidden_call(drop, (uint32_t)a, (uint32_t)(c >> 3));
+      keep[t] = dropout_hidden_keep(drop, bits, (int)(c & 7));
+    } else {
+      const Philox4 bits = dropout_prob_call(drop, (uint32_t)a, (uint32_t)(b >> 1), (uint32_t)(c >> 2));
+      keep[t] = dropout_prob_keep(drop, bits, (int)(b & 1), (int)(c & 3));
+    }
+  }
   return PROQA_OK;
 }
 

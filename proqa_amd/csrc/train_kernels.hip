@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "dropout_rng.h"
 
 namespace proqa {
 namespace {
@@ -162,6 +163,70 @@ __device__ __forceinline__ void reduce_waves_to_slab(float (*red)[3][64 * kMaxCh
 
 // ---- bias + residual + LayerNorm backward ------------------------------------------------------------------------------
 // workgroup = slab of rows_per_slab rows, wave = one row at a time; partials (dgamma, dbeta, dbias) -> ws[slab][3][cols]
+// DROP: the forward was LN(dropout(x + bias) + residual).  dz (to dz_out) is the gradient of the residual; the gradient of
+// x is dx = dz * keep * factor (to dx_out), and dbias is the column sum of dx before its rounding.
+__global__ __launch_bounds__(256) void bias_residual_layernorm_dropout_bwd(
+    const _Float16* __restrict__ dy_in, const _Float16* __restrict__ xin, const _Float16* __restrict__ bias,
+    const _Float16* __restrict__ residual, const _Float16* __restrict__ gamma, float eps, long long rows, int cols,
+    long long rows_per_slab, _Float16* __restrict__ dz_out, _Float16* __restrict__ dx_out, float* __restrict__ ws,
+    DropoutParams drop) {
+  __shared__ float red[3][3][64 * kMaxChunksPerLane * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_chunks = cols >> 3;
+  float gam[kMaxChunksPerLane][8], bia[kMaxChunksPerLane][8];
+  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dbia[kMaxChunksPerLane][8];
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c) {
+    const int chunk = lane + 64 * c;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gam[c][i] = bia[c][i] = dgam[c][i] = dbet[c][i] = dbia[c][i] = 0.f;
+    if (chunk < n_chunks) {
+      load8(gamma + chunk * 8, gam[c]);
+      load8(bias + chunk * 8, bia[c]);
+    }
+  }
+  const long long row0 = (long long)blockIdx.x * rows_per_slab;
+  const long long row1 = row0 + rows_per_slab < rows ? row0 + rows_per_slab : rows;
+  for (long long row = row0 + wave; row < row1; row += 4) {
+    float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
+    Philox4 bits[kMaxChunksPerLane];                   // the row's decisions: read again for dx
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+        float a[8], r[8];
+        load8(xin + row * cols + chunk * 8, a);
+        load8(residual + row * cols + chunk * 8, r);
+        load8(dy_in + row * cols + chunk * 8, dy[c]);
+        bits[c] = dropout_hidden_call(drop, (uint32_t)row, (uint32_t)chunk);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)   // the forward's expression
+          z[c][i] = (dropout_hidden_keep(drop, bits[c], i) ? (a[i] + bia[c][i]) * drop.factor : 0.f) + r[i];
+      }
+    }
+    layernorm_backward_row(z, dy, gam, lane, n_chunks, cols, eps, dz, dgam, dbet);
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+        f16x8 o, ox;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          // a dropped element has no gradient, whatever dz is (0 * inf would be NaN)
+          const float dx = dropout_hidden_keep(drop, bits[c], i) ? dz[c][i] * drop.factor : 0.f;
+          o[i] = (_Float16)dz[c][i];
+          ox[i] = (_Float16)dx;
+          dbia[c][i] += dx;
+        }
+        *(f16x8*)(dx_out + row * cols + chunk * 8) = ox;
+        *(f16x8*)(dz_out + row * cols + chunk * 8) = o;
+      }
+    }
+  }
+  float unused[kMaxChunksPerLane][8];
+  reduce_waves_to_slab(red, dgam, dbet, dbia, lane, wave, n_chunks, cols, ws + (long long)blockIdx.x * 3 * cols, unused);
+}
+
 __global__ __launch_bounds__(256) void bias_residual_layernorm_bwd(const _Float16* __restrict__ dy_in,
                                                                    const _Float16* __restrict__ xin,
                                                                    const _Float16* __restrict__ bias,
@@ -455,11 +520,15 @@ __device__ __forceinline__ void store_tile(const f32x16& o0, const f32x16& o1, f
   }
 }
 
-__global__ __launch_bounds__(256, 2) void attention_bwd_dq(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
-                                                           const _Float16* __restrict__ dctx, const int* __restrict__ cu_seqlens,
-                                                           int max_seq_len, int n_heads, int n_qc, long long n_tokens,
-                                                           _Float16* __restrict__ dqkv, float* __restrict__ ws_lse,
-                                                           float* __restrict__ ws_delta) {
+// DROP (the backward of proqa_attention_dropout_f16): with D = factor where a probability was kept and 0 elsewhere, the
+// forward was ctx = (P D)(V + b_v), so dP = D (dO (V + b_v)^T) -- the value bias does NOT drop out: the rows of P D do not
+// sum to 1 -- and delta = sum_k P dP, dS = P (dP - delta) as before; dV = (P D)^T dO.  dO b_v is one scalar per query.
+template <bool DROP>
+__device__ __forceinline__ void attention_bwd_dq_body(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
+                                                      const _Float16* __restrict__ dctx, const int* __restrict__ cu_seqlens,
+                                                      int max_seq_len, int n_heads, int n_qc, long long n_tokens,
+                                                      _Float16* __restrict__ dqkv, float* __restrict__ ws_lse,
+                                                      float* __restrict__ ws_delta, const DropoutParams& drop) {
   constexpr int t_stride = kChunk + kTPad;
   __shared__ __attribute__((aligned(16))) _Float16 smem[2 * kChunk * kRowStride + kHeadDim * t_stride];
   _Float16* k_lds = smem;                              // [128][72]
@@ -493,6 +562,28 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq(const _Float16* __res
       dof[j] = *(const f16x8*)(dctx + (tok0 + q) * hidden + head * kHeadDim + (2 * j + half) * 8);
     }
   }
+  float dob = 0.f;                                     // (DROP only) dO_q . b_v
+  if constexpr (DROP) {
+    if (qkv_bias) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f16x8 bv = *(const f16x8*)(qkv_bias + 2 * hidden + head * kHeadDim + (2 * j + half) * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dob = __builtin_fmaf((float)dof[j][e], (float)bv[e], dob);
+      }
+      dob += __shfl_xor(dob, 32, 64);
+    }
+  }
+  // DROP: dP^T of key tile kt <- D (dP^T + dO b_v); registers 4g .. 4g+3 are four consecutive keys: one generator call
+  auto drop_dp = [&](int kc, int kt, f32x16& dp) {
+    const int key_base = (kc * 4 + kt) * 32;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const Philox4 bits = dropout_prob_call(drop, (uint32_t)pair, (uint32_t)(q >> 1), (uint32_t)((key_base + 8 * g + 4 * half) >> 2));
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dp[4 * g + e] = dropout_prob_keep(drop, bits, q, e) ? (dp[4 * g + e] + dob) * drop.factor : 0.f;
+    }
+  };
 
   auto stage = [&](int kc) {
     constexpr int kIters = kChunk * 8 / 256;
@@ -547,6 +638,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq(const _Float16* __res
     for (int kt = 0; kt < tiles_here; ++kt) {
       f32x16 st = {0}, dp = {0};
       products(kc, kt, st, dp);
+      if constexpr (DROP) drop_dp(kc, kt, dp);
       float mt = st[0];
 #pragma unroll
       for (int r = 1; r < 16; ++r) mt = __builtin_fmaxf(mt, st[r]);
@@ -588,6 +680,7 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq(const _Float16* __res
     for (int kt = 0; kt < tiles_here; ++kt) {
       f32x16 st = {0}, dp = {0};
       products(kc, kt, st, dp);
+      if constexpr (DROP) drop_dp(kc, kt, dp);
       f16x8 dsf[2];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -606,6 +699,171 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dq(const _Float16* __res
   if (!active) return;
   store_tile(o0, o1, 0.125f, smem + wave * 32 * kRowStride, lane, dqkv + tok0 * row_stride + head * kHeadDim, row_stride,
              qb * 32, len);
+}
+
+__global__ __launch_bounds__(256, 2) void attention_bwd_dq(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
+                                                           const _Float16* __restrict__ dctx, const int* __restrict__ cu_seqlens,
+                                                           int max_seq_len, int n_heads, int n_qc, long long n_tokens,
+                                                           _Float16* __restrict__ dqkv, float* __restrict__ ws_lse,
+                                                           float* __restrict__ ws_delta) {
+  attention_bwd_dq_body<false>(qkv, qkv_bias, dctx, cu_seqlens, max_seq_len, n_heads, n_qc, n_tokens, dqkv, ws_lse, ws_delta,
+                               DropoutParams{});
+}
+
+__global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dq(const _Float16* __restrict__ qkv,
+                                                                   const _Float16* __restrict__ qkv_bias,
+                                                                   const _Float16* __restrict__ dctx,
+                                                                   const int* __restrict__ cu_seqlens, int max_seq_len,
+                                                                   int n_heads, int n_qc, long long n_tokens,
+                                                                   _Float16* __restrict__ dqkv, float* __restrict__ ws_lse,
+                                                                   float* __restrict__ ws_delta, DropoutParams drop) {
+  attention_bwd_dq_body<true>(qkv, qkv_bias, dctx, cu_seqlens, max_seq_len, n_heads, n_qc, n_tokens, dqkv, ws_lse, ws_delta, drop);
+}
+
+// attention_bwd_dkv with dropout (a kernel of its own: as a template instance the existing kernel's register allocation moved)
+__global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dkv(const _Float16* __restrict__ qkv,
+                                                                    const _Float16* __restrict__ qkv_bias,
+                                                                    const _Float16* __restrict__ dctx,
+                                                                    const int* __restrict__ cu_seqlens, int max_seq_len,
+                                                                    int n_heads, int n_kc, long long n_tokens,
+                                                                    _Float16* __restrict__ dqkv, const float* __restrict__ ws_lse,
+                                                                    const float* __restrict__ ws_delta, DropoutParams drop) {
+  constexpr int t_stride = kQChunk + kTPad;
+  __shared__ __attribute__((aligned(16))) _Float16 smem[2 * kQChunk * kRowStride + 2 * kHeadDim * t_stride];
+  __shared__ float lse_lds[kQChunk], delta_lds[kQChunk];
+  __shared__ float dob_lds[kQChunk];                   // dO_q . b_v of the staged queries
+  _Float16* q_lds = smem;                                                   // [64][72]  Q + b_q
+  _Float16* do_lds = smem + kQChunk * kRowStride;                           // [64][72]  d_ctx
+  _Float16* qt_lds = smem + 2 * kQChunk * kRowStride;                       // [64][68]  (Q + b_q)^T
+  _Float16* dot_lds = smem + 2 * kQChunk * kRowStride + kHeadDim * t_stride; // [64][68]  d_ctx^T
+  const int pair = blockIdx.x / n_kc, kc = blockIdx.x - pair * n_kc;
+  const int b = pair / n_heads, head = pair - b * n_heads;
+  const int hidden = n_heads * kHeadDim;
+  const long long row_stride = 3ll * hidden;
+  const long long tok0 = cu_seqlens[b];
+  int len = cu_seqlens[b + 1] - cu_seqlens[b];
+  len = len < 1 ? 1 : (len > max_seq_len ? max_seq_len : len);
+  if (tok0 < 0 || tok0 + len > n_tokens) return;
+  if (kc * kChunk >= len) return;                      // (the whole workgroup: no barrier has been met)
+  const _Float16* base = qkv + tok0 * row_stride + head * kHeadDim;
+  const _Float16* dbase = dctx + tok0 * hidden + head * kHeadDim;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, half = lane >> 5;
+  const int kb = kc * 4 + wave;
+  const bool active = kb * 32 < len;                   // wave-uniform
+  const int key = kb * 32 + li;
+  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+  f16x8 kf[4], vf[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    kf[j] = vf[j] = zero8;
+    if (key < len) {
+      const _Float16* src = base + key * row_stride + (2 * j + half) * 8;
+      kf[j] = *(const f16x8*)(src + hidden);           // (no key bias: the forward drops it)
+      vf[j] = *(const f16x8*)(src + 2 * hidden);
+    }
+  }
+  f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
+  const int n_qchunks = (len + kQChunk - 1) / kQChunk;
+  for (int qc = 0; qc < n_qchunks; ++qc) {
+    if (qc) __syncthreads();                           // every wave is done with the previous chunk
+    {
+      constexpr int kIters = kQChunk * 8 / 256;
+      f16x8 qreg[kIters], dreg[kIters];
+#pragma unroll
+      for (int it = 0; it < kIters; ++it) {
+        const int i = tid + it * 256;
+        const int row = qc * kQChunk + (i >> 3), c = i & 7;
+        qreg[it] = dreg[it] = zero8;
+        if (row < len) {
+          qreg[it] = *(const f16x8*)(base + row * row_stride + c * 8);
+          if (qkv_bias) qreg[it] = qreg[it] + *(const f16x8*)(qkv_bias + head * kHeadDim + c * 8);
+          dreg[it] = *(const f16x8*)(dbase + (long long)row * hidden + c * 8);
+        }
+      }
+      {
+        // the eight pieces of a row sit in eight consecutive lanes
+#pragma unroll
+        for (int it = 0; it < kIters; ++it) {
+          const int i = tid + it * 256;
+          float part = 0.f;
+          if (qkv_bias) {
+            const f16x8 bv = *(const f16x8*)(qkv_bias + 2 * hidden + head * kHeadDim + (i & 7) * 8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) part = __builtin_fmaf((float)dreg[it][e], (float)bv[e], part);
+          }
+          part += __shfl_xor(part, 1, 64);
+          part += __shfl_xor(part, 2, 64);
+          part += __shfl_xor(part, 4, 64);
+          if ((i & 7) == 0) dob_lds[i >> 3] = part;
+        }
+      }
+#pragma unroll
+      for (int it = 0; it < kIters; ++it) {
+        const int i = tid + it * 256;
+        const int r = i >> 3, c = i & 7;
+        *(f16x8*)(q_lds + r * kRowStride + c * 8) = qreg[it];
+        *(f16x8*)(do_lds + r * kRowStride + c * 8) = dreg[it];
+        stage_transposed(qreg[it], r, c, qt_lds, t_stride);
+        stage_transposed(dreg[it], r, c, dot_lds, t_stride);
+      }
+      if (tid < kQChunk) {
+        const int row = qc * kQChunk + tid;
+        // a query row that does not exist has P = exp2(s - inf) = 0
+        lse_lds[tid] = row < len ? ws_lse[(long long)head * n_tokens + tok0 + row] : __builtin_inff();
+        delta_lds[tid] = row < len ? ws_delta[(long long)head * n_tokens + tok0 + row] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (!active) continue;
+    const int rows_here = len - qc * kQChunk < kQChunk ? len - qc * kQChunk : kQChunk;
+    const int tiles_here = (rows_here + 31) >> 5;
+    for (int qt = 0; qt < tiles_here; ++qt) {
+      // S = Q K^T and dP = dO V^T of query tile qt: lane = key, registers = queries (r & 3) + 8 (r >> 2) + 4 half
+      f32x16 st = {0}, dp = {0};
+      const _Float16* qrow = q_lds + (qt * 32 + li) * kRowStride + half * 8;
+      const _Float16* drow = do_lds + (qt * 32 + li) * kRowStride + half * 8;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(qrow + j * 16), kf[j], st, 0, 0, 0);
+        dp = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(drow + j * 16), vf[j], dp, 0, 0, 0);
+      }
+      f16x8 pf[2], dsf[2];
+      {
+        // registers 4g .. 4g+3 are four consecutive queries of the lane's key: two generator calls (a call covers queries
+        // 2n, 2n + 1).  pf holds the kept probabilities; the factor enters dV once, at the store
+#pragma unroll
+        for (int g2 = 0; g2 < 8; ++g2) {
+          const int qi0 = qt * 32 + 8 * (g2 >> 1) + 4 * half + 2 * (g2 & 1);
+          const Philox4 bits = dropout_prob_call(drop, (uint32_t)pair, (uint32_t)((qc * kQChunk + qi0) >> 1), (uint32_t)(key >> 2));
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            const int r = 2 * g2 + e, qi = qi0 + e;
+            float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -lse_lds[qi]));
+            p = key < len ? p : 0.f;
+            const bool kept = dropout_prob_keep(drop, bits, e, key);
+            const float dpd = kept ? (dp[r] + dob_lds[qi]) * drop.factor : 0.f;
+            pf[r >> 3][r & 7] = (_Float16)(kept ? p : 0.f);
+            dsf[r >> 3][r & 7] = (_Float16)(p * (dpd - delta_lds[qi]));
+          }
+        }
+      }
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) {
+        const int q0 = qt * 32 + 16 * jj + 4 * half;
+        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(dot_lds, t_stride, li, q0), pf[jj], dv0, 0, 0, 0);
+        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(dot_lds, t_stride, 32 + li, q0), pf[jj], dv1, 0, 0, 0);
+        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(qt_lds, t_stride, li, q0), dsf[jj], dk0, 0, 0, 0);
+        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(qt_lds, t_stride, 32 + li, q0), dsf[jj], dk1, 0, 0, 0);
+      }
+    }
+  }
+  __syncthreads();                                     // the last chunk is dead: Q and d_ctx rows become the output staging tiles
+  if (!active) return;
+  _Float16* tile = smem + wave * 32 * kRowStride;      // 4 x 32 x 72 = the two row-major arrays
+  _Float16* out = dqkv + tok0 * row_stride + head * kHeadDim;
+  store_tile(dk0, dk1, 0.125f, tile, lane, out + hidden, row_stride, kb * 32, len);
+  store_tile(dv0, dv1, drop.factor, tile, lane, out + 2 * hidden, row_stride, kb * 32, len);
 }
 
 __global__ __launch_bounds__(256, 2) void attention_bwd_dkv(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
@@ -913,6 +1171,35 @@ int proqa_bias_residual_layernorm_backward_f16(const void* dy, const void* x, co
   return launch_reduce((const float*)ws, n_slabs, 3, cols, dgamma, dbeta, dbias, nullptr, 0, st);
 }
 
+int proqa_bias_residual_layernorm_dropout_backward_f16(const void* dy, const void* x, const void* bias, const void* residual,
+                                                       const void* gamma, float eps, int64_t rows, int cols, double p,
+                                                       uint64_t seed, int site, uint32_t call, void* dx, void* dresidual,
+                                                       float* dgamma, float* dbeta, float* dbias, void* ws, size_t ws_bytes,
+                                                       void* stream) {
+  if (!dy || !x || !bias || !residual || !gamma || !dx || !dresidual || !dgamma || !dbeta || !dbias || !ws)
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: NULL argument");
+  if (rows < 0 || rows > 0xffffffffll || cols <= 0 || cols % 8 || cols > 64 * kMaxChunksPerLane * 8)
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: cols=%d must be a multiple of 8 and <= %d, rows < 2^32",
+                cols, 64 * kMaxChunksPerLane * 8);
+  if (ws_bytes < proqa_backward_workspace_bytes(cols))
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: workspace too small");
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
+  hipStream_t st = as_stream(stream);
+  if (rows == 0) {
+    for (float* q : {dgamma, dbeta, dbias}) PROQA_HIP(hipMemsetAsync(q, 0, (size_t)cols * sizeof(float), st));
+    return PROQA_OK;
+  }
+  int64_t per;
+  const int n_slabs = slabs_for(rows, 16, &per);
+  hipLaunchKernelGGL(bias_residual_layernorm_dropout_bwd, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)dy,
+                     (const _Float16*)x, (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma, eps,
+                     (long long)rows, cols, (long long)per, (_Float16*)dresidual, (_Float16*)dx, (float*)ws, drop);
+  PROQA_LAUNCH_CHECK();
+  return launch_reduce((const float*)ws, n_slabs, 3, cols, dgamma, dbeta, dbias, nullptr, 0, st);
+}
+
 int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids_dev, const int32_t* cu_seqlens_dev,
                                               int batch, int seq_len, int hidden, int64_t n_tokens, const void* word_emb,
                                               int64_t vocab, const void* pos_emb, const void* type_emb, const void* ln_gamma,
@@ -958,6 +1245,35 @@ int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const vo
   hipLaunchKernelGGL(attention_bwd_dkv, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
                      (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
                      (_Float16*)d_qkv, (const float*)ws_lse, (const float*)ws_delta);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int proqa_attention_dropout_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx,
+                                         const int32_t* cu_seqlens_dev, int batch, int max_seq_len, int n_heads,
+                                         int64_t n_tokens, double p, uint64_t seed, int site, uint32_t call, void* d_qkv,
+                                         void* ws, size_t ws_bytes, void* stream) {
+  if (!qkv || !d_ctx || !cu_seqlens_dev || !d_qkv || !ws) return fail(PROQA_EINVAL, "attention_dropout_backward: NULL argument");
+  if (batch < 0 || max_seq_len <= 0 || max_seq_len > 512 || n_heads <= 0 || n_tokens < 0)
+    return fail(PROQA_EINVAL, "attention_dropout_backward: bad sizes (max_seq_len <= 512)");
+  if (ws_bytes < proqa_attention_backward_workspace_bytes(n_tokens, n_heads))
+    return fail(PROQA_EINVAL, "attention_dropout_backward: workspace too small");
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "attention_dropout_backward: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
+  if (batch == 0 || n_tokens == 0) return PROQA_OK;
+  hipStream_t st = as_stream(stream);
+  const int n_c = (max_seq_len + kChunk - 1) / kChunk;
+  const unsigned grid = (unsigned)batch * (unsigned)n_heads * (unsigned)n_c;
+  float* ws_lse = (float*)ws;
+  float* ws_delta = ws_lse + n_tokens * n_heads;
+  hipLaunchKernelGGL(attention_dropout_bwd_dq, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                     (_Float16*)d_qkv, ws_lse, ws_delta, drop);
+  PROQA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(attention_dropout_bwd_dkv, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                     (_Float16*)d_qkv, (const float*)ws_lse, (const float*)ws_delta, drop);
   PROQA_LAUNCH_CHECK();
   return PROQA_OK;
 }

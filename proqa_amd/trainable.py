@@ -25,8 +25,12 @@ Precision: fp32 master parameters, cast to fp16 once per step and tower (apex O1
 matrices, vectors and embedding tables alike).  Use a loss scale (a fixed one or torch.amp.GradScaler): every backward
 operator is linear in its incoming gradient and passes inf / NaN through.
 
-Deviation: NO DROPOUT.  The reference trains with transformers' dropout of 0.1 on hidden states and attention
-probabilities; this module trains without, and refuses any other setting.  There is no CPU path.
+Dropout: transformers' two rates, `hidden_dropout_prob` (embeddings, attention output, FFN output) and
+`attention_probs_dropout_prob`, are constructor arguments (default 0: existing callers pass configs that carry 0.1 and
+train without).  In train() mode with a rate above 0 the masks live INSIDE the fused operators: each is a pure function of
+(seed, site, call, coordinates) (csrc/dropout_rng.h), generated in the forward kernel and again in the backward kernels; no
+mask and no [B, heads, S, S] tensor reaches memory.  eval(), and a rate of 0, run exactly the kernels of the
+dropout-free path.  There is no CPU path.
 """
 import ctypes
 
@@ -180,6 +184,91 @@ def attention_backward(qkv, qkv_bias, d_ctx, cu_seqlens, batch, max_seq_len, n_h
     return d_qkv
 
 
+# ---- the operators with dropout.  `drop` = (p, seed, site, call) as Python numbers; p == 0 is the dropout-free operator itself.
+
+def _drop_args(drop):
+    p, seed, site, call = drop
+    return float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), int(call) & 0xFFFFFF
+
+
+def dropout(x, drop):
+    """x [rows, cols] fp16 -> x * keep / (1 - p_eff) (proqa_dropout_f16); its backward is the same call on dy"""
+    lib = _lib.load()
+    x = _f16(x, "x")
+    if drop[0] == 0:
+        return x.clone()
+    rows, cols = x.shape
+    out = torch.empty_like(x)
+    p, seed, site, call = _drop_args(drop)
+    _call(lib.proqa_dropout_f16, x.device, x.data_ptr(), rows, cols, p, seed, site, call, out.data_ptr())
+    return out
+
+
+def bias_residual_layernorm_dropout(x, bias, residual, gamma, beta, eps, drop):
+    """LayerNorm(dropout(x + bias) + residual)"""
+    if drop[0] == 0:
+        return bias_residual_layernorm(x, bias, residual, gamma, beta, eps)
+    lib = _lib.load()
+    x, residual = _f16(x, "x"), _f16(residual, "residual")
+    rows, cols = x.shape
+    out = torch.empty_like(x)
+    p, seed, site, call = _drop_args(drop)
+    _call(lib.proqa_bias_residual_layernorm_dropout_f16, x.device, x.data_ptr(), _f16(bias, "bias").data_ptr(),
+          residual.data_ptr(), _f16(gamma, "gamma").data_ptr(), _f16(beta, "beta").data_ptr(), float(eps), rows, cols,
+          p, seed, site, call, out.data_ptr())
+    return out
+
+
+def bias_residual_layernorm_dropout_backward(dy, x, bias, residual, gamma, eps, drop):
+    """-> (dx fp16, dresidual fp16 [rows, cols], dgamma, dbeta, dbias fp32 [cols])"""
+    if drop[0] == 0:
+        dz, dgamma, dbeta, dbias = bias_residual_layernorm_backward(dy, x, bias, residual, gamma, eps)
+        return dz, dz, dgamma, dbeta, dbias
+    lib = _lib.load()
+    dy, x, residual = _f16(dy, "dy"), _f16(x, "x"), _f16(residual, "residual")
+    bias, gamma = _f16(bias, "bias"), _f16(gamma, "gamma")
+    rows, cols = x.shape
+    dx, dres = torch.empty_like(x), torch.empty_like(x)
+    dgamma, dbeta, dbias = (torch.empty(cols, dtype=torch.float32, device=x.device) for _ in range(3))
+    ws = _workspace(x.device, lib.proqa_backward_workspace_bytes(cols))
+    p, seed, site, call = _drop_args(drop)
+    _call(lib.proqa_bias_residual_layernorm_dropout_backward_f16, x.device, dy.data_ptr(), x.data_ptr(), bias.data_ptr(),
+          residual.data_ptr(), gamma.data_ptr(), float(eps), rows, cols, p, seed, site, call, dx.data_ptr(), dres.data_ptr(),
+          dgamma.data_ptr(), dbeta.data_ptr(), dbias.data_ptr(), ws.data_ptr(), ws.numel())
+    return dx, dres, dgamma, dbeta, dbias
+
+
+def attention_dropout(qkv, qkv_bias, cu_seqlens, batch, max_seq_len, n_heads, drop):
+    """attention() with the probabilities dropped (proqa_attention_dropout_f16)"""
+    if drop[0] == 0:
+        return attention(qkv, qkv_bias, cu_seqlens, batch, max_seq_len, n_heads)
+    lib = _lib.load()
+    qkv = _f16(qkv, "qkv")
+    out = torch.empty((qkv.shape[0], n_heads * 64), dtype=torch.float16, device=qkv.device)
+    p, seed, site, call = _drop_args(drop)
+    _call(lib.proqa_attention_dropout_f16, qkv.device, qkv.data_ptr(), _f16(qkv_bias, "qkv_bias").data_ptr() if qkv_bias is not None
+          else None, cu_seqlens.data_ptr(), batch, max_seq_len, n_heads, p, seed, site, call, out.data_ptr())
+    return out
+
+
+def attention_dropout_backward(qkv, qkv_bias, d_ctx, cu_seqlens, batch, max_seq_len, n_heads, drop):
+    """-> d_qkv [T, 3*hidden] fp16; the gradient of qkv_bias is colsum(d_qkv)"""
+    if drop[0] == 0:
+        return attention_backward(qkv, qkv_bias, d_ctx, cu_seqlens, batch, max_seq_len, n_heads)
+    lib = _lib.load()
+    qkv, d_ctx = _f16(qkv, "qkv"), _f16(d_ctx, "d_ctx")
+    n_tokens = qkv.shape[0]
+    if qkv.shape[1] != 3 * n_heads * 64 or d_ctx.shape != (n_tokens, n_heads * 64):
+        raise ValueError(f"attention_dropout_backward: qkv {tuple(qkv.shape)} / d_ctx {tuple(d_ctx.shape)} do not fit {n_heads} heads of 64")
+    d_qkv = torch.empty_like(qkv)
+    ws = _workspace(qkv.device, lib.proqa_attention_backward_workspace_bytes(n_tokens, n_heads))
+    p, seed, site, call = _drop_args(drop)
+    _call(lib.proqa_attention_dropout_backward_f16, qkv.device, qkv.data_ptr(), _f16(qkv_bias, "qkv_bias").data_ptr()
+          if qkv_bias is not None else None, d_ctx.data_ptr(), cu_seqlens.data_ptr(), batch, max_seq_len, n_heads, n_tokens,
+          p, seed, site, call, d_qkv.data_ptr(), ws.data_ptr(), ws.numel())
+    return d_qkv
+
+
 def linear_wgrad(dy, x, out=None, accumulate=False):
     """dw [N, K] fp32 = (out if accumulate else 0) + dy^T x: dy [T, N], x [T, K] fp16 (proqa_linear_wgrad_f16).  The sum
     over the T tokens is one fp32 sum in a fixed order; nothing passes through fp16.  out: a contiguous fp32 [N, K]
@@ -238,20 +327,38 @@ class _EmbedLayerNorm(torch.autograd.Function):
         return None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None
 
 
+class _Dropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, drop):
+        ctx.drop = drop
+        return dropout(x, drop)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        return dropout(dy, ctx.drop), None
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, qkv_bias, cu_seqlens, batch, max_seq_len, n_heads):
+    def forward(ctx, qkv, qkv_bias, cu_seqlens, batch, max_seq_len, n_heads, drop=None):
         b16 = qkv_bias.half()
         ctx.save_for_backward(qkv, b16, cu_seqlens)
         ctx.dims = (batch, max_seq_len, n_heads)
-        return attention(qkv, b16, cu_seqlens, batch, max_seq_len, n_heads)
+        ctx.drop = drop
+        if drop is None:
+            return attention(qkv, b16, cu_seqlens, batch, max_seq_len, n_heads)
+        return attention_dropout(qkv, b16, cu_seqlens, batch, max_seq_len, n_heads, drop)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_ctx):
         qkv, b16, cu = ctx.saved_tensors
-        d_qkv = attention_backward(qkv, b16, d_ctx, cu, *ctx.dims)
-        return d_qkv, colsum(d_qkv), None, None, None, None
+        if ctx.drop is None:
+            d_qkv = attention_backward(qkv, b16, d_ctx, cu, *ctx.dims)
+        else:
+            d_qkv = attention_dropout_backward(qkv, b16, d_ctx, cu, *ctx.dims, ctx.drop)
+        return d_qkv, colsum(d_qkv), None, None, None, None, None
 
 
 class _BiasGelu(torch.autograd.Function):
@@ -270,18 +377,23 @@ class _BiasGelu(torch.autograd.Function):
 
 class _BiasResidualLayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, bias, residual, gamma, beta, eps):
+    def forward(ctx, x, bias, residual, gamma, beta, eps, drop=None):
         b16, g16 = bias.half(), gamma.half()
         ctx.save_for_backward(x, b16, residual, g16)
-        ctx.eps = eps
-        return bias_residual_layernorm(x, b16, residual, g16, beta.half(), eps)
+        ctx.eps, ctx.drop = eps, drop
+        if drop is None:
+            return bias_residual_layernorm(x, b16, residual, g16, beta.half(), eps)
+        return bias_residual_layernorm_dropout(x, b16, residual, g16, beta.half(), eps, drop)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         x, b16, residual, g16 = ctx.saved_tensors
-        dz, dgamma, dbeta, dbias = bias_residual_layernorm_backward(dy, x, b16, residual, g16, ctx.eps)
-        return dz, dbias, dz, dgamma, dbeta, None
+        if ctx.drop is None:
+            dz, dgamma, dbeta, dbias = bias_residual_layernorm_backward(dy, x, b16, residual, g16, ctx.eps)
+            return dz, dbias, dz, dgamma, dbeta, None, None
+        dx, dres, dgamma, dbeta, dbias = bias_residual_layernorm_dropout_backward(dy, x, b16, residual, g16, ctx.eps, ctx.drop)
+        return dx, dbias, dres, dgamma, dbeta, None, None
 
 
 class _Linear(torch.autograd.Function):
@@ -382,11 +494,16 @@ class TrainableRetriever(torch.nn.Module):
     """BertForRetriever with gradients.  forward(batch) takes a re_collate batch (input_ids_q / input_mask_q / input_ids_c /
     input_mask_c, right-padded) and returns {'q': [B, 128], 'c': [B, 128]} in fp16 with gradients."""
 
-    def __init__(self, config, device=None, dropout=0.0):
+    def __init__(self, config, device=None, dropout=0.0, *, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
+                 dropout_seed=None):
         super().__init__()
         cfg = config if not isinstance(config, dict) else config_from_dict(config)
         if dropout != 0:
-            raise ValueError("TrainableRetriever trains without dropout (DESIGN.md section 3e); dropout must be 0")
+            raise ValueError("TrainableRetriever has no single dropout rate; dropout must be 0: pass BERT's two rates as "
+                             "hidden_dropout_prob= and attention_probs_dropout_prob= (DESIGN.md section 3e)")
+        for name, rate in (("hidden_dropout_prob", hidden_dropout_prob), ("attention_probs_dropout_prob", attention_probs_dropout_prob)):
+            if not 0.0 <= float(rate) <= 0.9:
+                raise ValueError(f"{name}={rate!r}: a dropout rate must be in [0, 0.9]")
         dev = torch.device(device) if device is not None else torch.device("cuda")
         if dev.type != "cuda":
             raise RuntimeError("proqa_amd.TrainableRetriever runs on MI355X only; there is no CPU path")
@@ -402,6 +519,11 @@ class TrainableRetriever(torch.nn.Module):
             dev = torch.device("cuda", torch.cuda.current_device())
         self.config = cfg
         self.device = dev
+        self.hidden_dropout_prob = float(hidden_dropout_prob)
+        self.attention_probs_dropout_prob = float(attention_probs_dropout_prob)
+        # the masks' (seed, call): plain Python numbers, not part of state_dict() (which keeps the reference's keys)
+        self._dropout_seed = int(torch.initial_seed() if dropout_seed is None else dropout_seed) & 0xFFFFFFFFFFFFFFFF
+        self._dropout_call = 0
         self._flat = {}
         g = torch.Generator().manual_seed(0)
         for key, shape in _parameter_shapes(cfg).items():      # transformers' initialisation: N(0, 0.02), LayerNorm (1, 0), biases 0
@@ -431,6 +553,15 @@ class TrainableRetriever(torch.nn.Module):
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
         return super().load_state_dict(sd, strict=strict, **kwargs)
+
+    def dropout_state(self):
+        """(seed, call): what, with the rates, determines every mask of the next tower pass; `call` advances once per
+        tower pass in train() mode with a rate above 0 (24 bits, wraps).  Save it next to a checkpoint to resume."""
+        return self._dropout_seed, self._dropout_call
+
+    def set_dropout_state(self, state):
+        seed, call = state
+        self._dropout_seed, self._dropout_call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFF
 
     def _apply(self, fn, *args, **kwargs):
         probe = fn(torch.empty(0, dtype=torch.float32, device=self.device))
@@ -474,24 +605,35 @@ class TrainableRetriever(torch.nn.Module):
         cu = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
         cu[1:] = torch.cumsum(lens, 0)
         eps, n_heads = float(cfg.layer_norm_eps), cfg.num_attention_heads
+        # dropout: one `call` per tower pass, so the two towers of a step differ; a site whose rate is 0 (or eval()) gets
+        # None and runs the dropout-free operator
+        p_hid = self.hidden_dropout_prob if self.training else 0.0
+        p_att = self.attention_probs_dropout_prob if self.training else 0.0
+        seed, call = self._dropout_seed, self._dropout_call
+        if p_hid > 0 or p_att > 0:
+            self._dropout_call = (call + 1) & 0xFFFFFF
+        hid = (lambda site: (p_hid, seed, site, call)) if p_hid > 0 else (lambda site: None)
+        att = (lambda site: (p_att, seed, site, call)) if p_att > 0 else (lambda site: None)
 
         e = f"{tower}.embeddings"
         h = _EmbedLayerNorm.apply(ids, cu, n_tokens, P[f"{e}.word_embeddings.weight"], P[f"{e}.position_embeddings.weight"],
                                   P[f"{e}.token_type_embeddings.weight"], P[f"{e}.LayerNorm.weight"],
                                   P[f"{e}.LayerNorm.bias"], eps)
+        if p_hid > 0:
+            h = _Dropout.apply(h, hid(0))
         for i in range(cfg.num_hidden_layers):
             p = f"{tower}.encoder.layer.{i}"
             qkv_b = torch.cat([P[f"{p}.attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
             qkv = _Linear.apply(h, None, *(P[f"{p}.attention.self.{n}.weight"] for n in ("query", "key", "value")))
-            ctx = _Attention.apply(qkv, qkv_b, cu, B, max_len, n_heads)
+            ctx = _Attention.apply(qkv, qkv_b, cu, B, max_len, n_heads, att(1 + 3 * i))
             a = _Linear.apply(ctx, None, P[f"{p}.attention.output.dense.weight"])
             h1 = _BiasResidualLayerNorm.apply(a, P[f"{p}.attention.output.dense.bias"], h,
                                               P[f"{p}.attention.output.LayerNorm.weight"],
-                                              P[f"{p}.attention.output.LayerNorm.bias"], eps)
+                                              P[f"{p}.attention.output.LayerNorm.bias"], eps, hid(2 + 3 * i))
             f = _BiasGelu.apply(_Linear.apply(h1, None, P[f"{p}.intermediate.dense.weight"]), P[f"{p}.intermediate.dense.bias"])
             o = _Linear.apply(f, None, P[f"{p}.output.dense.weight"])
             h = _BiasResidualLayerNorm.apply(o, P[f"{p}.output.dense.bias"], h1, P[f"{p}.output.LayerNorm.weight"],
-                                             P[f"{p}.output.LayerNorm.bias"], eps)
+                                             P[f"{p}.output.LayerNorm.bias"], eps, hid(3 + 3 * i))
         cls = h.index_select(0, cu[:-1].to(torch.int64))
         pooled = torch.tanh(_Linear.apply(cls, P[f"{tower}.pooler.dense.bias"], P[f"{tower}.pooler.dense.weight"]))
         return _Linear.apply(pooled, P[f"{proj}.bias"], P[f"{proj}.weight"])

@@ -1,7 +1,7 @@
 """Time of one forward + backward step of proqa_amd.trainable.TrainableRetriever (dev), bert-base on seeded synthetic
 batches at the reference's --train_batch_size 640 (retrieval/train_retriever_single.sh) and at 64.
 
-    python scripts/dev_train_step_timing.py [--out DIR] [--batches 640,64] [--steps 5] [--skip-trace]
+    python scripts/dev_train_step_timing.py [--out DIR] [--batches 640,64] [--steps 5] [--skip-trace] [--dropout P]
 
 Three measurements, each in a fresh child process of this script:
   events   forward + backward + zero_grad per step between CUDA events, median of --steps after 2 warm-up steps;
@@ -10,6 +10,10 @@ Three measurements, each in a fresh child process of this script:
   trace    `rocprofv3 --kernel-trace` (a run of its own: no counters, no other tracing) over the module's steps: time per
            kernel name and step, and the attention backward's fraction of the fp16 dense peak from the flops its shapes
            imply (five products of 2 L^2 64 per (sequence, head); the kernels execute nine).
+--dropout P (what BERT's dropout costs): the module is built with both rates P; in `events` and `trace` a step with
+dropout and a step without (the rates set to 0: the dropout-free kernels) take turns in one process, each --steps times
+after the warm-up.  `events` adds step_ms_median_dropout and dropout_step_ratio; `trace` adds dropout_kernel_ratios: the
+time of each dropout kernel over its dropout-free counterpart (the three attention kernels and the LayerNorm pair).
 Questions have 5-30 tokens (--max_query_length 30), paragraphs 60-220.  Prints one JSON line.
 """
 import argparse
@@ -84,20 +88,22 @@ class TorchTower:
                 "c": self.tower("bert_c", "proj_c", batch["input_ids_c"], batch["input_mask_c"])}
 
 
-def child(mode, batches, steps):
+def child(mode, batches, steps, dropout=0.0):
     sys.path.insert(0, ROOT)
     import torch
     import torch.nn.functional as F
     from proqa_amd.retriever import BERT_BASE
     from proqa_amd.trainable import TrainableRetriever, inbatch_loss
     dev = torch.device("cuda", 0)
-    model = TrainableRetriever(BERT_BASE, device=dev)
+    model = TrainableRetriever(BERT_BASE, device=dev, dropout_seed=0)
+    turns = [0.0, dropout] if dropout > 0 and mode != "torch" else [0.0]
     result = {}
     for pairs in batches:
         batch, lq, lc = make_batch(pairs, pairs, dev)
         forward = TorchTower(model) if mode == "torch" else model
         times = []
-        for step in range(WARMUP + steps):
+        for step in range((WARMUP + steps) * len(turns)):
+            model.hidden_dropout_prob = model.attention_probs_dropout_prob = turns[step % len(turns)]
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             out = forward(batch)
@@ -110,14 +116,20 @@ def child(mode, batches, steps):
             t1.record()
             torch.cuda.synchronize()
             times.append(t0.elapsed_time(t1))
-        result[str(pairs)] = {"step_ms_median": statistics.median(times[WARMUP:]), "step_ms_min": min(times[WARMUP:]),
+        plain = times[0::len(turns)][WARMUP:]
+        result[str(pairs)] = {"step_ms_median": statistics.median(plain), "step_ms_min": min(plain),
                               "loss": float(loss), "tokens": sum(lq) + sum(lc),
                               "attention_backward_flops": attention_flops(lq, 12, 12) + attention_flops(lc, 12, 12)}
+        if len(turns) > 1:
+            dropped = times[1::2][WARMUP:]
+            result[str(pairs)].update(dropout=dropout, step_ms_median_dropout=statistics.median(dropped),
+                                      dropout_step_ratio=statistics.median(dropped) / statistics.median(plain))
     print("RESULT " + json.dumps(result))
 
 
 def run_child(mode, args, prefix=()):
-    cmd = list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", mode, "--batches", args.batches, "--steps", str(args.steps)]
+    cmd = list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", mode, "--batches", args.batches, "--steps", str(args.steps),
+                          "--dropout", str(args.dropout)]
     out = subprocess.run(cmd, check=True, timeout=900, capture_output=True, text=True).stdout
     return json.loads([l for l in out.splitlines() if l.startswith("RESULT ")][-1][len("RESULT "):])
 
@@ -134,7 +146,9 @@ def read_trace(out_dir):
 
 def short(name):
     name = name.split("(")[0]
-    for tag in ("attention_bwd_dq", "attention_bwd_dkv", "attention_fwd", "bias_residual_layernorm_bwd", "bias_residual_layernorm",
+    for tag in ("attention_dropout_bwd_dq", "attention_dropout_bwd_dkv", "attention_dropout_fwd", "bias_residual_layernorm_dropout_bwd",
+                "bias_residual_layernorm_dropout", "dropout_rows",
+                "attention_bwd_dq", "attention_bwd_dkv", "attention_fwd", "bias_residual_layernorm_bwd", "bias_residual_layernorm",
                 "embed_layernorm_bwd", "embed_layernorm", "column_kernel", "reduce_slabs", "bias_gelu_out", "inbatch_loss_grad",
                 "inbatch_eval"):
         if tag in name:
@@ -149,10 +163,11 @@ def main():
     ap.add_argument("--batches", default="640,64")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--skip-trace", action="store_true")
+    ap.add_argument("--dropout", type=float, default=0.0, help="also time steps with both dropout rates at this value")
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
     if args.child:
-        return child(args.child, batches, args.steps)
+        return child(args.child, batches, args.steps, args.dropout)
     result = {"rocm": open("/opt/rocm/.info/version").read().strip() if os.path.exists("/opt/rocm/.info/version") else "",
               "module": run_child("events", args), "torch_autograd_fp16": run_child("torch", args)}
     if not args.skip_trace:
@@ -164,7 +179,7 @@ def main():
         for b in batches:      # one traced run per batch size, so that the kernels of a size are the whole trace
             d = os.path.join(args.out, str(b))
             os.makedirs(d, exist_ok=True)
-            one = argparse.Namespace(batches=str(b), steps=args.steps)
+            one = argparse.Namespace(batches=str(b), steps=args.steps, dropout=args.dropout)
             info = run_child("trace", one, prefix=[prof, "--kernel-trace", "--output-format", "csv", "-d", d, "--"])[str(b)]
             per = {}
             for name, s, e in read_trace(d):
@@ -175,6 +190,12 @@ def main():
             per_batch[str(b)] = {"kernel_us_per_step": dict(list(table.items())[:16]), "kernels_us_per_step_total": sum(table.values()),
                                  "attention_backward_us_per_step": att_us,
                                  "attention_backward_fraction_of_fp16_peak": info["attention_backward_flops"] / (att_us * 1e-6) / 1e12 / PEAK_TFLOPS if att_us else None}
+            if args.dropout > 0:       # (both kinds of step ran n times each in the traced process)
+                pairs = {"attention_fwd": "attention_dropout_fwd", "attention_bwd_dq": "attention_dropout_bwd_dq",
+                         "attention_bwd_dkv": "attention_dropout_bwd_dkv", "bias_residual_layernorm": "bias_residual_layernorm_dropout",
+                         "bias_residual_layernorm_bwd": "bias_residual_layernorm_dropout_bwd"}
+                per_batch[str(b)]["dropout_kernel_ratios"] = {k: table[v] / table[k] for k, v in pairs.items() if k in table and v in table}
+                per_batch[str(b)]["dropout_kernel_us_per_step"] = {v: table.get(v) for v in list(pairs.values()) + ["dropout_rows"]}
         result["trace"] = per_batch
     print(json.dumps(result))
 
