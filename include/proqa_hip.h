@@ -532,6 +532,63 @@ int proqa_attention_dropout_backward_f16(const void* qkv, const void* qkv_bias, 
  * exists one 32 x 32 tile at a time. */
 int proqa_inbatch_loss_grad_f16(const void* q, const void* c, const int32_t* target, const float* lse, const float* grad_in,
                                 int nq, int nc, int dim, void* dq, void* dc, void* stream);
+/* ------------------------------------------------------------------------------------
+ * The reader's training objective (qa/bert_retrieve_qa.py:64-171 with --shared-norm, joint loss and early loss, as
+ * qa/train_dense_qa.sh trains it) on the hidden states of B sequences [CLS] q [SEP] p [SEP] of ONE question, and its
+ * gradient.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive); the rules of the backward block above hold:
+ * every sum in fp32, linear in the incoming gradient, inf / NaN pass through, no allocation, no host synchronisation, no
+ * atomics, bit-identical from run to run.
+ *   s_b[t], e_b[t]   the logits of proqa_reader_span_f16 (same device function, same bits): fp16(fp32(hidden[t] . qa_w[k]) +
+ *                    qa_b[k]); rows outside the paragraph mask [para_offset[b], len(b) - 1) count as -inf.  With p > 0 the
+ *                    hidden row is dropped first: PROQA_DROPOUT_HIDDEN at (packed row, column) -- the packed row in both
+ *                    layouts --, factor applied in fp32; site 255 is reserved for this head.
+ *   Z^s, Z^e         fp32 log-sum-exp of s / e over the paragraph rows: of all sequences with
+ *                    PROQA_READER_LOSS_SHARED_NORM, of each sequence on its own without
+ *   r                softmax_j(q . para_embed[j]) over all n_paras rows, the dot products in fp32; the first `batch` rows
+ *                    belong to the sequences, in order.  Z^r = their log-sum-exp
+ *   l_ba             s_b[start_pos[b, a]] - Z^s + e_b[end_pos[b, a]] - Z^e + log r_b for a pair whose two positions lie inside
+ *                    the sequence's paragraph mask (positions are sequence coordinates, -1 = padding); other pairs count as 0
+ *   joint            -logsumexp over the valid pairs of l_ba, or 0 when no pair is valid
+ *   early            -(logsumexp over labels[j] != 0 of log r_j), or 0 when no label is set or PROQA_READER_LOSS_NO_EARLY
+ *   loss_out[3]      = (joint + early, joint, early), fp32
+ * Layout of hidden / logits as proqa_reader_span_f16: exactly one of seq_lens_dev (padded) and cu_seqlens_dev (packed).
+ * start_pos / end_pos: int32 [batch, n_answers].  q: fp16 [128].  para_embed: [n_paras, 128] of para_dtype (PROQA_F16 or
+ * PROQA_F32), labels int32 [n_paras].  logits_out: fp16 [rows, 2], the unmasked logits of every valid row (the padded
+ * layout's padding rows are zeros).
+ * stats: fp32 [8 + 2 * batch], what the backward needs of the forward: [0] joint, [1] Z^r, [2] the log-sum-exp of the gold
+ * rows' scores, [3] 1 if a pair is valid else 0, [4] 1 if the early term is live else 0, [5..7] 0, then (Z^s_b, Z^e_b) of
+ * every sequence (the same pair for all under the shared norm).
+ * Limits: hidden_size % 8 == 0 and <= 1024, dim == 128, 1 <= batch <= n_paras <= 65536, 1 <= n_answers <= 1024,
+ * seq_len <= 4096; anything else is PROQA_EINVAL before the device is touched.  hidden, qa_w, q, para_embed, ws 16-byte
+ * aligned.  ws / ws_bytes: caller-owned scratch of at least proqa_reader_loss_workspace_bytes(...) bytes (a pure host
+ * function; 0 for sizes out of range); contents undefined afterwards, the backward reads nothing the forward left there. */
+#define PROQA_READER_LOSS_SHARED_NORM 1
+#define PROQA_READER_LOSS_NO_EARLY 2
+size_t proqa_reader_loss_workspace_bytes(int batch, int seq_len, int hidden_size, int n_answers, int n_paras);
+int proqa_reader_loss_f16(const void* hidden, const int32_t* seq_lens_dev, const int32_t* cu_seqlens_dev, int batch,
+                          int seq_len, int hidden_size, const int32_t* para_offset_dev, const void* qa_w, const void* qa_b,
+                          const int32_t* start_pos, const int32_t* end_pos, int n_answers, const void* q,
+                          const void* para_embed, int para_dtype, const int32_t* labels, int n_paras, int dim, int flags,
+                          double p, uint64_t seed, int site, uint32_t call, void* logits_out, float* stats, float* loss_out,
+                          void* ws, size_t ws_bytes, void* stream);
+/* Its gradient, times the fp32 device scalar *grad_in.  With w_ba = exp(l_ba + joint), omega_b = sum_a w_ba and W^s_b[t] /
+ * W^e_b[t] the sums of the w_ba whose start / end is t:
+ *   dlogit        ds_b[t] = c_b exp(s_b[t] - Z^s) - W^s_b[t] (c_b = 1 under the shared norm, omega_b without), likewise de;
+ *                 zero outside the mask and when no pair is valid.  It exists in fp32 registers only.
+ *   d_hidden      fp16, laid out like hidden: (ds w_0 + de w_1) * keep * factor in fp32, rounded once.  EVERY element is
+ *                 written: rows outside the mask and the padded layout's padding rows are zeros.
+ *   d_qa_w [2, hidden_size], d_qa_b [2]   fp32: sum_t dlogit[t, k] * (dropped) hidden[t] and sum_t dlogit[t, k]; workgroup
+ *                 slabs added in ascending order.
+ *   d_q [128]     fp16: sum_j drank_j para_embed[j], drank_j = (r_j - omega_j [j < batch]) + (r_j - g_j), g_j = r_j / (sum of
+ *                 the gold r) on gold rows; each bracket is dropped with the loss term it belongs to.
+ * logits and stats as the forward wrote them for the same operands. */
+int proqa_reader_loss_backward_f16(const void* hidden, const int32_t* seq_lens_dev, const int32_t* cu_seqlens_dev, int batch,
+                                   int seq_len, int hidden_size, const int32_t* para_offset_dev, const void* qa_w,
+                                   const int32_t* start_pos, const int32_t* end_pos, int n_answers, const void* q,
+                                   const void* para_embed, int para_dtype, const int32_t* labels, int n_paras, int dim,
+                                   int flags, double p, uint64_t seed, int site, uint32_t call, const void* logits,
+                                   const float* stats, const float* grad_in, void* d_hidden, float* d_qa_w, float* d_qa_b,
+                                   void* d_q, void* ws, size_t ws_bytes, void* stream);
 /* The weight gradient of a linear layer y = x w^T, on a kernel of our own (csrc/linear_kernels.hip) so that it never
  * passes through fp16: fp16 operands, ONE fp32 sum over the whole token axis on v_mfma_f32_32x32x16_f16, fp32 output
  * written or accumulated straight into the caller's buffer.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive).

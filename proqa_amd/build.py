@@ -28,6 +28,7 @@ SOURCES = [
     "lt_gemm.cpp",
     "encoder.cpp",
     "reader_kernels.hip",
+    "reader_loss_kernels.hip",
     "inbatch_kernels.hip",
     "train_kernels.hip",
     "linear_kernels.hip",

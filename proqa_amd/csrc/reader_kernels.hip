@@ -13,16 +13,14 @@
 #include <cmath>
 
 #include "common.h"
+#include "reader_head.h"
 
 namespace proqa {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int kSpanThreads = 512;      // 8 waves per sequence
 constexpr int kSpanWaves = kSpanThreads / 64;
-constexpr int kMaxChunks = 2;          // hidden <= 64 lanes * 2 chunks * 8 = 1024
+constexpr int kMaxChunks = kHeadMaxChunks;   // hidden <= 64 lanes * 2 chunks * 8 = 1024
 constexpr int kMaxSpanSeqLen = 4096;   // 2 x 4096 fp32 logits = 32 KiB of LDS
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -89,26 +87,14 @@ __global__ __launch_bounds__(kSpanThreads) void reader_span(const _Float16* __re
         ya[c] = *(const f16x8*)(y + chunk * 8);
       }
     }
-    float s0 = 0.f, e0 = 0.f, s1 = 0.f, e1 = 0.f;
-#pragma unroll
-    for (int c = 0; c < kMaxChunks; ++c) {
-      const int chunk = lane + 64 * c;
-      if (chunk < n_chunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          s0 += (float)xa[c][i] * (float)w0[c][i];
-          e0 += (float)xa[c][i] * (float)w1[c][i];
-          s1 += (float)ya[c][i] * (float)w0[c][i];
-          e1 += (float)ya[c][i] * (float)w1[c][i];
-        }
-      }
-    }
-    s0 = wave_sum(s0);
-    e0 = wave_sum(e0);
-    s1 = wave_sum(s1);
-    e1 = wave_sum(e1);
+    // the head's arithmetic lives in reader_head.h (the training objective forms the same bits)
+    const DropoutParams no_drop = {};
+    float s0, e0, s1, e1;
+    head_row_dots<false>(xa, w0, w1, lane, n_chunks, no_drop, 0u, s0, e0);
+    head_row_dots<false>(ya, w0, w1, lane, n_chunks, no_drop, 0u, s1, e1);
+    const _Float16 hs0 = head_logit(s0, b0), he0 = head_logit(e0, b1);
+    const _Float16 hs1 = head_logit(s1, b0), he1 = head_logit(e1, b1);
     if (lane == 0) {
-      const _Float16 hs0 = (_Float16)(s0 + b0), he0 = (_Float16)(e0 + b1);
       lg[r] = (float)hs0;
       lg[seq_len + r] = (float)he0;
       if (logits_out) {
@@ -116,7 +102,6 @@ __global__ __launch_bounds__(kSpanThreads) void reader_span(const _Float16* __re
         *(f16x2*)(logits_out + (row0 + r) * 2) = o;
       }
       if (two) {
-        const _Float16 hs1 = (_Float16)(s1 + b0), he1 = (_Float16)(e1 + b1);
         lg[r2] = (float)hs1;
         lg[seq_len + r2] = (float)he1;
         if (logits_out) {

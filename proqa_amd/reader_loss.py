@@ -1,0 +1,182 @@
+"""The reader's training objective on MI355X: span + rank loss of one question's passages, with gradients.
+
+Replaces qa/bert_retrieve_qa.py:64-171 of the reference as qa/train_dense_qa.sh trains it (--shared-norm, joint loss,
+early loss over the sampler's top-5000): the qa_outputs head, the paragraph mask, both normalisations, the rank softmax
+over para_embed and the marginal over the answer positions are proqa_reader_loss_f16 (three launches), the gradient is
+proqa_reader_loss_backward_f16 (four launches).  No Python loop, no nonzero(), no device-to-host copy, and the [T, 2]
+logit gradient is never stored: it lives in fp32 registers, so a loss scale of 2^16 does not overflow it.
+
+torch computes nothing here: it owns the memory and the stream, casts the fp32 masters to fp16 (as trainable.py does) and
+the sampler's int64 positions / labels to the int32 the kernels take, and autograd carries the four gradients.
+"""
+import torch
+
+from . import _lib
+from ._lib import EMBED_DIM
+from .trainable import _workspace
+
+SHARED_NORM = 1
+NO_EARLY = 2
+READER_HEAD_SITE = 255     # the dropout site reserved for the reader head (csrc/dropout_rng.h)
+MAX_SEQ_LEN = 4096
+
+
+def _i32(x, device, name):
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(x)
+    if x.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"reader_loss: {name} must be an integer tensor, got {x.dtype}")
+    return x.to(device=device, dtype=torch.int32).contiguous()
+
+
+class _Geometry:
+    """What both kernels are told about the batch (plain numbers and the int32 device tensors)."""
+
+    def __init__(self, hidden, cu_seqlens, seq_lens, para_offset, start_positions, end_positions, para_embed, labels,
+                 shared_norm, early, qa_drop, dropout_state, max_seq_len):
+        dev = hidden.device
+        if (cu_seqlens is None) == (seq_lens is None):
+            raise ValueError("reader_loss: exactly one of cu_seqlens (packed hidden [T, H]) and seq_lens (padded hidden "
+                             "[B, L, H]) must be given")
+        if cu_seqlens is not None:
+            if hidden.dim() != 2:
+                raise ValueError(f"reader_loss: packed hidden must be [T, H], got {tuple(hidden.shape)}")
+            self.cu, self.lens = _i32(cu_seqlens, dev, "cu_seqlens"), None
+            self.batch = self.cu.numel() - 1
+            self.seq_len = int(max_seq_len) if max_seq_len is not None else min(max(hidden.shape[0], 1), MAX_SEQ_LEN)
+        else:
+            if hidden.dim() != 3:
+                raise ValueError(f"reader_loss: padded hidden must be [B, L, H], got {tuple(hidden.shape)}")
+            self.cu, self.lens = None, _i32(seq_lens, dev, "seq_lens")
+            self.batch, self.seq_len = hidden.shape[0], hidden.shape[1]
+            if self.lens.numel() != self.batch:
+                raise ValueError(f"reader_loss: seq_lens must be [{self.batch}]")
+        self.hidden_size = hidden.shape[-1]
+        self.para_offset = _i32(para_offset, dev, "para_offset")
+        self.start, self.end = _i32(start_positions, dev, "start_positions"), _i32(end_positions, dev, "end_positions")
+        if self.start.dim() != 2 or self.start.shape != self.end.shape or self.start.shape[0] != self.batch:
+            raise ValueError(f"reader_loss: start / end positions must both be [{self.batch}, A], got "
+                             f"{tuple(self.start.shape)} and {tuple(self.end.shape)}")
+        if self.para_offset.numel() != self.batch:
+            raise ValueError(f"reader_loss: para_offset must be [{self.batch}]")
+        self.n_answers = self.start.shape[1]
+        if not para_embed.is_cuda or para_embed.dim() != 2 or para_embed.dtype not in (torch.float16, torch.float32):
+            raise ValueError("reader_loss: para_embed must be a float16 or float32 [P, 128] CUDA tensor")
+        self.para = para_embed.contiguous()
+        self.para_dtype = _lib.PROQA_F16 if para_embed.dtype == torch.float16 else _lib.PROQA_F32
+        self.n_paras, self.dim = para_embed.shape
+        self.labels = _i32(labels, dev, "top5000_labels").reshape(-1)
+        if self.labels.numel() != self.n_paras:
+            raise ValueError(f"reader_loss: top5000_labels must be [{self.n_paras}], got {self.labels.numel()}")
+        self.flags = (SHARED_NORM if shared_norm else 0) | (0 if early else NO_EARLY)
+        self.p = float(qa_drop)
+        if self.p > 0:
+            if dropout_state is None:
+                raise ValueError("reader_loss: qa_drop > 0 needs dropout_state=(seed, call)")
+            seed, call = dropout_state
+            self.seed, self.call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFF
+        else:
+            self.seed, self.call = 0, 0
+
+    def layout(self):
+        return (self.lens.data_ptr() if self.lens is not None else None, self.cu.data_ptr() if self.cu is not None else None,
+                self.batch, self.seq_len, self.hidden_size, self.para_offset.data_ptr())
+
+    def objective(self, q):
+        return (self.start.data_ptr(), self.end.data_ptr(), self.n_answers, q.data_ptr(), self.para.data_ptr(), self.para_dtype,
+                self.labels.data_ptr(), self.n_paras, self.dim, self.flags, self.p, self.seed, READER_HEAD_SITE, self.call)
+
+    def workspace(self, lib, device):
+        need = lib.proqa_reader_loss_workspace_bytes(self.batch, self.seq_len, self.hidden_size, self.n_answers, self.n_paras)
+        return _workspace(device, need)
+
+
+def reader_loss_forward(hidden, w16, b16, q, geo):
+    """-> (loss_out fp32 [3] = total, joint, early; logits fp16 [rows, 2]; stats fp32 [8 + 2 B]); no autograd"""
+    lib = _lib.load()
+    dev = hidden.device
+    rows = hidden.numel() // max(geo.hidden_size, 1)
+    logits = torch.empty((rows, 2), dtype=torch.float16, device=dev)
+    stats = torch.empty(8 + 2 * max(geo.batch, 0), dtype=torch.float32, device=dev)
+    loss_out = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = geo.workspace(lib, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.proqa_reader_loss_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), b16.data_ptr(), *geo.objective(q),
+                                             logits.data_ptr(), stats.data_ptr(), loss_out.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), _lib.current_stream_ptr()))
+    return loss_out, logits, stats
+
+
+def reader_loss_backward(hidden, w16, q, geo, logits, stats, grad_in):
+    """grad_in: fp32 device scalar -> (d_hidden fp16 like hidden, d_qa_w fp32 [2, H], d_qa_b fp32 [2], d_q fp16 [128])"""
+    lib = _lib.load()
+    dev = hidden.device
+    d_hidden = torch.empty_like(hidden)
+    d_w = torch.empty((2, geo.hidden_size), dtype=torch.float32, device=dev)
+    d_b = torch.empty(2, dtype=torch.float32, device=dev)
+    d_q = torch.empty(EMBED_DIM, dtype=torch.float16, device=dev)
+    ws = geo.workspace(lib, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.proqa_reader_loss_backward_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), *geo.objective(q),
+                                                      logits.data_ptr(), stats.data_ptr(), grad_in.data_ptr(),
+                                                      d_hidden.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), d_q.data_ptr(),
+                                                      ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+    return d_hidden, d_w, d_b, d_q
+
+
+class _ReaderLoss(torch.autograd.Function):
+    """(hidden fp16, qa_weight fp32 master, qa_bias fp32 master, q fp16 [128]) -> fp32 [3] = (loss, joint, early); only
+    element 0 is differentiated."""
+
+    @staticmethod
+    def forward(ctx, hidden, qa_weight, qa_bias, q, geo):
+        w16, b16 = qa_weight.half().contiguous(), qa_bias.half().contiguous()
+        loss_out, logits, stats = reader_loss_forward(hidden, w16, b16, q, geo)
+        ctx.save_for_backward(hidden, w16, q, logits, stats)
+        ctx.geo = geo
+        return loss_out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        hidden, w16, q, logits, stats = ctx.saved_tensors
+        g = grad_out.to(torch.float32).contiguous()     # element 0: the gradient of the total loss
+        d_hidden, d_w, d_b, d_q = reader_loss_backward(hidden, w16, q, ctx.geo, logits, stats, g)
+        return d_hidden, d_w, d_b, d_q, None
+
+
+def reader_loss(hidden, qa_weight, qa_bias, q, para_embed, top5000_labels, start_positions, end_positions, para_offset, *,
+                cu_seqlens=None, seq_lens=None, shared_norm=True, early=True, qa_drop=0.0, dropout_state=None,
+                max_seq_len=None):
+    """The training loss of BertRetrieveQA.forward for the B passages of one question.
+
+    hidden            fp16 last hidden state of the reader's BERT: packed [T, H] with cu_seqlens (int [B + 1]), or padded
+                      [B, L, H] with seq_lens (int [B]); H % 8 == 0, H <= 1024
+    qa_weight/qa_bias the fp32 masters of qa_outputs, [2, H] and [2]; their gradients are fp32
+    q                 fp16 question embedding [128], or [n, 128] of which row 0 is taken (the reference's q[0]), e.g.
+                      TrainableRetriever.get_embed(batch, True)["embed"]
+    para_embed        [P, 128] float16 or float32, the sampler's rows; the first B belong to the sequences
+    top5000_labels    int [P]; start_positions / end_positions: int [B, A] in sequence coordinates, -1 = padding
+    para_offset       int [B]: the paragraph mask of sequence b is [para_offset[b], len(b) - 1)
+    shared_norm       --shared-norm; early=False is --drop-early (the loss without the early term)
+    qa_drop           rate of the dropout in front of qa_outputs; dropout_state = (seed, call), call advanced by the caller
+    max_seq_len       packed layout only: a bound on the longest sequence (default min(T, 4096))
+
+    -> {"loss": fp32 scalar with gradients w.r.t. hidden, q, qa_weight and qa_bias, "joint", "early": fp32 scalars, detached}.
+    Everything stays on the device and on torch's current stream."""
+    if not torch.is_tensor(hidden) or not hidden.is_cuda or hidden.dtype != torch.float16:
+        raise ValueError("reader_loss: hidden must be a float16 CUDA tensor (there is no CPU path)")
+    if not q.is_cuda or q.dtype != torch.float16 or q.shape[-1] != EMBED_DIM or q.dim() not in (1, 2):
+        raise ValueError(f"reader_loss: q must be a float16 CUDA tensor [{EMBED_DIM}] or [n, {EMBED_DIM}], got {q.dtype} "
+                         f"{tuple(q.shape)}")
+    if qa_weight.dtype != torch.float32 or qa_bias.dtype != torch.float32:
+        raise ValueError("reader_loss: qa_weight / qa_bias are the fp32 masters; they are cast to fp16 inside")
+    if tuple(qa_weight.shape) != (2, hidden.shape[-1]) or tuple(qa_bias.shape) != (2,):
+        raise ValueError(f"reader_loss: qa_weight must be [2, {hidden.shape[-1]}] and qa_bias [2]")
+    if not 0.0 <= float(qa_drop) <= 0.9:
+        raise ValueError(f"reader_loss: qa_drop={qa_drop!r} must be in [0, 0.9]")
+    geo = _Geometry(hidden.contiguous(), cu_seqlens, seq_lens, para_offset, start_positions, end_positions, para_embed,
+                    top5000_labels, shared_norm, early, qa_drop, dropout_state, max_seq_len)
+    q0 = (q[0] if q.dim() == 2 else q).contiguous()
+    out = _ReaderLoss.apply(hidden.contiguous(), qa_weight, qa_bias, q0, geo)
+    return {"loss": out[0], "joint": out[1].detach(), "early": out[2].detach()}
