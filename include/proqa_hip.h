@@ -465,6 +465,25 @@ int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids
                                               int64_t vocab, const void* pos_emb, const void* type_emb, const void* ln_gamma,
                                               float eps, float* dgamma, float* dbeta, float* d_word, float* d_pos,
                                               float* d_type0, void* ws, size_t ws_bytes, void* stream);
+/* backward of proqa_embed_layernorm_typed_varlen_f16 (the reader's [CLS] q [SEP] p [SEP] with segment ids); the rules and
+ * the arguments of proqa_embed_layernorm_varlen_backward_f16, with: type_ids_dev int64 padded [batch, seq_len] like ids
+ * (NULL: every token has type 0); type_emb_table [n_types, hidden] fp16; d_types [n_types, hidden] fp32, ADDED INTO like
+ * the other four.  n_types must be 1 or 2 (BERT's type_vocab_size).  A type id outside [0, n_types) read row 0 in the
+ * forward and its gradient goes to row 0; likewise a word id outside the vocabulary.  Everything but d_word is
+ * bit-identical from run to run: a workgroup owns a position, keeps its sum in two parts (tokens of type 0, of type 1),
+ * d_pos[s] is their sum and d_types[t] the sum over the positions of part t, in ascending order.  With type_ids NULL,
+ * dgamma / dbeta / d_pos / d_types[0] carry the bits of the untyped entry point.  ws: at least
+ * proqa_embed_layernorm_typed_backward_workspace_bytes(hidden) bytes (four quantities per position, one more than
+ * proqa_backward_workspace_bytes provides).  PROQA_EINVAL before any launch for n_types, hidden % 8, hidden > 1024,
+ * seq_len > 512, a short workspace or a NULL argument other than type_ids_dev. */
+size_t proqa_embed_layernorm_typed_backward_workspace_bytes(int hidden);
+int proqa_embed_layernorm_typed_varlen_backward_f16(const void* dy, const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                                    const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden,
+                                                    int64_t n_tokens, const void* word_emb, int64_t vocab,
+                                                    const void* pos_emb, const void* type_emb_table, int n_types,
+                                                    const void* ln_gamma, float eps, float* dgamma, float* dbeta,
+                                                    float* d_word, float* d_pos, float* d_types, void* ws, size_t ws_bytes,
+                                                    void* stream);
 /* backward of proqa_attention_ex_f16 on the packed layout (cls_only = 0): qkv [n_tokens, 3*hidden] (the GEMM output before
  * the bias), qkv_bias [3*hidden] or NULL, d_ctx [n_tokens, hidden] -> d_qkv [n_tokens, 3*hidden], every element written.
  * The probabilities are recomputed with the forward's conventions (query bias added, key bias dropped, scores / 8, fp32

@@ -362,6 +362,130 @@ __global__ __launch_bounds__(256) void embed_layernorm_bwd(const _Float16* __res
   }
 }
 
+// ---- embedding + LayerNorm backward with token types (the reader's [CLS] q [SEP] p [SEP]) ---------------------------------
+// embed_layernorm_bwd with a fourth per-wave accumulator: the position's sum is kept in two parts, the tokens of type 0
+// and those of type 1 (a type id outside [0, n_types) read row 0 in the forward and counts as type 0 here).  Slab s of the
+// workspace is (dgamma, dbeta, d_types[0], d_types[1]) of position s; d_pos[s] = part 0 + part 1.  With type_ids == nullptr
+// part 1 is +0 and every sum is the sum embed_layernorm_bwd takes, in its order.
+__global__ __launch_bounds__(256) void embed_layernorm_typed_bwd(
+    const _Float16* __restrict__ dy_in, const long long* __restrict__ ids, const long long* __restrict__ type_ids,
+    const int* __restrict__ cu_seqlens, int batch, int seq_len, int hidden, const _Float16* __restrict__ word, long long vocab,
+    const _Float16* __restrict__ pos, const _Float16* __restrict__ type_table, int n_types,
+    const _Float16* __restrict__ gamma, float eps, long long n_tokens, float* __restrict__ d_word, float* __restrict__ d_pos,
+    float* __restrict__ ws) {
+  __shared__ float red[3][4][64 * kMaxChunksPerLane * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_chunks = hidden >> 3;
+  const int s = blockIdx.x;
+  float gam[kMaxChunksPerLane][8], posr[kMaxChunksPerLane][8];
+  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dty0[kMaxChunksPerLane][8], dty1[kMaxChunksPerLane][8];
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c) {
+    const int chunk = lane + 64 * c;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gam[c][i] = posr[c][i] = dgam[c][i] = dbet[c][i] = dty0[c][i] = dty1[c][i] = 0.f;
+    if (chunk < n_chunks) {
+      load8(gamma + chunk * 8, gam[c]);
+      load8(pos + (long long)s * hidden + chunk * 8, posr[c]);
+    }
+  }
+  for (int b = wave; b < batch; b += 4) {
+    const int first = cu_seqlens[b];
+    const long long row = (long long)first + s;
+    if (s >= cu_seqlens[b + 1] - first || row >= n_tokens) continue;   // wave-uniform
+    long long id = ids[(long long)b * seq_len + s];
+    if (id < 0 || id >= vocab) id = 0;   // the forward read row 0 for such an id
+    long long tt = type_ids ? type_ids[(long long)b * seq_len + s] : 0;
+    if (tt < 0 || tt >= n_types) tt = 0;   // and row 0 of the type table
+    float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+        float w[8], t[8];
+        load8(word + id * hidden + chunk * 8, w);
+        load8(type_table + tt * hidden + chunk * 8, t);
+        load8(dy_in + row * hidden + chunk * 8, dy[c]);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) z[c][i] = w[i] + (posr[c][i] + t[i]);   // embed_layernorm_bwd's association
+      }
+    }
+    layernorm_backward_row(z, dy, gam, lane, n_chunks, hidden, eps, dz, dgam, dbet);
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          if (tt == 0) dty0[c][i] += dz[c][i];   // wave-uniform
+          else dty1[c][i] += dz[c][i];
+          atomicAdd(d_word + id * hidden + chunk * 8 + i, dz[c][i]);
+        }
+      }
+    }
+  }
+  // the four per-wave partials -> slab s, waves added in ascending order (reduce_waves_to_slab with one more quantity)
+  if (wave > 0) {
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          red[wave - 1][0][chunk * 8 + i] = dgam[c][i];
+          red[wave - 1][1][chunk * 8 + i] = dbet[c][i];
+          red[wave - 1][2][chunk * 8 + i] = dty0[c][i];
+          red[wave - 1][3][chunk * 8 + i] = dty1[c][i];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    float* __restrict__ slab = ws + (long long)s * 4 * hidden;
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          float a = dgam[c][i], b = dbet[c][i], t0 = dty0[c][i], t1 = dty1[c][i];
+          for (int w = 0; w < 3; ++w) {
+            a += red[w][0][chunk * 8 + i];
+            b += red[w][1][chunk * 8 + i];
+            t0 += red[w][2][chunk * 8 + i];
+            t1 += red[w][3][chunk * 8 + i];
+          }
+          slab[chunk * 8 + i] = a;
+          slab[hidden + chunk * 8 + i] = b;
+          slab[2 * hidden + chunk * 8 + i] = t0;
+          slab[3 * hidden + chunk * 8 + i] = t1;
+          d_pos[(long long)s * hidden + chunk * 8 + i] += t0 + t1;
+        }
+      }
+    }
+  }
+}
+
+// out_k[c] += sum over the slabs, in ascending order, of ws[slab][k][c], k < 4 (reduce_slabs' compensated sum); a null
+// out_k is skipped
+__global__ __launch_bounds__(256) void reduce_slabs_typed(const float* __restrict__ ws, int n_slabs, int cols, float* out0,
+                                                          float* out1, float* out2, float* out3) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 4 * cols) return;
+  const int k = t / cols, c = t - k * cols;
+  float* out = k == 0 ? out0 : (k == 1 ? out1 : (k == 2 ? out2 : out3));
+  if (!out) return;
+  float s = 0.f, comp = 0.f;
+  for (int b = 0; b < n_slabs; ++b) {
+    const float y = ws[((long long)b * 4 + k) * cols + c] - comp;
+    const float t = s + y;
+    comp = (t - s) - y;
+    s = t;
+  }
+  out[c] = out[c] + s;
+}
+
 // ---- column-owning kernels: column sum, bias + GELU backward --------------------------------------------------------------
 // workgroup = slab of rows, thread = up to kMaxColChunks 8-column pieces of every row of the slab, summed in row order:
 // no reduction inside the workgroup.  MODE 0: sum of x.  MODE 1: dx = dy gelu'(x_pre + bias), sum of dx.
@@ -1222,6 +1346,43 @@ int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids
                      (long long)n_tokens, d_word, d_pos, (float*)ws);
   PROQA_LAUNCH_CHECK();
   return launch_reduce((const float*)ws, seq_len, 3, hidden, dgamma, dbeta, nullptr, d_type0, 1, st);
+}
+
+size_t proqa_embed_layernorm_typed_backward_workspace_bytes(int hidden) {
+  return hidden > 0 ? (size_t)kMaxSlabs * 4 * (size_t)hidden * sizeof(float) : 0;
+}
+
+int proqa_embed_layernorm_typed_varlen_backward_f16(const void* dy, const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                                    const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden,
+                                                    int64_t n_tokens, const void* word_emb, int64_t vocab,
+                                                    const void* pos_emb, const void* type_emb_table, int n_types,
+                                                    const void* ln_gamma, float eps, float* dgamma, float* dbeta,
+                                                    float* d_word, float* d_pos, float* d_types, void* ws, size_t ws_bytes,
+                                                    void* stream) {
+  if (!dy || !ids_dev || !cu_seqlens_dev || !word_emb || !pos_emb || !type_emb_table || !ln_gamma || !dgamma || !dbeta ||
+      !d_word || !d_pos || !d_types || !ws)
+    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: NULL argument");
+  if (n_types != 1 && n_types != 2)
+    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: n_types=%d must be 1 or 2", n_types);
+  if (batch < 0 || seq_len <= 0 || seq_len > kMaxSlabs || vocab <= 0 || n_tokens < 0)
+    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: bad sizes (seq_len <= %d)", kMaxSlabs);
+  if (hidden <= 0 || hidden % 8 || hidden > 64 * kMaxChunksPerLane * 8)
+    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: hidden=%d must be a multiple of 8 and <= %d", hidden,
+                64 * kMaxChunksPerLane * 8);
+  if (ws_bytes < proqa_embed_layernorm_typed_backward_workspace_bytes(hidden))
+    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: workspace too small");
+  if (batch == 0 || n_tokens == 0) return PROQA_OK;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(embed_layernorm_typed_bwd, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
+                     (const long long*)ids_dev, (const long long*)type_ids_dev, (const int*)cu_seqlens_dev, batch, seq_len,
+                     hidden, (const _Float16*)word_emb, (long long)vocab, (const _Float16*)pos_emb,
+                     (const _Float16*)type_emb_table, n_types, (const _Float16*)ln_gamma, eps, (long long)n_tokens, d_word,
+                     d_pos, (float*)ws);
+  PROQA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(reduce_slabs_typed, dim3((unsigned)ceil_div<int>(4 * hidden, 256)), dim3(256), 0, st, (const float*)ws,
+                     seq_len, hidden, dgamma, dbeta, d_types, n_types == 2 ? d_types + hidden : (float*)nullptr);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
 }
 
 int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx, const int32_t* cu_seqlens_dev,

@@ -159,6 +159,43 @@ def embed_layernorm_backward(dy, ids, cu_seqlens, word, pos, type0, gamma, eps):
     return dgamma, dbeta, d_word, d_pos, d_type0
 
 
+def embed_layernorm_typed(ids, type_ids, cu_seqlens, n_tokens, word, pos, types, gamma, beta, eps):
+    """embed_layernorm with token types: type_ids int64 [batch, seq_len] like ids (None: all 0), types [n_types, hidden]"""
+    lib = _lib.load()
+    batch, seq_len = ids.shape
+    hidden = word.shape[1]
+    out = torch.empty((n_tokens, hidden), dtype=torch.float16, device=ids.device)
+    _call(lib.proqa_embed_layernorm_typed_varlen_f16, ids.device, ids.data_ptr(), type_ids.data_ptr() if type_ids is not None
+          else None, cu_seqlens.data_ptr(), batch, seq_len, hidden, _f16(word, "word").data_ptr(), word.shape[0],
+          _f16(pos, "pos").data_ptr(), _f16(types, "types").data_ptr(), types.shape[0], _f16(gamma, "gamma").data_ptr(),
+          _f16(beta, "beta").data_ptr(), float(eps), out.data_ptr())
+    return out
+
+
+def embed_layernorm_typed_backward(dy, ids, type_ids, cu_seqlens, word, pos, types, gamma, eps):
+    """-> fp32 (dgamma [hidden], dbeta [hidden], d_word [vocab, hidden], d_pos [positions, hidden], d_types [n_types, hidden])"""
+    lib = _lib.load()
+    dy = _f16(dy, "dy")
+    batch, seq_len = ids.shape
+    n_tokens, hidden = dy.shape
+    if seq_len > pos.shape[0]:
+        raise ValueError(f"sequence length {seq_len} exceeds the {pos.shape[0]} positions of the table")
+    if type_ids is not None and type_ids.shape != ids.shape:
+        raise ValueError(f"type_ids {tuple(type_ids.shape)} must have the shape of ids {tuple(ids.shape)}")
+    dev = dy.device
+    dgamma, dbeta = (torch.zeros(hidden, dtype=torch.float32, device=dev) for _ in range(2))
+    d_word = torch.zeros(word.shape, dtype=torch.float32, device=dev)
+    d_pos = torch.zeros(pos.shape, dtype=torch.float32, device=dev)
+    d_types = torch.zeros(types.shape, dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.proqa_embed_layernorm_typed_backward_workspace_bytes(hidden))
+    _call(lib.proqa_embed_layernorm_typed_varlen_backward_f16, dev, dy.data_ptr(), ids.data_ptr(),
+          type_ids.data_ptr() if type_ids is not None else None, cu_seqlens.data_ptr(), batch, seq_len, hidden, n_tokens,
+          _f16(word, "word").data_ptr(), word.shape[0], _f16(pos, "pos").data_ptr(), _f16(types, "types").data_ptr(),
+          types.shape[0], _f16(gamma, "gamma").data_ptr(), float(eps), dgamma.data_ptr(), dbeta.data_ptr(), d_word.data_ptr(),
+          d_pos.data_ptr(), d_types.data_ptr(), ws.data_ptr(), ws.numel())
+    return dgamma, dbeta, d_word, d_pos, d_types
+
+
 def attention(qkv, qkv_bias, cu_seqlens, batch, max_seq_len, n_heads):
     """qkv packed [T, 3*hidden] fp16 (before the bias), qkv_bias [3*hidden] fp16 or None -> ctx [T, hidden]"""
     lib = _lib.load()
@@ -327,6 +364,24 @@ class _EmbedLayerNorm(torch.autograd.Function):
         return None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None
 
 
+class _EmbedLayerNormTyped(torch.autograd.Function):
+    """The reader's embeddings: token types from `type_ids`; the gradient of the type table is the full [n_types, hidden]."""
+
+    @staticmethod
+    def forward(ctx, ids, type_ids, cu_seqlens, n_tokens, word, pos, types, gamma, beta, eps):
+        w16, p16, t16, g16 = word.half(), pos.half(), types.half().contiguous(), gamma.half()
+        ctx.save_for_backward(ids, type_ids, cu_seqlens, w16, p16, t16, g16)
+        ctx.eps = eps
+        return embed_layernorm_typed(ids, type_ids, cu_seqlens, n_tokens, w16, p16, t16, g16, beta.half(), eps)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        ids, type_ids, cu, w16, p16, t16, g16 = ctx.saved_tensors
+        dgamma, dbeta, d_word, d_pos, d_types = embed_layernorm_typed_backward(dy, ids, type_ids, cu, w16, p16, t16, g16, ctx.eps)
+        return None, None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None
+
+
 class _Dropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, drop):
@@ -454,6 +509,73 @@ def inbatch_loss(q, c, target=None):
     return _InBatchLoss.apply(q, c, target)
 
 
+# ---- one tower pass, shared by TrainableRetriever and TrainableReader ----------------------------------------------------------
+
+def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None, drop=(0.0, 0.0, 0, 0), probe_extra=None):
+    """One BERT tower with gradients.  P: {key: fp32 master}; `tower` the key prefix of the tower's parameters (bert_q,
+    bert_c, bert).  input_ids / input_mask [B, S] right-padded CUDA tensors, B >= 1; type_ids [B, S] or None (every token
+    of type 0: the untyped embedding operator).  drop = (hidden rate, attention rate, seed, call) of this pass; a rate of 0
+    runs the dropout-free operator.  probe_extra(lens) -> (device bool scalar, message): one more condition for the pass's
+    single host round trip to check (ValueError(message) when it holds).
+    -> proj given (the key prefix of the projection): the [B, 128] fp16 embedding of pooler + projection;
+       proj None: (h, cu_seqlens, lens, max_len), the packed last hidden state [T, H] fp16 and its geometry."""
+    B, S = input_ids.shape
+    if S > cfg.max_position_embeddings or S > 512:
+        raise ValueError(f"sequence length {S} exceeds max_position_embeddings {cfg.max_position_embeddings} (or 512)")
+    ids = input_ids.contiguous().to(torch.int64)
+    mask = input_mask.to(torch.bool)
+    # as BertForRetriever.encode: a row without a valid token is evaluated as its first token; the mask of every row
+    # must be a prefix of ones (re_collate pads on the right); one host round trip for the check and the sizes
+    lens = mask.sum(dim=1).clamp_(min=1).to(torch.int32)
+    bad = (mask[:, 1:] & ~mask[:, :-1]).any() if S > 1 else torch.zeros((), dtype=torch.bool, device=mask.device)
+    flags = [bad.to(torch.int64), lens.sum(dtype=torch.int64), lens.max().to(torch.int64)]
+    extra_message = None
+    if probe_extra is not None:
+        extra_bad, extra_message = probe_extra(lens)
+        flags.append(extra_bad.to(torch.int64))
+    probe = torch.stack(flags).cpu()
+    if bool(probe[0]):
+        raise ValueError("input_mask must be right-padded (a prefix of True per row), as re_collate produces")
+    if extra_message is not None and bool(probe[3]):
+        raise ValueError(extra_message)
+    n_tokens, max_len = int(probe[1]), int(probe[2])
+    cu = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
+    cu[1:] = torch.cumsum(lens, 0)
+    eps, n_heads = float(cfg.layer_norm_eps), cfg.num_attention_heads
+    # a site whose rate is 0 (or eval()) gets None and runs the dropout-free operator
+    p_hid, p_att, seed, call = drop
+    hid = (lambda site: (p_hid, seed, site, call)) if p_hid > 0 else (lambda site: None)
+    att = (lambda site: (p_att, seed, site, call)) if p_att > 0 else (lambda site: None)
+
+    e = f"{tower}.embeddings"
+    tables = (P[f"{e}.word_embeddings.weight"], P[f"{e}.position_embeddings.weight"], P[f"{e}.token_type_embeddings.weight"],
+              P[f"{e}.LayerNorm.weight"], P[f"{e}.LayerNorm.bias"])
+    if type_ids is None:
+        h = _EmbedLayerNorm.apply(ids, cu, n_tokens, *tables, eps)
+    else:
+        h = _EmbedLayerNormTyped.apply(ids, type_ids.contiguous().to(torch.int64), cu, n_tokens, *tables, eps)
+    if p_hid > 0:
+        h = _Dropout.apply(h, hid(0))
+    for i in range(cfg.num_hidden_layers):
+        p = f"{tower}.encoder.layer.{i}"
+        qkv_b = torch.cat([P[f"{p}.attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
+        qkv = _Linear.apply(h, None, *(P[f"{p}.attention.self.{n}.weight"] for n in ("query", "key", "value")))
+        ctx = _Attention.apply(qkv, qkv_b, cu, B, max_len, n_heads, att(1 + 3 * i))
+        a = _Linear.apply(ctx, None, P[f"{p}.attention.output.dense.weight"])
+        h1 = _BiasResidualLayerNorm.apply(a, P[f"{p}.attention.output.dense.bias"], h,
+                                          P[f"{p}.attention.output.LayerNorm.weight"],
+                                          P[f"{p}.attention.output.LayerNorm.bias"], eps, hid(2 + 3 * i))
+        f = _BiasGelu.apply(_Linear.apply(h1, None, P[f"{p}.intermediate.dense.weight"]), P[f"{p}.intermediate.dense.bias"])
+        o = _Linear.apply(f, None, P[f"{p}.output.dense.weight"])
+        h = _BiasResidualLayerNorm.apply(o, P[f"{p}.output.dense.bias"], h1, P[f"{p}.output.LayerNorm.weight"],
+                                         P[f"{p}.output.LayerNorm.bias"], eps, hid(3 + 3 * i))
+    if proj is None:
+        return h, cu, lens, max_len
+    cls = h.index_select(0, cu[:-1].to(torch.int64))
+    pooled = torch.tanh(_Linear.apply(cls, P[f"{tower}.pooler.dense.bias"], P[f"{tower}.pooler.dense.weight"]))
+    return _Linear.apply(pooled, P[f"{proj}.bias"], P[f"{proj}.weight"])
+
+
 # ---- the module -----------------------------------------------------------------------------------------------------------
 
 def state_dict_keys(config):
@@ -463,10 +585,11 @@ def state_dict_keys(config):
     return (tower_keys("bert_q", n) + tower_keys("bert_c", n) + ["proj_q.weight", "proj_q.bias", "proj_c.weight", "proj_c.bias"])
 
 
-def _parameter_shapes(cfg):
+def _parameter_shapes(cfg, keys=None):
+    """{key: shape} of the tower / projection parameters `keys` (default: the retriever's state_dict_keys)"""
     H, I = cfg.hidden_size, cfg.intermediate_size
     shapes = {}
-    for key in state_dict_keys(cfg):
+    for key in (state_dict_keys(cfg) if keys is None else keys):
         if key.startswith("proj_"):
             shapes[key] = (EMBED_DIM, H) if key.endswith("weight") else (EMBED_DIM,)
         elif "word_embeddings" in key:
@@ -584,56 +707,14 @@ class TrainableRetriever(torch.nn.Module):
         return {"embed": self._tower(tower, proj, batch["input_ids"], batch["input_mask"])}
 
     def _tower(self, tower, proj, input_ids, input_mask):
-        cfg, P = self.config, self._flat
         if not input_ids.is_cuda:
             raise RuntimeError("TrainableRetriever expects CUDA tensors (the reference feeds move_to_cuda(batch))")
-        B, S = input_ids.shape
-        if S > cfg.max_position_embeddings or S > 512:
-            raise ValueError(f"sequence length {S} exceeds max_position_embeddings {cfg.max_position_embeddings} (or 512)")
-        if B == 0:
+        if input_ids.shape[0] == 0:
             return torch.empty((0, EMBED_DIM), dtype=torch.float16, device=self.device)
-        ids = input_ids.contiguous().to(torch.int64)
-        mask = input_mask.to(torch.bool)
-        # as BertForRetriever.encode: a row without a valid token is evaluated as its first token; the mask of every row
-        # must be a prefix of ones (re_collate pads on the right); one host round trip for the check and the sizes
-        lens = mask.sum(dim=1).clamp_(min=1).to(torch.int32)
-        bad = (mask[:, 1:] & ~mask[:, :-1]).any() if S > 1 else torch.zeros((), dtype=torch.bool, device=mask.device)
-        probe = torch.stack([bad.to(torch.int64), lens.sum(dtype=torch.int64), lens.max().to(torch.int64)]).cpu()
-        if bool(probe[0]):
-            raise ValueError("input_mask must be right-padded (a prefix of True per row), as re_collate produces")
-        n_tokens, max_len = int(probe[1]), int(probe[2])
-        cu = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
-        cu[1:] = torch.cumsum(lens, 0)
-        eps, n_heads = float(cfg.layer_norm_eps), cfg.num_attention_heads
-        # dropout: one `call` per tower pass, so the two towers of a step differ; a site whose rate is 0 (or eval()) gets
-        # None and runs the dropout-free operator
+        # dropout: one `call` per tower pass, so the two towers of a step differ
         p_hid = self.hidden_dropout_prob if self.training else 0.0
         p_att = self.attention_probs_dropout_prob if self.training else 0.0
         seed, call = self._dropout_seed, self._dropout_call
         if p_hid > 0 or p_att > 0:
             self._dropout_call = (call + 1) & 0xFFFFFF
-        hid = (lambda site: (p_hid, seed, site, call)) if p_hid > 0 else (lambda site: None)
-        att = (lambda site: (p_att, seed, site, call)) if p_att > 0 else (lambda site: None)
-
-        e = f"{tower}.embeddings"
-        h = _EmbedLayerNorm.apply(ids, cu, n_tokens, P[f"{e}.word_embeddings.weight"], P[f"{e}.position_embeddings.weight"],
-                                  P[f"{e}.token_type_embeddings.weight"], P[f"{e}.LayerNorm.weight"],
-                                  P[f"{e}.LayerNorm.bias"], eps)
-        if p_hid > 0:
-            h = _Dropout.apply(h, hid(0))
-        for i in range(cfg.num_hidden_layers):
-            p = f"{tower}.encoder.layer.{i}"
-            qkv_b = torch.cat([P[f"{p}.attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
-            qkv = _Linear.apply(h, None, *(P[f"{p}.attention.self.{n}.weight"] for n in ("query", "key", "value")))
-            ctx = _Attention.apply(qkv, qkv_b, cu, B, max_len, n_heads, att(1 + 3 * i))
-            a = _Linear.apply(ctx, None, P[f"{p}.attention.output.dense.weight"])
-            h1 = _BiasResidualLayerNorm.apply(a, P[f"{p}.attention.output.dense.bias"], h,
-                                              P[f"{p}.attention.output.LayerNorm.weight"],
-                                              P[f"{p}.attention.output.LayerNorm.bias"], eps, hid(2 + 3 * i))
-            f = _BiasGelu.apply(_Linear.apply(h1, None, P[f"{p}.intermediate.dense.weight"]), P[f"{p}.intermediate.dense.bias"])
-            o = _Linear.apply(f, None, P[f"{p}.output.dense.weight"])
-            h = _BiasResidualLayerNorm.apply(o, P[f"{p}.output.dense.bias"], h1, P[f"{p}.output.LayerNorm.weight"],
-                                             P[f"{p}.output.LayerNorm.bias"], eps, hid(3 + 3 * i))
-        cls = h.index_select(0, cu[:-1].to(torch.int64))
-        pooled = torch.tanh(_Linear.apply(cls, P[f"{tower}.pooler.dense.bias"], P[f"{tower}.pooler.dense.weight"]))
-        return _Linear.apply(pooled, P[f"{proj}.bias"], P[f"{proj}.weight"])
+        return run_tower(self._flat, tower, self.config, input_ids, input_mask, proj=proj, drop=(p_hid, p_att, seed, call))

@@ -1,0 +1,241 @@
+"""Trainable reader on MI355X: BertRetrieveQA (qa/bert_retrieve_qa.py of the reference) with gradients.
+
+`TrainableReader` is a torch.nn.Module with the parameter names of the reference's BertRetrieveQA.state_dict() -- `bert.*`
+(the reader's BERT, read with segment ids), `qa_outputs.*`, and `retriever.*`, a TrainableRetriever submodule -- so the
+reference's loop (qa/train_retrieve_qa.py) runs with the model class and the optimizer swapped, its sampler keeps calling
+`model.retriever.get_embed`, and the checkpoint it saves loads into BertReader.load / train_retrieve_qa.py --do_predict.
+
+forward(net_input) in train() mode is three steps, all on the device: the reader tower on [CLS] q [SEP] p [SEP] with token
+types (trainable.run_tower: the operators of TrainableRetriever, the embeddings through
+proqa_embed_layernorm_typed_varlen_f16 and its backward), the question tower on ROW 0 of input_ids_q (the reference runs B
+identical rows and uses q[0]), and proqa_amd.reader_loss on the packed hidden states.  One host round trip per tower pass
+(the sizes and the checks of the masks), none in the loss.
+
+forward(net_input) in eval() mode returns the reference's keys (start_logits, end_logits, rank_logits) for its dev loop.  It
+runs the INFERENCE class (proqa_amd.reader.BertReader: the fused encoder and proqa_reader_span_f16) over an fp16 copy of the
+parameters, taken at the first forward after eval() is entered, so a dev score during training is the score --do_predict
+gives for the checkpoint.  predict_qa keeps BertReader itself as its hot path.
+
+Precision and dropout are TrainableRetriever's: fp32 masters, fp16 activations, fp32 sums and parameter gradients; BERT's
+two rates inside the fused operators, qa_drop inside the loss kernels (site 255).  Not built: --separate and --add-select
+(they need a select term in the loss kernels).  There is no CPU path.
+"""
+import torch
+
+from .reader import BertReader
+from .reader_loss import reader_loss
+from .retriever import config_from_dict, tower_keys
+from .trainable import TrainableRetriever, _Node, _parameter_shapes, run_tower
+from .trainable import state_dict_keys as _retriever_keys
+
+CALLS_PER_FORWARD = 3      # dropout `call`s one train() forward takes: reader tower, question tower, head
+
+
+def state_dict_keys(config):
+    """The keys of the reference's BertRetrieveQA.state_dict() (without `position_ids` buffers), in its order, without a GPU."""
+    cfg = config if not isinstance(config, dict) else config_from_dict(config)
+    return (tower_keys("bert", cfg.num_hidden_layers) + ["retriever." + k for k in _retriever_keys(cfg)] +
+            ["qa_outputs.weight", "qa_outputs.bias"])
+
+
+_PARAGRAPH_MESSAGE = ("paragraph_mask must be one run of True per row, from the paragraph's first token to the token before "
+                      "the final [SEP]")
+
+
+def _paragraph_geometry(pmask, lens):
+    """(para_offset int32 [B]: the first True of the row, or the row's length; a device bool: some row is not
+    [para_offset, len - 1)) -- on the device, no host round trip"""
+    S = pmask.shape[1]
+    ar = torch.arange(S, device=pmask.device, dtype=torch.int32)[None]
+    first = torch.argmax(pmask.to(torch.int8), dim=1).to(torch.int32)
+    po = torch.where(pmask.any(dim=1), first, lens)
+    want = (ar >= po[:, None]) & (ar < (lens[:, None] - 1))
+    return po, (want != pmask).any()
+
+
+def _check_rate(name, rate):
+    if not 0.0 <= float(rate) <= 0.9:
+        raise ValueError(f"{name}={rate!r}: a dropout rate must be in [0, 0.9]")
+    return float(rate)
+
+
+class TrainableReader(torch.nn.Module):
+    """BertRetrieveQA with gradients.  forward(net_input) takes the sampler's net_input; train(): {"loss", "joint",
+    "early"}, eval(): {"start_logits", "end_logits", "rank_logits"}."""
+
+    def __init__(self, config, device=None, *, shared_norm=True, drop_early=False, qa_drop=0.0, hidden_dropout_prob=0.0,
+                 attention_probs_dropout_prob=0.0, dropout_seed=None, separate=False, add_select=False):
+        super().__init__()
+        cfg = config if not isinstance(config, dict) else config_from_dict(config)
+        if separate or add_select:
+            raise ValueError("TrainableReader: separate / add_select are not built: they need a select term in the loss "
+                             "kernels (DESIGN.md section 3h)")
+        self.qa_drop = _check_rate("qa_drop", qa_drop)
+        self.hidden_dropout_prob = _check_rate("hidden_dropout_prob", hidden_dropout_prob)
+        self.attention_probs_dropout_prob = _check_rate("attention_probs_dropout_prob", attention_probs_dropout_prob)
+        dev = torch.device(device) if device is not None else torch.device("cuda")
+        if dev.type != "cuda":
+            raise RuntimeError("proqa_amd.TrainableReader runs on MI355X only; there is no CPU path")
+        self.shared_norm, self.drop_early = bool(shared_norm), bool(drop_early)
+        self._dropout_seed = int(torch.initial_seed() if dropout_seed is None else dropout_seed) & 0xFFFFFFFFFFFFFFFF
+        self._dropout_call = 0
+        self._inference = None
+        # the towers of the retriever (and every check of the geometry and of the device)
+        retriever = TrainableRetriever(cfg, device=dev, hidden_dropout_prob=hidden_dropout_prob,
+                                       attention_probs_dropout_prob=attention_probs_dropout_prob,
+                                       dropout_seed=self._dropout_seed)
+        dev = retriever.device
+        self.config, self.device = cfg, dev
+        self._flat = {}
+        shapes = _parameter_shapes(cfg, tower_keys("bert", cfg.num_hidden_layers))
+        shapes["qa_outputs.weight"], shapes["qa_outputs.bias"] = (2, cfg.hidden_size), (2,)
+        g = torch.Generator().manual_seed(1)
+        for key, shape in shapes.items():      # transformers' initialisation: N(0, 0.02), LayerNorm (1, 0), biases 0
+            if key.endswith("LayerNorm.weight"):
+                value = torch.ones(shape)
+            elif key.endswith(".bias"):
+                value = torch.zeros(shape)
+            else:
+                value = 0.02 * torch.randn(shape, generator=g)
+            node = self
+            *path, leaf = key.split(".")
+            for name in path:
+                if name not in node._modules:
+                    node.add_module(name, _Node())
+                node = node._modules[name]
+            p = torch.nn.Parameter(value.to(dev))
+            node.register_parameter(leaf, p)
+            self._flat[key] = p
+            if key == "bert.pooler.dense.bias":      # the reference's order: bert, retriever, qa_outputs
+                self.add_module("retriever", retriever)
+
+    @classmethod
+    def from_args(cls, config, args, device=None, **kwargs):
+        """The reference's flags (qa/train_retrieve_qa.py): shared_norm, drop_early, qa_drop, separate, add_select and
+        retriever_path; BERT's two dropout rates come from kwargs (the reference takes them from the pretrained config)."""
+        model = cls(config, device, shared_norm=getattr(args, "shared_norm", False), drop_early=getattr(args, "drop_early", False),
+                    qa_drop=getattr(args, "qa_drop", 0.0), separate=getattr(args, "separate", False),
+                    add_select=getattr(args, "add_select", False), **kwargs)
+        if getattr(args, "retriever_path", ""):
+            model.load_pretrained_retriever(args.retriever_path)
+        return model
+
+    # -- reference-compatible surface -----------------------------------------------------
+    def state_dict_keys(self):
+        return state_dict_keys(self.config)
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        """Accepts the reference checkpoint layout: a 'module.' prefix (DataParallel) is stripped, `position_ids` buffers
+        of newer transformers are ignored."""
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+        self._inference = None
+        return super().load_state_dict(sd, strict=strict, **kwargs)
+
+    def load_pretrained_retriever(self, path_or_dict):
+        """BertRetrieveQA.load_pretrained_retriever: a retriever checkpoint (path or state dict) into `retriever`."""
+        sd = torch.load(path_or_dict, map_location="cpu") if isinstance(path_or_dict, str) else path_or_dict
+        self._inference = None
+        return self.retriever.load_state_dict(sd)
+
+    def freeze_c_encoder(self):
+        for name, p in self.retriever.named_parameters():
+            if name.startswith(("bert_c.", "proj_c.")):
+                p.requires_grad = False
+
+    def freeze_retriever(self):
+        for p in self.retriever.parameters():
+            p.requires_grad = False
+
+    def dropout_state(self):
+        """(seed, call) of the module's own masks; a train() forward with any rate above 0 advances `call` by
+        CALLS_PER_FORWARD = 3: the reader tower takes call, the question tower call + 1, the head (site 255) call + 2."""
+        return self._dropout_seed, self._dropout_call
+
+    def set_dropout_state(self, state):
+        seed, call = state
+        self._dropout_seed, self._dropout_call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFF
+
+    def _apply(self, fn, *args, **kwargs):
+        probe = fn(torch.empty(0, dtype=torch.float32, device=self.device))
+        if probe.device.type != "cuda":
+            raise RuntimeError("proqa_amd.TrainableReader runs on MI355X only; there is no CPU path")
+        if probe.dtype != torch.float32:
+            raise RuntimeError("the parameters are the fp32 masters; the module casts them to fp16 itself")
+        if probe.device != self.device:
+            self.device = probe.device
+        self._inference = None
+        return super()._apply(fn, *args, **kwargs)
+
+    # -- forward ----------------------------------------------------------------------------
+    def train(self, mode=True):
+        self._inference = None          # eval() takes its fp16 copy of the parameters again after any training
+        return super().train(mode)
+
+    def forward(self, net_input):
+        ids = net_input["input_ids"]
+        if not ids.is_cuda:
+            raise RuntimeError("TrainableReader expects CUDA tensors (the reference feeds move_to_cuda(batch))")
+        B, S = ids.shape
+        if B == 0:
+            raise ValueError("TrainableReader: an empty batch")
+        pmask = net_input["paragraph_mask"].to(torch.bool)
+        if pmask.shape != ids.shape:
+            raise ValueError(f"paragraph_mask {tuple(pmask.shape)} must have the shape of input_ids {tuple(ids.shape)}")
+        if not self.training:
+            return self._predict(net_input, pmask)
+        p_hid, p_att, p_qa = self.hidden_dropout_prob, self.attention_probs_dropout_prob, self.qa_drop
+        seed, call = self._dropout_seed, self._dropout_call
+        if p_hid > 0 or p_att > 0 or p_qa > 0:
+            self._dropout_call = (call + CALLS_PER_FORWARD) & 0xFFFFFF
+        geometry = {}
+
+        def paragraph_probe(lens):
+            geometry["para_offset"], bad = _paragraph_geometry(pmask, lens)
+            return bad, _PARAGRAPH_MESSAGE
+
+        hidden, cu, lens, max_len = run_tower(self._flat, "bert", self.config, ids, net_input["input_mask"],
+                                              type_ids=net_input["segment_ids"], drop=(p_hid, p_att, seed, call),
+                                              probe_extra=paragraph_probe)
+        # the question tower on row 0 alone: the reference encodes B identical rows and uses q[0]
+        q = run_tower(self.retriever._flat, "bert_q", self.config, net_input["input_ids_q"][:1], net_input["input_mask_q"][:1],
+                      proj="proj_q", drop=(p_hid, p_att, seed, (call + 1) & 0xFFFFFF))
+        return reader_loss(hidden, self._flat["qa_outputs.weight"], self._flat["qa_outputs.bias"], q, net_input["para_embed"],
+                           net_input["top5000_labels"], net_input["start_positions"], net_input["end_positions"],
+                           geometry["para_offset"], cu_seqlens=cu, shared_norm=self.shared_norm, early=not self.drop_early,
+                           qa_drop=p_qa, dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
+
+    @torch.no_grad()
+    def _predict(self, net_input, pmask):
+        """eval(): the reference's keys, computed by the inference class over an fp16 copy of the parameters (taken at the
+        first eval() forward after train() or a load), so that what is evaluated during training is what BertReader and
+        --do_predict serve.  start / end logits [B, L] fp16 carry the bits of proqa_reader_span_f16's logits, -inf outside
+        the paragraph mask; rank_logits [1, P] fp32.  One host round trip (the lengths and the checks of the masks)."""
+        if self._inference is None:
+            self._inference = BertReader(self.config, self.device).load_state_dict(
+                {k: p.detach() for k, p in self.named_parameters()})
+        reader = self._inference
+        dev = self.device
+        ids = net_input["input_ids"]
+        B, S = ids.shape
+        mask = net_input["input_mask"].to(torch.bool)
+        lens = mask.sum(dim=1).clamp_(min=1).to(torch.int32)
+        bad = (mask[:, 1:] & ~mask[:, :-1]).any() if S > 1 else torch.zeros((), dtype=torch.bool, device=mask.device)
+        po, bad_paragraph = _paragraph_geometry(pmask, lens)
+        probe = torch.cat([torch.stack([bad, bad_paragraph]).to(torch.int32), lens, po]).cpu().tolist()
+        if probe[0]:
+            raise ValueError("input_mask must be right-padded (a prefix of True per row), as re_collate produces")
+        if probe[1]:
+            raise ValueError(_PARAGRAPH_MESSAGE)
+        seq_lens, para_offset = probe[2:2 + B], probe[2 + B:]
+        hidden, _ = reader.hidden(ids, net_input["segment_ids"], seq_lens)
+        *_, logits = reader.span(hidden, seq_lens, para_offset, S, return_logits=True)
+        cu = torch.zeros(B, dtype=torch.int64, device=dev)
+        cu[1:] = torch.cumsum(lens[:-1], 0)
+        rows = (cu[:, None] + torch.arange(S, device=dev)[None]).clamp_(max=hidden.shape[0] - 1)
+        neg = torch.full((), float("-inf"), dtype=torch.float16, device=dev)
+        out = torch.where(pmask[..., None], logits[rows], neg)                    # [B, S, 2]; only masked rows are kept
+        q = reader.retriever.get_embed({"input_ids": net_input["input_ids_q"][:1], "input_mask": net_input["input_mask_q"][:1]},
+                                       True)["embed"]
+        rank = q[:1].float() @ net_input["para_embed"].to(device=dev, dtype=torch.float32).t()
+        return {"start_logits": out[..., 0].contiguous(), "end_logits": out[..., 1].contiguous(), "rank_logits": rank}
