@@ -654,6 +654,8 @@ int proqa_linear_wgrad_plan(int64_t T, int N, int K, int n_cus, int* splits, siz
  * Without clipping (max_grad_norm <= 0) and without a scale (PROQA_ADAMW_SCALE_NONE) launches 1 and 2 are skipped, the
  * state is not touched (state_dev, ws may be NULL) and the step number is the caller's host_step.
  * Results are bit-identical from run to run.
+ * proqa_adamw_step_half is the same step that also writes an fp16 working copy of every tensor it updates (mixed
+ * precision: the forward's weights without a cast per forward); proqa_cast_half_tensors writes the copies alone.
  * ---------------------------------------------------------------------------------- */
 #define PROQA_ADAMW_CHUNK 16384
 #define PROQA_ADAMW_SCALE_NONE 0      /* gradients are not scaled (the state's scale is 1) */
@@ -697,6 +699,21 @@ int proqa_adamw_state_init(void* state_dev, int64_t step, float loss_scale, int6
                            void* stream);
 int proqa_adamw_step(const proqa_adamw_tensor* table_dev, int n_tensors, const proqa_adamw_chunk* chunks_dev, int64_t n_chunks,
                      const proqa_adamw_hyper* hyper, void* state_dev, void* ws, size_t ws_bytes, void* stream);
+/* as proqa_adamw_step; half_dev: DEVICE array of n_tensors pointers (or NULL = proqa_adamw_step).  half_dev[t] != NULL:
+ * every element of tensor t that launch 3 writes is also written to half_dev[t][i] as fp16, round to nearest even from
+ * the fp32 value just stored in p (beyond +-65504 -> +-inf, as p.to(float16)).  Nothing else changes: p, m, v and the
+ * state get the bits proqa_adamw_step gives them.  A skipped step (found_inf) and a tensor with g = NULL write no copy
+ * (p did not change, so the copy is still p's).  A copy is [n] fp16, 2-byte aligned; one that is 8-byte aligned (with p,
+ * g, m, v 16-byte aligned) is written with 8-byte stores, any other with 2-byte stores.  Which loop computes p, m, v is
+ * decided by the alignment of p, g, m, v alone, as in proqa_adamw_step. */
+int proqa_adamw_step_half(const proqa_adamw_tensor* table_dev, void* const* half_dev, int n_tensors,
+                          const proqa_adamw_chunk* chunks_dev, int64_t n_chunks, const proqa_adamw_hyper* hyper, void* state_dev,
+                          void* ws, size_t ws_bytes, void* stream);
+/* half_dev[t][i] = (fp16) p[i] for every tensor with a copy: one launch over the same chunk map (only p and n of the
+ * table are read).  For construction, after load_state_dict, after any edit of the masters that did not go through the
+ * step. */
+int proqa_cast_half_tensors(const proqa_adamw_tensor* table_dev, void* const* half_dev, int n_tensors,
+                            const proqa_adamw_chunk* chunks_dev, int64_t n_chunks, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * k-means over passage embeddings.  Replaces faiss.Clustering.train + index.search(data, 1) of

@@ -221,6 +221,9 @@ SIGNATURES = {
     "proqa_adamw_state_init": (c_int, [c_void_p, c_int64, c_float, c_int64, c_int64, c_void_p]),
     "proqa_adamw_step": (c_int, [c_void_p, c_int, c_void_p, c_int64, ctypes.POINTER(AdamwHyper), c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
+    "proqa_adamw_step_half": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, ctypes.POINTER(AdamwHyper), c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "proqa_cast_half_tensors": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
     "proqa_kmeans_create": (c_int, [c_int, c_int64, c_int, ctypes.POINTER(c_void_p)]),
     "proqa_kmeans_free": (c_int, [c_void_p]),
     "proqa_kmeans_assign_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,

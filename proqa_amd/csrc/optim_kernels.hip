@@ -3,6 +3,8 @@
 //   adamw_grad_sumsq  one workgroup per fixed chunk of one tensor -> one fp32 partial per chunk (no atomics)
 //   adamw_finalize    one workgroup: norm, overflow flag, clip coefficient, step counter, bias corrections, loss scale
 //   adamw_update      the same chunks: g, p, m, v read once, p, m, v written once
+//   adamw_update_half the same, and every p written is also written as fp16 to the tensor's working copy (2 more bytes)
+//   adamw_cast_half   p -> the working copies alone, over the same chunk map (construction, load_state_dict)
 // The kernels are bound by HBM (32 bytes per parameter); the arithmetic is a dozen fp32 operations per element with
 // correctly rounded sqrt and division (hipcc's default for HIP).
 #include <cmath>
@@ -177,6 +179,8 @@ __device__ __forceinline__ void adamw_element(float g, float& p, float& m, float
   }
 }
 
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+
 template <bool kTorch>
 __device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                             float* __restrict__ v, int n, bool vec, const ElementCoefs& c) {
@@ -210,10 +214,38 @@ __device__ __forceinline__ void adamw_chunk(float* __restrict__ p, const float* 
   }
 }
 
-// state == nullptr: no skip rule, factor 1, bias corrections from the arguments
-__global__ __launch_bounds__(kThreads) void adamw_update(const proqa_adamw_tensor* __restrict__ table,
-                                                         const proqa_adamw_chunk* __restrict__ chunks,
-                                                         const AdamwState* __restrict__ state, UpdateArgs a) {
+// h[i] = (fp16) p[i] over one chunk: round to nearest even, beyond +-65504 -> +-inf (v_cvt_f16_f32 in the default mode,
+// what p.to(float16) does).  Thread-strided exactly as adamw_chunk, so that in the update a thread converts the elements
+// it has just written itself (its own stores: no barrier), still in the cache.  With p 16-byte and h 8-byte aligned a
+// lane packs four results into one 8-byte store; any other pair takes the scalar loop.
+__device__ __forceinline__ void cast_chunk(const float* p, _Float16* __restrict__ h, int n, bool vec) {
+  int done = 0;
+  if (vec) {
+    const int n4 = n >> 2;
+    const float4* p4 = reinterpret_cast<const float4*>(p);
+    half4* __restrict__ h4 = reinterpret_cast<half4*>(h);
+#pragma unroll 4
+    for (int i = threadIdx.x; i < n4; i += kThreads) {
+      const float4 pp = p4[i];
+      half4 hh;
+      hh.x = (_Float16)pp.x;
+      hh.y = (_Float16)pp.y;
+      hh.z = (_Float16)pp.z;
+      hh.w = (_Float16)pp.w;
+      h4[i] = hh;
+    }
+    done = n4 << 2;
+  }
+  for (int i = done + threadIdx.x; i < n; i += kThreads) h[i] = (_Float16)p[i];
+}
+
+// state == nullptr: no skip rule, factor 1, bias corrections from the arguments.  kHalf: half_table[t] (or NULL) is the
+// fp16 working copy of tensor t; a tensor without one runs exactly the code of the kHalf = false instantiation.
+template <bool kHalf>
+__device__ __forceinline__ void adamw_update_body(const proqa_adamw_tensor* __restrict__ table,
+                                                  const proqa_adamw_chunk* __restrict__ chunks,
+                                                  const AdamwState* __restrict__ state, UpdateArgs a,
+                                                  void* const* __restrict__ half_table) {
   double bc1 = a.bc1, bc2 = a.bc2;
   float factor = 1.0f;
   if (state != nullptr) {
@@ -248,10 +280,48 @@ __global__ __launch_bounds__(kThreads) void adamw_update(const proqa_adamw_tenso
   const float* g = static_cast<const float*>(t.g) + start;
   float* m = static_cast<float*>(t.m) + start;
   float* v = static_cast<float*>(t.v) + start;
+  // the loops of p, g, m, v are the same code with and without copies, chosen by THEIR alignment alone: the compiler
+  // contracts the 16-byte loop and the scalar loop differently, and a tensor keeps the bits proqa_adamw_step gives it
   if (a.torch_semantics)
     adamw_chunk<true>(p, g, m, v, n, vec, c);
   else
     adamw_chunk<false>(p, g, m, v, n, vec, c);
+  if (kHalf) {
+    _Float16* h = static_cast<_Float16*>(half_table[ck.tensor]);
+    if (h == nullptr) return;
+    // vec: a thread reads back the float4s it wrote; otherwise the scalars it wrote, or (p 16-byte aligned, the copy not
+    // 8-byte aligned) scalars of the float4s and of the tail that other threads wrote: those wait for the workgroup
+    const bool hvec = vec && (reinterpret_cast<uintptr_t>(h) & 7) == 0;
+    if (vec && !hvec) __syncthreads();
+    cast_chunk(p, h + start, n, hvec);       // (kChunk keeps the alignment of the tensor's start)
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void adamw_update(const proqa_adamw_tensor* __restrict__ table,
+                                                         const proqa_adamw_chunk* __restrict__ chunks,
+                                                         const AdamwState* __restrict__ state, UpdateArgs a) {
+  adamw_update_body<false>(table, chunks, state, a, nullptr);
+}
+
+__global__ __launch_bounds__(kThreads) void adamw_update_half(const proqa_adamw_tensor* __restrict__ table,
+                                                              const proqa_adamw_chunk* __restrict__ chunks,
+                                                              const AdamwState* __restrict__ state, UpdateArgs a,
+                                                              void* const* __restrict__ half_table) {
+  adamw_update_body<true>(table, chunks, state, a, half_table);
+}
+
+// half_table[t][i] = (fp16) p[i] over the same chunk map; a tensor without a copy is left alone
+__global__ __launch_bounds__(kThreads) void adamw_cast_half(const proqa_adamw_tensor* __restrict__ table,
+                                                            const proqa_adamw_chunk* __restrict__ chunks,
+                                                            void* const* __restrict__ half_table) {
+  const proqa_adamw_chunk ck = chunks[blockIdx.x];
+  _Float16* h = static_cast<_Float16*>(half_table[ck.tensor]);
+  if (h == nullptr) return;
+  const proqa_adamw_tensor t = table[ck.tensor];
+  const long long start = (long long)ck.index * kChunk;
+  const int n = (int)(t.n - start < kChunk ? t.n - start : kChunk);
+  const bool vec = (reinterpret_cast<uintptr_t>(t.p) & 15) == 0 && (reinterpret_cast<uintptr_t>(h) & 7) == 0;
+  cast_chunk(static_cast<const float*>(t.p) + start, h + start, n, vec);
 }
 
 __global__ void adamw_state_init(AdamwState* state, long long step, float loss_scale, long long clean_steps,
@@ -308,8 +378,9 @@ int proqa_adamw_state_init(void* state_dev, int64_t step, float loss_scale, int6
   return PROQA_OK;
 }
 
-int proqa_adamw_step(const proqa_adamw_tensor* table_dev, int n_tensors, const proqa_adamw_chunk* chunks_dev, int64_t n_chunks,
-                     const proqa_adamw_hyper* hyper, void* state_dev, void* ws, size_t ws_bytes, void* stream) {
+static int adamw_step_impl(const proqa_adamw_tensor* table_dev, void* const* half_dev, int n_tensors,
+                           const proqa_adamw_chunk* chunks_dev, int64_t n_chunks, const proqa_adamw_hyper* hyper, void* state_dev,
+                           void* ws, size_t ws_bytes, void* stream) {
   if (n_tensors < 0 || n_chunks < 0 || n_chunks > INT32_MAX)
     return fail(PROQA_EINVAL, "adamw_step: n_tensors=%d n_chunks=%lld", n_tensors, (long long)n_chunks);
   if (!hyper) return fail(PROQA_EINVAL, "adamw_step: NULL hyper-parameters");
@@ -361,7 +432,36 @@ int proqa_adamw_step(const proqa_adamw_tensor* table_dev, int n_tensors, const p
   ua.torch_semantics = h.torch_semantics ? 1 : 0;
   ua.bc1 = plain ? 1.0 - std::pow(h.beta1, (double)h.host_step) : 1.0;
   ua.bc2 = plain ? 1.0 - std::pow(h.beta2, (double)h.host_step) : 1.0;
-  hipLaunchKernelGGL(adamw_update, dim3((unsigned)n_chunks), dim3(kThreads), 0, st, table_dev, chunks_dev, state, ua);
+  if (half_dev)
+    hipLaunchKernelGGL(adamw_update_half, dim3((unsigned)n_chunks), dim3(kThreads), 0, st, table_dev, chunks_dev, state, ua,
+                       half_dev);
+  else
+    hipLaunchKernelGGL(adamw_update, dim3((unsigned)n_chunks), dim3(kThreads), 0, st, table_dev, chunks_dev, state, ua);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int proqa_adamw_step(const proqa_adamw_tensor* table_dev, int n_tensors, const proqa_adamw_chunk* chunks_dev, int64_t n_chunks,
+                     const proqa_adamw_hyper* hyper, void* state_dev, void* ws, size_t ws_bytes, void* stream) {
+  return adamw_step_impl(table_dev, nullptr, n_tensors, chunks_dev, n_chunks, hyper, state_dev, ws, ws_bytes, stream);
+}
+
+int proqa_adamw_step_half(const proqa_adamw_tensor* table_dev, void* const* half_dev, int n_tensors,
+                          const proqa_adamw_chunk* chunks_dev, int64_t n_chunks, const proqa_adamw_hyper* hyper, void* state_dev,
+                          void* ws, size_t ws_bytes, void* stream) {
+  return adamw_step_impl(table_dev, half_dev, n_tensors, chunks_dev, n_chunks, hyper, state_dev, ws, ws_bytes, stream);
+}
+
+int proqa_cast_half_tensors(const proqa_adamw_tensor* table_dev, void* const* half_dev, int n_tensors,
+                            const proqa_adamw_chunk* chunks_dev, int64_t n_chunks, void* stream) {
+  if (n_tensors < 0 || n_chunks < 0 || n_chunks > INT32_MAX)
+    return fail(PROQA_EINVAL, "cast_half_tensors: n_tensors=%d n_chunks=%lld", n_tensors, (long long)n_chunks);
+  if (!table_dev || !half_dev || (n_chunks > 0 && !chunks_dev))
+    return fail(PROQA_EINVAL, "cast_half_tensors: NULL tensor table, copy table or chunk map");
+  if (n_chunks > 0 && n_tensors == 0) return fail(PROQA_EINVAL, "cast_half_tensors: chunks without tensors");
+  if (n_chunks == 0) return PROQA_OK;
+  hipLaunchKernelGGL(adamw_cast_half, dim3((unsigned)n_chunks), dim3(kThreads), 0, as_stream(stream), table_dev, chunks_dev,
+                     half_dev);
   PROQA_LAUNCH_CHECK();
   return PROQA_OK;
 }

@@ -33,6 +33,47 @@ assert _TENSOR_DTYPE.itemsize == ctypes.sizeof(_lib.AdamwTensor)
 DYNAMIC_INIT_SCALE = 65536.0     # apex amp's dynamic scaler starts at 2**16
 
 
+def _chunk_map(lib, sizes):
+    """(device-ready int32 [n_chunks, 2] array, n_chunks) of proqa_adamw_chunk_map for these tensor sizes"""
+    n = len(sizes)
+    n_chunks = lib.proqa_adamw_chunk_map(sizes.ctypes.data, n, None, 0)
+    if n_chunks < 0:
+        _lib.check(int(n_chunks))
+    chunks = np.zeros((max(int(n_chunks), 1), 2), dtype=np.int32)
+    if lib.proqa_adamw_chunk_map(sizes.ctypes.data, n, chunks.ctypes.data, n_chunks) != n_chunks:
+        _lib.check(-1)
+    return chunks, int(n_chunks)
+
+
+def cast_half_tensors(masters, copies):
+    """copies[i][...] = masters[i].to(float16) for contiguous fp32 CUDA masters and contiguous fp16 copies of the same
+    numel on one device (None: no copy): one launch of proqa_cast_half_tensors, no host wait.  The tables are built and
+    uploaded per call: this is for construction and for re-casts after an edit, not for the training step."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    if len(masters) != len(copies) or not masters:
+        raise ValueError("cast_half_tensors takes as many copies as masters, at least one")
+    dev = masters[0].device
+    for p, h in zip(masters, copies):
+        if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+            raise ValueError("cast_half_tensors takes contiguous fp32 CUDA masters of one device")
+        if h is not None and (h.dtype != torch.float16 or not h.is_contiguous() or h.device != dev or h.numel() != p.numel()):
+            raise ValueError("a half copy must be a contiguous float16 tensor of its master's numel and device")
+    table = np.zeros(len(masters), dtype=_TENSOR_DTYPE)
+    table["p"] = [p.data_ptr() for p in masters]
+    table["n"] = [p.numel() for p in masters]
+    chunks, n_chunks = _chunk_map(lib, np.ascontiguousarray(table["n"]))
+    ptrs = np.array([0 if h is None else h.data_ptr() for h in copies], dtype=np.uint64)
+    with torch.cuda.device(dev):
+        table_dev = torch.from_numpy(table.view(np.uint8)).to(dev)
+        chunks_dev = torch.from_numpy(chunks).to(dev)
+        ptrs_dev = torch.from_numpy(ptrs.view(np.int64)).to(dev)
+        _lib.check(lib.proqa_cast_half_tensors(table_dev.data_ptr(), ptrs_dev.data_ptr(), len(masters), chunks_dev.data_ptr(),
+                                               n_chunks, _lib.current_stream_ptr()))
+        for t in (table_dev, chunks_dev, ptrs_dev):      # the launch reads them on this stream: no reuse before it ran
+            t.record_stream(torch.cuda.current_stream())
+
+
 class FusedAdamW(torch.optim.Optimizer):
     """AdamW over fp32 CUDA parameters, one fused step for all of them.
 
@@ -43,10 +84,15 @@ class FusedAdamW(torch.optim.Optimizer):
 
     `betas` and `eps` hold for the whole optimizer; `lr` and `weight_decay` are per group and read at every step, so
     schedulers that edit param_groups[i]["lr"] work.  Gradients may be reallocated, left None or accumulated over several
-    backward() calls between steps."""
+    backward() calls between steps.
+
+    half_copies: {parameter: fp16 tensor} (TrainableRetriever.half_weights() returns one).  The step that writes a
+    parameter writes its fp16 working copy in the same pass (proqa_adamw_step_half), so that no forward has to cast the
+    master again.  A copy has the parameter's numel, is contiguous fp16 on its device; the optimizer keeps it alive.  A
+    skipped step and a parameter without a gradient leave p, and therefore the copy, as they are."""
 
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, loss_scale=None,
-                 growth_interval=2000, torch_semantics=False, backoff_factor=0.5, growth_factor=2.0):
+                 growth_interval=2000, torch_semantics=False, backoff_factor=0.5, growth_factor=2.0, half_copies=None):
         if not lr >= 0.0:
             raise ValueError(f"invalid learning rate: {lr}")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
@@ -89,6 +135,7 @@ class FusedAdamW(torch.optim.Optimizer):
             if p.device != self._params[0].device:
                 raise ValueError("FusedAdamW takes parameters of one device")
         self._device = self._params[0].device
+        self._half = self._check_half_copies(half_copies)
         self._lib = _lib.load()
         _lib.require_gpu()
         for p in self._params:
@@ -98,13 +145,7 @@ class FusedAdamW(torch.optim.Optimizer):
         # the chunk map depends on the sizes only: built and uploaded once
         n = len(self._params)
         sizes = np.array([p.numel() for p in self._params], dtype=np.int64)
-        n_chunks = self._lib.proqa_adamw_chunk_map(sizes.ctypes.data, n, None, 0)
-        if n_chunks < 0:
-            _lib.check(int(n_chunks))
-        chunks = np.zeros((max(int(n_chunks), 1), 2), dtype=np.int32)
-        if self._lib.proqa_adamw_chunk_map(sizes.ctypes.data, n, chunks.ctypes.data, n_chunks) != n_chunks:
-            _lib.check(-1)
-        self._n_chunks = int(n_chunks)
+        chunks, self._n_chunks = _chunk_map(self._lib, sizes)
         self._chunks_dev = torch.from_numpy(chunks).to(self._device)
         self._table = np.zeros(n, dtype=_TENSOR_DTYPE)
         self._table["n"] = sizes
@@ -113,7 +154,40 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self._device)
         self._state_dev = torch.zeros(_lib.ADAMW_STATE_BYTES, dtype=torch.uint8, device=self._device)
         self._refresh_static_pointers()
+        # the copies never move: their pointer array is uploaded once
+        self._half_dev = None
+        if self._half is not None:
+            ptrs = np.array([0 if h is None else h.data_ptr() for h in self._half], dtype=np.uint64)
+            self._half_dev = torch.from_numpy(ptrs.view(np.int64)).to(self._device)
         self._init_device_state(0, init_scale, 0, 0)
+
+    def _check_half_copies(self, half_copies):
+        if half_copies is None:
+            return None
+        if not hasattr(half_copies, "items"):
+            raise ValueError("half_copies must be a {parameter: fp16 tensor} mapping")
+        by_id = {id(p): i for i, p in enumerate(self._params)}
+        copies = [None] * len(self._params)
+        for p, h in half_copies.items():
+            if id(p) not in by_id:
+                raise ValueError("half_copies names a tensor that is not a parameter of this optimizer")
+            if not isinstance(h, torch.Tensor) or h.dtype != torch.float16:
+                raise ValueError(f"a half copy must be a float16 tensor, got {getattr(h, 'dtype', type(h))}")
+            if h.numel() != p.numel():
+                raise ValueError(f"a half copy must have its parameter's {p.numel()} elements, got {h.numel()}")
+            if h.device != p.device:
+                raise ValueError(f"a half copy must live on its parameter's device {p.device}, got {h.device}")
+            if not h.is_contiguous():
+                raise ValueError("a half copy must be contiguous")
+            copies[by_id[id(p)]] = h
+        return copies if any(h is not None for h in copies) else None
+
+    @property
+    def half_copies(self):
+        """{parameter: fp16 working copy} the step writes, or {}"""
+        if self._half is None:
+            return {}
+        return {p: h for p, h in zip(self._params, self._half) if h is not None}
 
     # ---- device scalars ------------------------------------------------------------------------------------------
     def _view(self, offset, dtype):
@@ -198,9 +272,15 @@ class FusedAdamW(torch.optim.Optimizer):
             staged = torch.empty(table.nbytes, dtype=torch.uint8, pin_memory=True)
             staged.numpy()[:] = table.view(np.uint8)
             self._table_dev.copy_(staged, non_blocking=True)
-            _lib.check(self._lib.proqa_adamw_step(self._table_dev.data_ptr(), len(table), self._chunks_dev.data_ptr(),
-                                                  self._n_chunks, ctypes.byref(hyper), self._state_dev.data_ptr(),
-                                                  self._ws.data_ptr(), self._ws.numel(), _lib.current_stream_ptr()))
+            if self._half_dev is None:
+                _lib.check(self._lib.proqa_adamw_step(self._table_dev.data_ptr(), len(table), self._chunks_dev.data_ptr(),
+                                                      self._n_chunks, ctypes.byref(hyper), self._state_dev.data_ptr(),
+                                                      self._ws.data_ptr(), self._ws.numel(), _lib.current_stream_ptr()))
+            else:
+                _lib.check(self._lib.proqa_adamw_step_half(self._table_dev.data_ptr(), self._half_dev.data_ptr(), len(table),
+                                                           self._chunks_dev.data_ptr(), self._n_chunks, ctypes.byref(hyper),
+                                                           self._state_dev.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                                           _lib.current_stream_ptr()))
         if self._plain:
             self._plain_step += 1
         return loss

@@ -1,0 +1,364 @@
+"""`python pretrain_retriever.py --train_file train.txt --predict_file dev.txt --bert_model_name DIR ...`: retriever
+pre-training, the loop of retrieval/train_retriever.py:32-285 on one MI355X.
+
+Same flags (proqa_amd.config), same output directory and model_name, same accumulation rule, evaluation, checkpoints
+(checkpoint_{step}.pt, checkpoint_last.pt, checkpoint_best.pt: model.state_dict(), fp32, the reference's keys) and
+early-stopping counter.  The model is TrainableRetriever with the config's two dropout rates, the optimizer FusedAdamW
+with the reference's two parameter groups, a dynamic loss scale, the clip of --max_grad_norm inside the fused step, and
+the fp16 working copies of the weight matrices written by that step (TrainableRetriever.half_weights()).
+
+Intended differences: activations are fp16 with or without --fp16 and --fp16_opt_level is ignored;
+batches are tokenised in this process (ReTextView + ReTokenizeCollate), no worker is forked once the GPU is initialised;
+the host never reads a loss inside the loop: the per-micro-batch losses stay on the device and are read at evaluation
+and checkpoint time and at the end; the initial BERT weights come from the local --bert_model_name directory only (nothing
+is fetched); --local_rank, --no_cuda and a ';' list in --init_checkpoint are refused.  `train_retriever.py --do_train` keeps
+its refusal; `--do_predict` alone belongs to that command.
+"""
+import json
+import logging
+import os
+import random
+import time
+
+LAST_RUN_STATS = {}
+
+# test hook: parameters whose name contains one of these substrings are frozen (the word-embedding gradient is summed
+# with atomics, the module's one run-to-run difference; frozen, two runs of one seed log identical losses)
+FROZEN_PARAMETERS = ()
+
+logger = logging.getLogger(__name__)
+
+
+# ---- pure pieces (no GPU) ------------------------------------------------------------------------------------------------
+
+def model_name(args):
+    """the reference's run name (train_retriever.py:44-45), from the flags BEFORE train_batch_size is divided"""
+    data_name = args.train_file.split("/")[-1].split("-")[0]
+    return (f"{data_name}-seed{args.seed}-bsz{args.train_batch_size}-fp16{args.fp16}-{args.prefix}-lr{args.learning_rate}-"
+            f"{args.bert_model_name}-filter{args.filter}")
+
+
+def check_args(args):
+    """The refusals, and --do_train implied.  Raises what the reference raises where it raises."""
+    if args.accumulate_gradients < 1:
+        raise ValueError("Invalid accumulate_gradients parameter: {}, should be >= 1".format(args.accumulate_gradients))
+    if args.do_predict and not args.do_train:
+        raise SystemExit("pretrain_retriever.py: --do_predict alone is the dev evaluation of a checkpoint: run "
+                         "train_retriever.py --do_predict --init_checkpoint ...")
+    args.do_train = True
+    if not args.train_file:
+        raise ValueError("If `do_train` is True, then `train_file` must be specified.")
+    if not args.predict_file:
+        raise ValueError("If `do_train` is True, then `predict_file` must be specified.")
+    if args.local_rank != -1:
+        raise SystemExit("pretrain_retriever.py: --local_rank (DistributedDataParallel) is not supported: one GPU per run")
+    if args.no_cuda:
+        raise SystemExit("pretrain_retriever.py: --no_cuda: proqa_amd has no CPU path")
+    if ";" in args.init_checkpoint:
+        raise SystemExit("pretrain_retriever.py: a ';' list in --init_checkpoint (the reference's ensemble path) is not "
+                         "supported; training starts from one checkpoint")
+    if args.gradient_accumulation_steps < 1:
+        raise ValueError(f"Invalid gradient_accumulation_steps parameter: {args.gradient_accumulation_steps}, should be >= 1")
+    if int(args.train_batch_size / args.accumulate_gradients) < 1:
+        raise ValueError(f"--train_batch_size {args.train_batch_size} / --accumulate_gradients {args.accumulate_gradients} "
+                         "leaves no example per batch")
+    return args
+
+
+def batch_slices(order, batch_size):
+    """What DataLoader(batch_size=..., sampler=...) yields: consecutive slices of the sampler's order, the short last one
+    kept."""
+    order = list(order)
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+
+def is_update_step(batch_step, gradient_accumulation_steps):
+    """The reference's rule (train_retriever.py:222), batch_step counted from 1 (it is incremented before the forward):
+    with G = 2 the first update follows ONE micro-batch (batch_step 1), every later one two."""
+    return (batch_step + 1) % gradient_accumulation_steps == 0
+
+
+def update_schedule(n_batches, gradient_accumulation_steps):
+    """[batch_step of every optimizer step] over n_batches micro-batches"""
+    return [b for b in range(1, n_batches + 1) if is_update_step(b, gradient_accumulation_steps)]
+
+
+def load_bert_weights(model_dir):
+    """{bare BertModel key: tensor} from pytorch_model.bin (or model.safetensors if that package imports) of a LOCAL model
+    directory; a 'bert.' prefix (BertForPreTraining checkpoints) is stripped, heads that are not BertModel's are dropped.
+    SystemExit when the directory holds no weights: nothing is ever fetched."""
+    import torch
+    path_bin = os.path.join(model_dir, "pytorch_model.bin")
+    path_st = os.path.join(model_dir, "model.safetensors")
+    sd = None
+    if os.path.isfile(path_bin):
+        sd = torch.load(path_bin, map_location="cpu")
+    elif os.path.isfile(path_st):
+        try:
+            from safetensors.torch import load_file
+        except ImportError:
+            load_file = None
+        if load_file is not None:
+            sd = load_file(path_st)
+    if sd is None:
+        raise SystemExit(f"pretrain_retriever.py: no BERT weights in {model_dir!r} (pytorch_model.bin, or model.safetensors "
+                         "with the safetensors package) and no --init_checkpoint: nothing to start from; weights are "
+                         "never downloaded")
+    out = {}
+    for k, v in sd.items():
+        if k.startswith("bert."):
+            k = k[len("bert."):]
+        if k.startswith(("embeddings.", "encoder.", "pooler.")) and not k.endswith("position_ids"):
+            out[k] = v
+    return out
+
+
+def initial_state_dict(cfg, bert_weights, seed):
+    """The reference's untrained retriever: both towers are the pre-trained BertModel, the projections nn.Linear's
+    initialisation (under `seed`)."""
+    import torch
+    from ._lib import EMBED_DIM
+    from .retriever import tower_keys
+    sd = {}
+    for tower in ("bert_q", "bert_c"):
+        for key in tower_keys(tower, cfg.num_hidden_layers):
+            bare = key[len(tower) + 1:]
+            if bare not in bert_weights:
+                raise SystemExit(f"pretrain_retriever.py: the BERT weights lack {bare!r}")
+            sd[key] = bert_weights[bare].detach().to(torch.float32).clone()
+    torch.manual_seed(seed)
+    for proj in ("proj_q", "proj_c"):
+        lin = torch.nn.Linear(cfg.hidden_size, EMBED_DIM)
+        sd[f"{proj}.weight"], sd[f"{proj}.bias"] = lin.weight.detach().clone(), lin.bias.detach().clone()
+    return sd
+
+
+def load_model_config(name_or_dir):
+    """(config namespace, hidden_dropout_prob, attention_probs_dropout_prob) of a model directory's config.json (else of
+    transformers' local files); the two rates default to BertConfig's 0.1"""
+    from .retriever import config_from_dict
+    cfg_path = os.path.join(name_or_dir, "config.json")
+    if os.path.isfile(cfg_path):
+        with open(cfg_path) as f:
+            d = json.load(f)
+    else:
+        from transformers import BertConfig
+        d = BertConfig.from_pretrained(name_or_dir, local_files_only=True).to_dict()
+    return config_from_dict(d), float(d.get("hidden_dropout_prob", 0.1)), float(d.get("attention_probs_dropout_prob", 0.1))
+
+
+def parameter_groups(model, weight_decay):
+    """The reference's two groups (train_retriever.py:140-146), without the parameters that do not train"""
+    no_decay = ["bias", "LayerNorm.weight"]
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    return [{"params": [p for n, p in named if not any(nd in n for nd in no_decay)], "weight_decay": weight_decay},
+            {"params": [p for n, p in named if any(nd in n for nd in no_decay)], "weight_decay": 0.0}]
+
+
+# ---- the command -------------------------------------------------------------------------------------------------------------
+
+class _Losses:
+    """The reference's AverageMeter and its per-batch record without a host read per batch: device scalars queue up and
+    are read together at flush()."""
+
+    def __init__(self):
+        self.pending, self.pending_steps = [], []
+        self.values, self.steps = [], []
+
+    def add(self, loss, global_step):
+        self.pending.append(loss)
+        self.pending_steps.append(global_step)
+
+    def flush(self, tb=None):
+        if self.pending:
+            import torch
+            new = torch.stack(self.pending).cpu().tolist()
+            for value, step in zip(new, self.pending_steps):
+                self.values.append(value)
+                self.steps.append(step)
+                if tb is not None:
+                    tb.add_scalar("batch_train_loss", value, step)
+                    tb.add_scalar("smoothed_train_loss", sum(self.values) / len(self.values), step)
+            self.pending, self.pending_steps = [], []
+
+    @property
+    def avg(self):
+        return sum(self.values) / len(self.values) if self.values else 0.0
+
+
+def _tensorboard(log_dir):
+    try:
+        from torch.utils.tensorboard import SummaryWriter
+    except Exception:
+        return None
+    return SummaryWriter(log_dir)
+
+
+def main(argv=None):
+    from .config import get_args
+    args = check_args(get_args(argv))
+    import numpy as np
+    import torch
+    from transformers import BertTokenizer
+    from .datasets import ClusterDataset, ClusterSampler, ReDataset, ReSampler, ReTextView, ReTokenizeCollate
+    from .get_embed import usable_cpus
+    from .optim import FusedAdamW
+    from .train_retriever import predict
+    from .trainable import TrainableRetriever, inbatch_loss
+    from .utils import move_to_cuda
+
+    name = model_name(args)
+    tb_dir = os.path.join(args.output_dir, "tflogs", name)
+    args.output_dir = os.path.join(args.output_dir, name)
+    if os.path.exists(args.output_dir) and os.listdir(args.output_dir):
+        print(f"output directory {args.output_dir} already exists and is not empty.")
+    os.makedirs(args.output_dir, exist_ok=True)
+    handlers = [logging.FileHandler(os.path.join(args.output_dir, "log.txt")), logging.StreamHandler()]
+    for h in handlers:
+        h.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S"))
+        logger.addHandler(h)
+    logger.setLevel(logging.INFO)
+    logger.propagate = False
+    tb = None
+    try:
+        logger.info(args)
+        if not torch.cuda.is_available():
+            raise RuntimeError("no MI355X visible: retriever training has no CPU fallback")
+        args.train_batch_size = int(args.train_batch_size / args.accumulate_gradients)
+        random.seed(args.seed)
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
+        torch.cuda.manual_seed_all(args.seed)
+
+        cfg, p_hidden, p_attention = load_model_config(args.bert_model_name)
+        if args.max_seq_length > cfg.max_position_embeddings:
+            raise ValueError("Cannot use sequence length %d because the BERT model was only trained up to sequence length %d"
+                             % (args.max_seq_length, cfg.max_position_embeddings))
+        tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
+
+        # the data first: ClusterDataset reads its folder with a process pool, and nothing forks once the GPU is in use
+        # (the samplers draw from `random` / `np.random`, the model's initialisation from torch: the order does not matter)
+        eval_dataset = ReDataset(tokenizer, args.predict_file, args.max_query_length, args.max_seq_length)
+        if len(eval_dataset) == 0:
+            raise ValueError(f"{args.predict_file} holds no example")
+        if not os.path.isdir(args.train_file):
+            train_dataset = ReDataset(tokenizer, args.train_file, args.max_query_length, args.max_seq_length, args.filter)
+            sampler = ReSampler(train_dataset)
+        else:
+            train_dataset = ClusterDataset(tokenizer, args.train_file, args.max_query_length, args.max_seq_length, args.filter)
+            sampler = ClusterSampler(train_dataset, args.train_batch_size)
+        if len(train_dataset) == 0:
+            raise ValueError(f"{args.train_file} holds no example")
+        train_batches = batch_slices(sampler, args.train_batch_size)      # the same order every epoch, as the reference's
+        workers = max(0, min(args.eval_workers, usable_cpus() - 2))
+        collate = ReTokenizeCollate(tokenizer, args.max_query_length, args.max_seq_length, native_threads=workers)
+        train_texts, eval_texts = ReTextView(train_dataset), ReTextView(eval_dataset)
+
+        def tensors(texts, indices):
+            batch = collate([texts[i] for i in indices])
+            batch.pop("seq_lens_q", None)       # host lists the inference class takes; the module reads the masks
+            batch.pop("seq_lens_c", None)
+            return batch
+
+        def eval_dataloader():
+            n = len(eval_texts)
+            return (tensors(eval_texts, range(b0, min(b0 + args.predict_batch_size, n)))
+                    for b0 in range(0, n, args.predict_batch_size))
+        logger.info(f"Num of dev batches: {-(-len(eval_texts) // args.predict_batch_size)}")
+
+        device = torch.device("cuda", torch.cuda.current_device())
+        logger.info("device %s n_gpu %d distributed training %r", device, 1, False)
+        model = TrainableRetriever(cfg, device=device, hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention,
+                                   dropout_seed=args.seed)
+        if args.init_checkpoint != "":
+            state = torch.load(args.init_checkpoint, map_location="cpu")
+        else:
+            state = initial_state_dict(cfg, load_bert_weights(args.bert_model_name), args.seed)
+        model.load_state_dict(state)
+        for n, p in model.named_parameters():
+            if any(s in n for s in FROZEN_PARAMETERS):
+                p.requires_grad_(False)
+        print(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+
+        optimizer = FusedAdamW(parameter_groups(model, args.weight_decay), lr=args.learning_rate, eps=args.adam_epsilon,
+                               max_grad_norm=args.max_grad_norm, loss_scale="dynamic", half_copies=model.half_weights())
+        logger.info("activations and their gradients are fp16 with or without --fp16 (fp32 masters, dynamic loss scale); "
+                    "--fp16_opt_level is ignored")
+        tb = _tensorboard(tb_dir)
+
+        global_step = 0      # gradient update step
+        batch_step = 0       # forward batch count
+        best_acc = 0
+        wait_step = 0
+        stop_training = False
+        meter = _Losses()
+        evals = []
+        G = args.gradient_accumulation_steps
+        model.train()
+        logger.info("Start training....")
+        t_start = time.perf_counter()
+        for epoch in range(int(args.num_train_epochs)):
+            for indices in train_batches:
+                batch_step += 1
+                batch = move_to_cuda(tensors(train_texts, indices), device)
+                outputs = model(batch)
+                loss = inbatch_loss(outputs["q"], outputs["c"])
+                if G > 1:
+                    loss = loss / G
+                optimizer.scale_loss(loss).backward()
+                meter.add(loss.detach(), global_step)
+
+                if is_update_step(batch_step, G):
+                    optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
+                    model.zero_grad()
+                    global_step += 1
+
+                    if global_step % args.save_checkpoints_steps == 0:
+                        meter.flush(tb)
+                        torch.save(model.state_dict(), os.path.join(args.output_dir, f"checkpoint_{global_step}.pt"))
+
+                    if global_step % args.eval_period == 0:
+                        meter.flush(tb)
+                        acc = predict(args, model, eval_dataloader(), device, fp16=args.efficient_eval)
+                        logger.info("Step %d Train loss %.2f Acc %.2f on epoch=%d" % (global_step, meter.avg, acc * 100, epoch))
+                        evals.append({"step": global_step, "acc": acc, "train_loss_avg": meter.avg})
+                        if tb is not None:
+                            tb.add_scalar("dev_acc", acc * 100, global_step)
+                        # save most recent model
+                        torch.save(model.state_dict(), os.path.join(args.output_dir, "checkpoint_last.pt"))
+                        if best_acc < acc:
+                            logger.info("Saving model with best  Acc %.2f -> Acc %.2f on epoch=%d" % (best_acc * 100, acc * 100, epoch))
+                            torch.save(model.state_dict(), os.path.join(args.output_dir, "checkpoint_best.pt"))
+                            best_acc = acc
+                            wait_step = 0
+                            stop_training = False
+                        else:
+                            wait_step += 1
+                            if wait_step == args.wait_step:
+                                stop_training = True
+            if stop_training:
+                break
+        meter.flush(tb)
+        fused = optimizer.state_dict()["fused"]
+        seconds = time.perf_counter() - t_start
+        logger.info("Training finished!")
+
+        stats = LAST_RUN_STATS
+        stats.clear()
+        stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
+                     skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"], seconds=seconds,
+                     best_acc=best_acc, output_dir=args.output_dir)
+        if os.environ.get("PROQA_STATS_JSON"):
+            with open(os.environ["PROQA_STATS_JSON"], "w") as f:
+                json.dump(stats, f)
+        return stats
+    finally:
+        if tb is not None:
+            tb.close()
+        for h in handlers:
+            logger.removeHandler(h)
+            h.close()
+
+
+if __name__ == "__main__":
+    main()

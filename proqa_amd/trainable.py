@@ -21,7 +21,7 @@ torch computes.  Biases of the encoder layers are NOT passed to linear: the fuse
 gradients.
 
 Precision: fp32 master parameters, cast to fp16 once per step and tower (apex O1 semantics; the reference trains with
---fp16); activations and their gradients fp16, every sum inside a kernel fp32, every parameter gradient fp32 (weight
+--fp16), or, after half_weights(), weight matrices whose fp16 working copies the optimizer step writes with the masters; activations and their gradients fp16, every sum inside a kernel fp32, every parameter gradient fp32 (weight
 matrices, vectors and embedding tables alike).  Use a loss scale (a fixed one or torch.amp.GradScaler): every backward
 operator is linear in its incoming gradient and passes inf / NaN through.
 
@@ -454,15 +454,18 @@ class _BiasResidualLayerNorm(torch.autograd.Function):
 class _Linear(torch.autograd.Function):
     """y = x [w_0; w_1; ...]^T (+ bias) over the fp32 masters w_i [N_i, K]: the Q / K / V layer is three masters and one
     product.  The forward and dx = dy w go through torch (rocBLAS / hipBLASLt); the weight gradient is linear_wgrad, one
-    call into an fp32 [sum N_i, K] buffer whose row slices are the gradients of the masters."""
+    call into an fp32 [sum N_i, K] buffer whose row slices are the gradients of the masters.
+    w16: the fp16 working copy [sum N_i, K] that the optimizer step keeps current (half_weights), taken as it lies, or None:
+    the masters are cast here, one copy_ per master."""
 
     @staticmethod
-    def forward(ctx, x, bias, *weights):
-        w16 = torch.empty((sum(w.shape[0] for w in weights), weights[0].shape[1]), dtype=torch.float16, device=x.device)
-        r = 0
-        for w in weights:
-            w16[r:r + w.shape[0]].copy_(w)         # the cast, straight into its row slice
-            r += w.shape[0]
+    def forward(ctx, x, bias, w16, *weights):
+        if w16 is None:
+            w16 = torch.empty((sum(w.shape[0] for w in weights), weights[0].shape[1]), dtype=torch.float16, device=x.device)
+            r = 0
+            for w in weights:
+                w16[r:r + w.shape[0]].copy_(w)         # the cast, straight into its row slice
+                r += w.shape[0]
         ctx.save_for_backward(x, w16)
         ctx.rows = [w.shape[0] for w in weights]
         return F.linear(x, w16, bias.half() if bias is not None else None)
@@ -476,14 +479,14 @@ class _Linear(torch.autograd.Function):
         dx = dy @ w16 if need[0] else None
         dbias = colsum(dy) if need[1] else None
         dws = [None] * len(ctx.rows)
-        if any(need[2:]):
+        if any(need[3:]):
             dw = linear_wgrad(dy, x)
             r = 0
             for i, n in enumerate(ctx.rows):
-                if need[2 + i]:
+                if need[3 + i]:
                     dws[i] = dw[r:r + n]
                 r += n
-        return (dx, dbias, *dws)
+        return (dx, dbias, None, *dws)
 
 
 class _InBatchLoss(torch.autograd.Function):
@@ -511,12 +514,15 @@ def inbatch_loss(q, c, target=None):
 
 # ---- one tower pass, shared by TrainableRetriever and TrainableReader ----------------------------------------------------------
 
-def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None, drop=(0.0, 0.0, 0, 0), probe_extra=None):
+def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None, drop=(0.0, 0.0, 0, 0), probe_extra=None,
+              half=None):
     """One BERT tower with gradients.  P: {key: fp32 master}; `tower` the key prefix of the tower's parameters (bert_q,
     bert_c, bert).  input_ids / input_mask [B, S] right-padded CUDA tensors, B >= 1; type_ids [B, S] or None (every token
     of type 0: the untyped embedding operator).  drop = (hidden rate, attention rate, seed, call) of this pass; a rate of 0
     runs the dropout-free operator.  probe_extra(lens) -> (device bool scalar, message): one more condition for the pass's
-    single host round trip to check (ValueError(message) when it holds).
+    single host round trip to check (ValueError(message) when it holds).  half: {tuple of weight keys: fp16 working copy
+    of those masters stacked by rows} for EVERY product of the pass (HalfWeights.views), or None: each product casts its
+    masters itself.
     -> proj given (the key prefix of the projection): the [B, 128] fp16 embedding of pooler + projection;
        proj None: (h, cu_seqlens, lens, max_len), the packed last hidden state [T, H] fp16 and its geometry."""
     B, S = input_ids.shape
@@ -547,6 +553,9 @@ def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None,
     hid = (lambda site: (p_hid, seed, site, call)) if p_hid > 0 else (lambda site: None)
     att = (lambda site: (p_att, seed, site, call)) if p_att > 0 else (lambda site: None)
 
+    def linear(x, bias, *keys):
+        return _Linear.apply(x, bias, half[keys] if half is not None else None, *(P[k] for k in keys))
+
     e = f"{tower}.embeddings"
     tables = (P[f"{e}.word_embeddings.weight"], P[f"{e}.position_embeddings.weight"], P[f"{e}.token_type_embeddings.weight"],
               P[f"{e}.LayerNorm.weight"], P[f"{e}.LayerNorm.bias"])
@@ -559,21 +568,76 @@ def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None,
     for i in range(cfg.num_hidden_layers):
         p = f"{tower}.encoder.layer.{i}"
         qkv_b = torch.cat([P[f"{p}.attention.self.{n}.bias"] for n in ("query", "key", "value")], 0)
-        qkv = _Linear.apply(h, None, *(P[f"{p}.attention.self.{n}.weight"] for n in ("query", "key", "value")))
+        qkv = linear(h, None, *(f"{p}.attention.self.{n}.weight" for n in ("query", "key", "value")))
         ctx = _Attention.apply(qkv, qkv_b, cu, B, max_len, n_heads, att(1 + 3 * i))
-        a = _Linear.apply(ctx, None, P[f"{p}.attention.output.dense.weight"])
+        a = linear(ctx, None, f"{p}.attention.output.dense.weight")
         h1 = _BiasResidualLayerNorm.apply(a, P[f"{p}.attention.output.dense.bias"], h,
                                           P[f"{p}.attention.output.LayerNorm.weight"],
                                           P[f"{p}.attention.output.LayerNorm.bias"], eps, hid(2 + 3 * i))
-        f = _BiasGelu.apply(_Linear.apply(h1, None, P[f"{p}.intermediate.dense.weight"]), P[f"{p}.intermediate.dense.bias"])
-        o = _Linear.apply(f, None, P[f"{p}.output.dense.weight"])
+        f = _BiasGelu.apply(linear(h1, None, f"{p}.intermediate.dense.weight"), P[f"{p}.intermediate.dense.bias"])
+        o = linear(f, None, f"{p}.output.dense.weight")
         h = _BiasResidualLayerNorm.apply(o, P[f"{p}.output.dense.bias"], h1, P[f"{p}.output.LayerNorm.weight"],
                                          P[f"{p}.output.LayerNorm.bias"], eps, hid(3 + 3 * i))
     if proj is None:
         return h, cu, lens, max_len
     cls = h.index_select(0, cu[:-1].to(torch.int64))
-    pooled = torch.tanh(_Linear.apply(cls, P[f"{tower}.pooler.dense.bias"], P[f"{tower}.pooler.dense.weight"]))
-    return _Linear.apply(pooled, P[f"{proj}.bias"], P[f"{proj}.weight"])
+    pooled = torch.tanh(linear(cls, P[f"{tower}.pooler.dense.bias"], f"{tower}.pooler.dense.weight"))
+    return linear(pooled, P[f"{proj}.bias"], f"{proj}.weight")
+
+
+# ---- fp16 working copies of the weight matrices, kept current by the optimizer step ------------------------------------------
+
+_COPY_ALIGN = 128        # elements: every copy starts on a 256-byte boundary of the flat buffer (16 bytes are required)
+
+
+def linear_groups(tower, cfg, proj=None):
+    """The weight keys of each product of run_tower(tower, proj=proj), in the pass's order: the Q / K / V masters of a
+    layer form one group (one product over their rows), every other matrix its own."""
+    groups = []
+    for i in range(cfg.num_hidden_layers):
+        p = f"{tower}.encoder.layer.{i}"
+        groups.append(tuple(f"{p}.attention.self.{n}.weight" for n in ("query", "key", "value")))
+        groups += [(f"{p}.attention.output.dense.weight",), (f"{p}.intermediate.dense.weight",), (f"{p}.output.dense.weight",)]
+    if proj is not None:
+        groups += [(f"{tower}.pooler.dense.weight",), (f"{proj}.weight",)]
+    return groups
+
+
+class HalfWeights:
+    """One flat fp16 buffer with a working copy of every weight matrix of `groups` (linear_groups): the masters of a group
+    lie adjacent in the group's order, so that the group's product takes one [sum N_i, K] view.
+    .views   {group: fp16 [sum N_i, K] view}: what run_tower(half=...) takes
+    .copies  {parameter: fp16 view of its shape}: what FusedAdamW(half_copies=...) takes
+    The buffer is filled by refresh() (proqa_cast_half_tensors) and from then on by the optimizer step."""
+
+    def __init__(self, P, groups):
+        self._params = [P[k] for group in groups for k in group]
+        dev = self._params[0].device
+        offsets, at = [], 0
+        for group in groups:
+            at = -(-at // _COPY_ALIGN) * _COPY_ALIGN
+            offsets.append(at)
+            at += sum(P[k].numel() for k in group)
+        self.flat = torch.empty(at, dtype=torch.float16, device=dev)
+        self.views, self.copies = {}, {}
+        for group, start in zip(groups, offsets):
+            K = P[group[0]].shape[1]
+            rows = sum(P[k].shape[0] for k in group)
+            self.views[group] = self.flat[start:start + rows * K].view(rows, K)
+            for k in group:
+                self.copies[P[k]] = self.flat[start:start + P[k].numel()].view(P[k].shape)
+                start += P[k].numel()
+        self._pointers = [p.data_ptr() for p in self._params]
+        self.refresh()
+
+    def moved(self):
+        """True when a master no longer lies where its copy was made from (an _apply that moved storage)"""
+        return [p.data_ptr() for p in self._params] != self._pointers
+
+    def refresh(self):
+        """copy = (fp16) master for every matrix: one launch"""
+        from .optim import cast_half_tensors
+        cast_half_tensors(self._params, [self.copies[p] for p in self._params])
 
 
 # ---- the module -----------------------------------------------------------------------------------------------------------
@@ -647,6 +711,7 @@ class TrainableRetriever(torch.nn.Module):
         # the masks' (seed, call): plain Python numbers, not part of state_dict() (which keeps the reference's keys)
         self._dropout_seed = int(torch.initial_seed() if dropout_seed is None else dropout_seed) & 0xFFFFFFFFFFFFFFFF
         self._dropout_call = 0
+        self._half = None           # HalfWeights once half_weights() was called
         self._flat = {}
         g = torch.Generator().manual_seed(0)
         for key, shape in _parameter_shapes(cfg).items():      # transformers' initialisation: N(0, 0.02), LayerNorm (1, 0), biases 0
@@ -675,7 +740,27 @@ class TrainableRetriever(torch.nn.Module):
         of newer transformers are ignored."""
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
-        return super().load_state_dict(sd, strict=strict, **kwargs)
+        result = super().load_state_dict(sd, strict=strict, **kwargs)
+        self.refresh_half_weights()
+        return result
+
+    def half_weights(self):
+        """Switch the module to fp16 working copies of its weight matrices and return {parameter: fp16 view} for
+        FusedAdamW(half_copies=...), whose step then writes each copy with the master.  One flat buffer, every copy
+        16-byte aligned, a layer's query / key / value copies adjacent; _Linear takes the views as they lie, so a
+        forward casts no matrix.  The results are bit-identical to the per-forward casts.  The copies follow the masters
+        through the optimizer step and load_state_dict; after any other edit of a master call refresh_half_weights()."""
+        if self._half is None or self._half.moved():
+            groups = (linear_groups("bert_q", self.config, "proj_q") + linear_groups("bert_c", self.config, "proj_c"))
+            self._half = HalfWeights(self._flat, groups)
+        else:
+            self._half.refresh()
+        return dict(self._half.copies)
+
+    def refresh_half_weights(self):
+        """Cast every master matrix into its working copy again (one launch); nothing to do without half_weights()."""
+        if self._half is not None:
+            self._half.refresh()
 
     def dropout_state(self):
         """(seed, call): what, with the rates, determines every mask of the next tower pass; `call` advances once per
@@ -694,7 +779,13 @@ class TrainableRetriever(torch.nn.Module):
             raise RuntimeError("the parameters are the fp32 masters; the module casts them to fp16 itself")
         if probe.device != self.device:
             self.device = probe.device
-        return super()._apply(fn, *args, **kwargs)
+        result = super()._apply(fn, *args, **kwargs)
+        if self._half is not None:
+            if self._half.moved():
+                self._half = None        # the copies belong to storage that is gone: back to the per-forward casts
+            else:
+                self._half.refresh()     # fn may have edited the masters in place
+        return result
 
     # -- forward ----------------------------------------------------------------------------
     def forward(self, batch):
@@ -717,4 +808,5 @@ class TrainableRetriever(torch.nn.Module):
         seed, call = self._dropout_seed, self._dropout_call
         if p_hid > 0 or p_att > 0:
             self._dropout_call = (call + 1) & 0xFFFFFF
-        return run_tower(self._flat, tower, self.config, input_ids, input_mask, proj=proj, drop=(p_hid, p_att, seed, call))
+        return run_tower(self._flat, tower, self.config, input_ids, input_mask, proj=proj, drop=(p_hid, p_att, seed, call),
+                         half=self._half.views if self._half is not None else None)

@@ -2,6 +2,7 @@
 batches at the reference's --train_batch_size 640 (retrieval/train_retriever_single.sh) and at 64.
 
     python scripts/dev_train_step_timing.py [--out DIR] [--batches 640,64] [--steps 5] [--skip-trace] [--dropout P]
+                                            [--half-weights [--accumulate N]]
 
 Three measurements, each in a fresh child process of this script:
   events   forward + backward + zero_grad per step between CUDA events, median of --steps after 2 warm-up steps;
@@ -14,6 +15,11 @@ Three measurements, each in a fresh child process of this script:
 dropout and a step without (the rates set to 0: the dropout-free kernels) take turns in one process, each --steps times
 after the warm-up.  `events` adds step_ms_median_dropout and dropout_step_ratio; `trace` adds dropout_kernel_ratios: the
 time of each dropout kernel over its dropout-free counterpart (the three attention kernels and the LayerNorm pair).
+--half-weights (what the fp16 working copies are worth): the step becomes --accumulate N micro-batches of forward +
+backward, one FusedAdamW step (clip 2.0, dynamic scale) and zero_grad.  Two modules of the same weights take turns in one
+process, one casting its masters in every forward, the other with half_weights() and FusedAdamW(half_copies=...): `events`
+gives step_ms_median_casts / _copies and their ratio; `trace` runs each variant in a traced process of its own and gives
+launches per micro-batch, the adamw_update time and the time of the cast kernels.  The torch baseline is skipped.
 Questions have 5-30 tokens (--max_query_length 30), paragraphs 60-220.  Prints one JSON line.
 """
 import argparse
@@ -127,9 +133,54 @@ def child(mode, batches, steps, dropout=0.0):
     print("RESULT " + json.dumps(result))
 
 
-def run_child(mode, args, prefix=()):
+def child_half(mode, batches, steps, accumulate, variant):
+    """--half-weights: optimizer steps of `accumulate` micro-batches, per-forward casts and working copies taking turns
+    (variant None) or one of them alone (a traced run)"""
+    sys.path.insert(0, ROOT)
+    import torch
+    from proqa_amd.optim import FusedAdamW
+    from proqa_amd.retriever import BERT_BASE
+    from proqa_amd.trainable import TrainableRetriever, inbatch_loss
+    dev = torch.device("cuda", 0)
+    names = ["casts", "copies"] if variant is None else [variant]
+    models, opts = {}, {}
+    for name in names:
+        model = TrainableRetriever(BERT_BASE, device=dev, dropout_seed=0)
+        kw = dict(half_copies=model.half_weights()) if name == "copies" else {}
+        models[name] = model
+        opts[name] = FusedAdamW(model.parameters(), lr=1e-5, max_grad_norm=2.0, loss_scale="dynamic", **kw)
+    result = {}
+    for pairs in batches:
+        batch, lq, lc = make_batch(pairs, pairs, dev)
+        times = {name: [] for name in names}
+        for step in range((WARMUP + steps) * len(names)):
+            name = names[step % len(names)]
+            model, opt = models[name], opts[name]
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(accumulate):
+                out = model(batch)
+                loss = inbatch_loss(out["q"], out["c"]) / accumulate
+                opt.scale_loss(loss).backward()
+            opt.step()
+            opt.zero_grad(set_to_none=True)
+            t1.record()
+            torch.cuda.synchronize()
+            times[name].append(t0.elapsed_time(t1))
+        med = {name: statistics.median(t[WARMUP:]) for name, t in times.items()}
+        result[str(pairs)] = {"accumulate": accumulate, "loss": float(loss), "tokens": sum(lq) + sum(lc),
+                              **{f"step_ms_median_{name}": v for name, v in med.items()},
+                              **{f"step_ms_min_{name}": min(t[WARMUP:]) for name, t in times.items()}}
+        if len(names) == 2:
+            result[str(pairs)]["copies_over_casts"] = med["copies"] / med["casts"]
+    print("RESULT " + json.dumps(result))
+
+
+def run_child(mode, args, prefix=(), variant=None):
     cmd = list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", mode, "--batches", args.batches, "--steps", str(args.steps),
                           "--dropout", str(args.dropout)]
+    if getattr(args, "half_weights", False):
+        cmd += ["--half-weights", "--accumulate", str(args.accumulate)] + (["--variant", variant] if variant else [])
     out = subprocess.run(cmd, check=True, timeout=900, capture_output=True, text=True).stdout
     return json.loads([l for l in out.splitlines() if l.startswith("RESULT ")][-1][len("RESULT "):])
 
@@ -156,6 +207,33 @@ def short(name):
     return "gemm (library)" if ("Cijk" in name or "gemm" in name.lower()) else "torch: " + name[-60:]
 
 
+def main_half(args, batches):
+    result = {"rocm": open("/opt/rocm/.info/version").read().strip() if os.path.exists("/opt/rocm/.info/version") else "",
+              "accumulate": args.accumulate, "module": run_child("events", args)}
+    if not args.skip_trace:
+        prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+        if args.out is None:
+            import tempfile
+            args.out = tempfile.mkdtemp(prefix="train_step_timing_")
+        trace = {}
+        for b in batches:
+            for variant in ("casts", "copies"):      # one traced run per size and variant: its kernels are the whole trace
+                d = os.path.join(args.out, f"{b}_{variant}")
+                os.makedirs(d, exist_ok=True)
+                one = argparse.Namespace(batches=str(b), steps=args.steps, dropout=0.0, half_weights=True, accumulate=args.accumulate)
+                run_child("trace", one, prefix=[prof, "--kernel-trace", "--output-format", "csv", "-d", d, "--"], variant=variant)
+                rows = read_trace(d)
+                n = WARMUP + args.steps
+                us = lambda pred: sum(e - s for name, s, e in rows if pred(name)) / n / 1e3
+                trace.setdefault(str(b), {})[variant] = {
+                    "launches_per_micro_batch": len(rows) / n / args.accumulate,      # (the optimizer's few launches included)
+                    "adamw_update_us_per_step": us(lambda k: "adamw_update" in k),
+                    "adamw_us_per_step": us(lambda k: "adamw_" in k),
+                    "kernels_us_per_step_total": us(lambda k: True)}
+        result["trace"] = trace
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--child", default=None, choices=["events", "torch", "trace"])
@@ -164,10 +242,17 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--skip-trace", action="store_true")
     ap.add_argument("--dropout", type=float, default=0.0, help="also time steps with both dropout rates at this value")
+    ap.add_argument("--half-weights", action="store_true", help="optimizer steps with and without the fp16 working copies")
+    ap.add_argument("--accumulate", type=int, default=1, help="micro-batches per optimizer step (with --half-weights)")
+    ap.add_argument("--variant", default=None, choices=["casts", "copies"], help=argparse.SUPPRESS)
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
+    if args.child and args.half_weights:
+        return child_half(args.child, batches, args.steps, args.accumulate, args.variant)
     if args.child:
         return child(args.child, batches, args.steps, args.dropout)
+    if args.half_weights:
+        return main_half(args, batches)
     result = {"rocm": open("/opt/rocm/.info/version").read().strip() if os.path.exists("/opt/rocm/.info/version") else "",
               "module": run_child("events", args), "torch_autograd_fp16": run_child("torch", args)}
     if not args.skip_trace:
