@@ -151,6 +151,19 @@ int proqa_index_search_finish(proqa_index* idx, int* rewritten);
 int proqa_index_reconstruct_batch_device(proqa_index* idx, const int64_t* ids_dev, int64_t n, int64_t idx_offset,
                                          void* out_dev, int out_dtype, void* stream);
 
+/* the collect step of the reference's online sampler (qa/online_sampler.py:117-136: I to the host, a dict
+ * lookup and an `in gold_paras` test per id, para_embed[I] gathered and copied back) as one launch on device pointers.
+ * With live(j) = idx_offset <= ids[j] < idx_offset + ntotal:
+ *   rows_out[j]   = what proqa_index_reconstruct_batch_device writes for ids[j] ([k, d] of out_dtype; zero row if !live(j))
+ *   labels_out[j] = 1 if live(j) and ids[j] occurs in gold_dev, else 0 (int32 [k]); gold_dev: n_gold int64 ids, strictly
+ *                   ascending, in the id space of ids_dev (may be NULL when n_gold == 0)
+ *   record_dev    = int64 [2 + head]: the number of live ids, the sum of labels_out, then ids[0..head) with -1 past k
+ * head is in [0, 64].  k == 0 writes the record only.  The two counts are integer sums, so every output is the same bits
+ * from run to run.  Asynchronous on `stream`; record_dev is written on it from its first word on. */
+int proqa_sampler_collect_device(proqa_index* idx, const int64_t* ids_dev, int64_t k, int64_t idx_offset, const int64_t* gold_dev,
+                                 int64_t n_gold, int head, void* rows_out_dev, int out_dtype, int32_t* labels_out_dev,
+                                 int64_t* record_dev, void* stream);
+
 /* statistics of the last search on this handle (for tests and the benchmark) */
 typedef struct proqa_search_stats {
   int32_t rounds;            /* filter+merge rounds launched */

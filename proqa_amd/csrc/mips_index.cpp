@@ -2219,6 +2219,26 @@ int proqa_index_reconstruct_batch_device(proqa_index* idx, const int64_t* ids_de
   return PROQA_OK;
 }
 
+int proqa_sampler_collect_device(proqa_index* idx, const int64_t* ids_dev, int64_t k, int64_t idx_offset, const int64_t* gold_dev,
+                                 int64_t n_gold, int head, void* rows_out_dev, int out_dtype, int32_t* labels_out_dev,
+                                 int64_t* record_dev, void* stream) {
+  if (!idx) return fail(PROQA_EINVAL, "sampler_collect: idx is NULL");
+  if (k < 0 || (k > 0 && (!ids_dev || !rows_out_dev || !labels_out_dev)))
+    return fail(PROQA_EINVAL, "sampler_collect: k=%lld or NULL argument", (long long)k);
+  if (head < 0 || head > 64) return fail(PROQA_EINVAL, "sampler_collect: head=%d is outside [0, 64]", head);
+  if (n_gold < 0 || n_gold > INT32_MAX || (n_gold > 0 && !gold_dev))
+    return fail(PROQA_EINVAL, "sampler_collect: n_gold=%lld or NULL gold list", (long long)n_gold);
+  if (!record_dev) return fail(PROQA_EINVAL, "sampler_collect: record is NULL");
+  if (out_dtype != PROQA_F16 && out_dtype != PROQA_F32) return fail(PROQA_EINVAL, "sampler_collect: bad dtype %d", out_dtype);
+  PROQA_ON_DEVICE(idx->device);
+  hipStream_t st = (hipStream_t)stream;
+  PROQA_HIP(hipMemsetAsync(record_dev, 0, 2 * sizeof(int64_t), st));   // the kernel's integer atomics add to these two
+  PROQA_HIP(launch_sampler_collect_rows(idx->xb, idx->exact ? idx->xb32 : nullptr, idx->n, (const long long*)ids_dev, k, idx_offset,
+                                        (const long long*)gold_dev, (int)n_gold, head, rows_out_dev, out_dtype == PROQA_F32,
+                                        labels_out_dev, (long long*)record_dev, st));
+  return PROQA_OK;
+}
+
 int proqa_topk_merge_strided_device(const float* D_parts_dev, const int64_t* I_parts_dev, int n_parts, int64_t nq, int k,
                                     int64_t stride_d, int64_t stride_i, float* D_dev, int64_t* I_dev, void* stream) {
   if (!D_parts_dev || !I_parts_dev || !D_dev || !I_dev || n_parts <= 0 || nq < 0 || k <= 0)

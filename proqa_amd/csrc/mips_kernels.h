@@ -183,6 +183,12 @@ hipError_t launch_merge(const MergeArgs& a, unsigned nq_pad, hipStream_t st);
 // index keeps float32 copies, else upcasts of the fp16 rows)
 hipError_t launch_gather_index_rows(const void* xb16, const float* xb32, long long n_index, const long long* ids, long long n,
                                     long long idx_offset, void* out, bool out_f32, hipStream_t st);
+// launch_gather_index_rows plus labels[r] = (ids[r] is a row of the index and occurs in gold[0..n_gold), ascending int64 ids)
+// and record[2 + head] = {rows of the index among ids, sum of labels, ids[0..head) with -1 past n}; the caller zeroes
+// record[0..2) on st before the launch (integer atomics add to it)
+hipError_t launch_sampler_collect_rows(const void* xb16, const float* xb32, long long n_index, const long long* ids, long long n,
+                                       long long idx_offset, const long long* gold, int n_gold, int head, void* out, bool out_f32,
+                                       int* labels, long long* record, hipStream_t st);
 // *flag = 1 if any of the nq lists holds fewer than `want` keys
 hipError_t launch_flag_short_lists(const unsigned* run_n, long long nq, unsigned want, unsigned* flag, hipStream_t st);
 // exact top-k of rows [0, n_rows) (n_rows <= kBootstrapMaxRows, k <= kBootstrapMaxK) for every query: run_keys / run_n /

@@ -2293,6 +2293,67 @@ __global__ void gather_index_rows(const _Float16* __restrict__ xb16, const float
   }
 }
 
+// the online sampler's collect (qa/online_sampler.py:117-136 does this on the host: I to the host, 5000 dict lookups and
+// `in gold_paras` tests, para_embed[I] gathered and copied back): gather_index_rows' rows, plus labels[r] = live(r) and
+// ids[r] in gold (int64, strictly ascending, id space), plus record = {#live, sum of labels, ids[0..head) padded with -1}.
+// One thread per 16 bytes of output row; the lane that holds a row's first piece searches gold.  The two counts are
+// reduced per wave (ballot + popcount) and added with integer atomics to the record the caller zeroed on the stream:
+// integer sums commute, so the record is the same bits every run.  Grid covers max(n * per_row, head) threads.
+__global__ void sampler_collect_rows(const _Float16* __restrict__ xb16, const float* __restrict__ xb32, long long n_index,
+                                     const long long* __restrict__ ids, long long n, long long idx_offset,
+                                     const long long* __restrict__ gold, int n_gold, int head, void* out, int out_f32,
+                                     int* __restrict__ labels, long long* __restrict__ record) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < head) record[2 + t] = t < n ? ids[t] : -1ll;
+  const int per_row = out_f32 ? kDim / 4 : kDim / 8;      // 16-byte pieces per output row
+  const bool in_range = t < n * per_row;
+  const long long r = in_range ? t / per_row : 0;
+  const int c = (int)(t - r * per_row);
+  long long id = 0;
+  bool live = false;
+  long long row = 0;
+  if (in_range) {
+    id = ids[r];
+    row = id - idx_offset;
+    live = row >= 0 && row < n_index;
+    if (!out_f32) {
+      f16x8 v = {0};
+      if (live) v = *(const f16x8*)(xb16 + row * kDim + c * 8);
+      *(f16x8*)((_Float16*)out + r * kDim + c * 8) = v;
+    } else {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (live) {
+        if (xb32) {
+          v = *(const f32x4*)(xb32 + row * kDim + c * 4);
+        } else {
+          const _Float16* src = xb16 + row * kDim + c * 4;
+          v = f32x4{(float)src[0], (float)src[1], (float)src[2], (float)src[3]};
+        }
+      }
+      *(f32x4*)((float*)out + r * kDim + c * 4) = v;
+    }
+  }
+  const bool owner = in_range && c == 0;
+  bool hit = false;
+  if (owner) {
+    if (live) {
+      int lo = 0, hi = n_gold;     // first gold[lo] >= id
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (gold[mid] < id) lo = mid + 1; else hi = mid;
+      }
+      hit = lo < n_gold && gold[lo] == id;
+    }
+    labels[r] = hit ? 1 : 0;
+  }
+  const unsigned long long live_mask = __ballot(owner && live);
+  const unsigned long long hit_mask = __ballot(hit);
+  if ((threadIdx.x & 63) == 0) {
+    if (live_mask) atomicAdd((unsigned long long*)record + 0, (unsigned long long)__builtin_popcountll(live_mask));
+    if (hit_mask) atomicAdd((unsigned long long*)record + 1, (unsigned long long)__builtin_popcountll(hit_mask));
+  }
+}
+
 // one-pass search of a large k: a query that collected fewer than `want` rows above its estimated threshold
 // the queries a leaping round left short are searched again on ordinary rounds as a batch of their own (mips_index.cpp
 // rescue_short_queries): their padded fp16 rows out, their result rows back in
@@ -2738,6 +2799,17 @@ hipError_t launch_gather_index_rows(const void* xb16, const float* xb32, long lo
   const long long pieces = n * (out_f32 ? kDim / 4 : kDim / 8);
   hipLaunchKernelGGL(gather_index_rows, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, (const _Float16*)xb16, xb32,
                      n_index, ids, n, idx_offset, out, out_f32 ? 1 : 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_sampler_collect_rows(const void* xb16, const float* xb32, long long n_index, const long long* ids, long long n,
+                                       long long idx_offset, const long long* gold, int n_gold, int head, void* out, bool out_f32,
+                                       int* labels, long long* record, hipStream_t st) {
+  const long long pieces = n * (out_f32 ? kDim / 4 : kDim / 8);
+  const long long threads = pieces > head ? pieces : head;
+  if (threads == 0) return hipSuccess;
+  hipLaunchKernelGGL(sampler_collect_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, (const _Float16*)xb16, xb32,
+                     n_index, ids, n, idx_offset, gold, n_gold, head, out, out_f32 ? 1 : 0, labels, record);
   return hipGetLastError();
 }
 

@@ -175,6 +175,35 @@ class IndexFlatIP:
                                                                       _lib.current_stream_ptr()))
         return out
 
+    def collect_labeled_device(self, ids, gold_rows, head, dtype=None, idx_offset=0):
+        """The collect step of the reference's online sampler (qa/online_sampler.py:117-136) in one launch: ids int64 CUDA
+        tensor [k] (a row of search_device's I), gold_rows int64 CUDA tensor of strictly ascending ids (or None) ->
+        (rows [k, d] as reconstruct_batch_device gives them, labels int32 [k]: 1 where the id is a row of the index and
+        occurs in gold_rows, record int64 [2 + head]: the number of ids that are rows of the index, the sum of the
+        labels, ids[:head] padded with -1).  Nothing leaves the GPU."""
+        import torch
+        if not ids.is_cuda or ids.dtype != torch.int64:
+            raise ValueError("collect_labeled_device expects an int64 CUDA tensor")
+        if gold_rows is not None and (not gold_rows.is_cuda or gold_rows.dtype != torch.int64 or gold_rows.dim() != 1):
+            raise ValueError("collect_labeled_device expects gold_rows as a 1-D int64 CUDA tensor")
+        if ids.dim() != 1:
+            raise ValueError(f"ids must have shape [k], got {tuple(ids.shape)}")
+        head = int(head)            # outside [0, 64]: the library's PROQA_EINVAL
+        dtype = dtype or torch.float16
+        ids = ids.contiguous()
+        k = ids.numel()
+        n_gold = 0 if gold_rows is None else gold_rows.numel()
+        gold_rows = gold_rows.contiguous() if n_gold else None
+        rows = torch.empty((k, self.d), dtype=dtype, device=ids.device)
+        labels = torch.empty((k,), dtype=torch.int32, device=ids.device)
+        record = torch.empty((2 + min(max(head, 0), 64),), dtype=torch.int64, device=ids.device)
+        with torch.cuda.device(ids.device):
+            _lib.check(self._lib.proqa_sampler_collect_device(
+                self._h, ids.data_ptr() if k else None, k, int(idx_offset), gold_rows.data_ptr() if n_gold else None, n_gold,
+                head, rows.data_ptr() if k else None, _torch_dtype_code(rows), labels.data_ptr() if k else None,
+                record.data_ptr(), _lib.current_stream_ptr()))
+        return rows, labels, record
+
     # -- introspection / tuning ---------------------------------------------------------
     def last_stats(self):
         st = _lib.SearchStats()

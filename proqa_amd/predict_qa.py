@@ -13,7 +13,8 @@ The rank score of a passage is its fp32 dot product with the fp16 question embed
 index; under --search ivf the inner product the IVF search returns beside its L2 distance, as the reference's rank_logits
 is q . para_embed of the gathered rows, qa/bert_retrieve_qa.py:76); under --efficient_eval the reference rounds it to
 fp16.  A passage without any paragraph token gets the answer ""
-(the reference raises IndexError there).  Training (--do_train) is not part of this project.
+(the reference raises IndexError there).  Training (--do_train) is refused here: it is train_reader.py, whose dev
+evaluation is this module's evaluate().
 """
 import argparse
 import json
@@ -90,56 +91,17 @@ def load_qa(path):
         return [json.loads(line) for line in f.readlines()]
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
-    _refuse_training(argv)
-    args = build_parser().parse_args(argv)
-    if not args.do_predict:
-        raise SystemExit("train_retrieve_qa.py: only --do_predict is supported")
-    check_search_args(args)
+def evaluate(args, reader, tokenizer, qa_data, index, index2paraid, stats=None, say=print):
+    """Steps 1-5 of the module's docstring over loaded pieces: reader (a BertReader), the questions of qa_data, an index that
+    holds the rows (IndexFlatIP, or IndexIVFFlat under args.search == "ivf") and its idx_id.json mapping.  Prints the alpha
+    sweep's lines through `say`, fills the per-stage seconds into `stats`, returns the best EM.  Also the dev evaluation of
+    train_reader.py, over the index its sampler searches."""
     import torch
-    from transformers import BertTokenizer
     from . import qa_utils as qu
     from .datasets import TokenizeCollate
-    from .get_embed import load_bert_config
-    from .index import IndexFlatIP, IndexIVFFlat
-    from .reader import BertReader
     from .utils import DocDB
-
-    t_start = time.perf_counter()
-    stats = LAST_RUN_STATS
-    stats.clear()
-    cfg = load_bert_config(args.bert_model_name)
-    tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    reader = BertReader.load(args.init_checkpoint, cfg, dev)
-    if args.add_select and not reader.add_select:
-        raise SystemExit("--add-select: the checkpoint has no select_outputs")
-    reader.add_select = bool(args.add_select)
-    qa_data = load_qa(args.raw_eval_data)
-    with open(args.index2paraid) as f:
-        index2paraid = json.load(f)
-    para_embed = np.load(args.index_path).astype("float32")
-    if args.search == "ivf":
-        # qa/online_sampler.py:75-79, and no IndexFlatIP of the rows beside it
-        rows16 = torch.from_numpy(para_embed).to(dev)
-        rows16 = rows16.half() if torch.equal(rows16.half().float(), rows16) else rows16
-        del para_embed
-        index = IndexIVFFlat(IndexFlatIP(128), 128, args.nlist)
-        t_ivf = time.perf_counter()
-        index.train(rows16)
-        torch.cuda.synchronize()
-        stats["ivf_train_seconds"] = time.perf_counter() - t_ivf
-        t_ivf = time.perf_counter()
-        index.add(rows16)
-        torch.cuda.synchronize()
-        stats["ivf_add_seconds"] = time.perf_counter() - t_ivf
-        index.nprobe = args.nprobe
-        del rows16
-    else:
-        index = IndexFlatIP(128)
-        index.add(para_embed)
-
+    stats = {} if stats is None else stats
+    dev = reader.device
     # 1 + 2: all questions through the question tower, one search
     t0 = time.perf_counter()
     questions = [qa["question"] for qa in qa_data]
@@ -210,12 +172,65 @@ def main(argv=None):
             "passage": " ".join(p["doc_tokens"]), "question": questions[qi]})
         qid2ground[qid] = qa_data[qi]["answer"]
     _, best = qu.alpha_sweep(qid2results, qid2ground, regex=args.regex,
-                             save_prefix=args.prefix if args.save_pred else None)
-    print(best)
+                             save_prefix=args.prefix if args.save_pred else None, out=say)
     t4 = time.perf_counter()
     stats.update(questions=len(questions), sequences=len(items), tokens=int(sum(len(it[3]) for it in items)),
-                 startup_seconds=t0 - t_start, search_seconds=t1 - t0, pair_building_seconds=t2 - t1,
-                 reader_seconds=t3 - t2, postprocess_seconds=t4 - t3, total_seconds=t4 - t_start)
+                 search_seconds=t1 - t0, pair_building_seconds=t2 - t1, reader_seconds=t3 - t2, postprocess_seconds=t4 - t3)
+    return best
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    _refuse_training(argv)
+    args = build_parser().parse_args(argv)
+    if not args.do_predict:
+        raise SystemExit("train_retrieve_qa.py: only --do_predict is supported")
+    check_search_args(args)
+    import torch
+    from transformers import BertTokenizer
+    from .get_embed import load_bert_config
+    from .index import IndexFlatIP, IndexIVFFlat
+    from .reader import BertReader
+
+    t_start = time.perf_counter()
+    stats = LAST_RUN_STATS
+    stats.clear()
+    cfg = load_bert_config(args.bert_model_name)
+    tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    reader = BertReader.load(args.init_checkpoint, cfg, dev)
+    if args.add_select and not reader.add_select:
+        raise SystemExit("--add-select: the checkpoint has no select_outputs")
+    reader.add_select = bool(args.add_select)
+    qa_data = load_qa(args.raw_eval_data)
+    with open(args.index2paraid) as f:
+        index2paraid = json.load(f)
+    para_embed = np.load(args.index_path).astype("float32")
+    if args.search == "ivf":
+        # qa/online_sampler.py:75-79, and no IndexFlatIP of the rows beside it
+        rows16 = torch.from_numpy(para_embed).to(dev)
+        rows16 = rows16.half() if torch.equal(rows16.half().float(), rows16) else rows16
+        del para_embed
+        index = IndexIVFFlat(IndexFlatIP(128), 128, args.nlist)
+        t_ivf = time.perf_counter()
+        index.train(rows16)
+        torch.cuda.synchronize()
+        stats["ivf_train_seconds"] = time.perf_counter() - t_ivf
+        t_ivf = time.perf_counter()
+        index.add(rows16)
+        torch.cuda.synchronize()
+        stats["ivf_add_seconds"] = time.perf_counter() - t_ivf
+        index.nprobe = args.nprobe
+        del rows16
+    else:
+        index = IndexFlatIP(128)
+        index.add(para_embed)
+
+    t0 = time.perf_counter()
+    best = evaluate(args, reader, tokenizer, qa_data, index, index2paraid, stats)
+    print(best)
+    t4 = time.perf_counter()
+    stats.update(startup_seconds=t0 - t_start, total_seconds=t4 - t_start)
     if os.environ.get("PROQA_STATS_JSON"):
         with open(os.environ["PROQA_STATS_JSON"], "w") as f:
             json.dump(stats, f)

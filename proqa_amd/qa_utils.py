@@ -123,6 +123,81 @@ def prepare_many(passages, wordpieces):
     return out
 
 
+def char_to_word_offset(text):
+    """prepare()'s char_to_word_offset (qa/prepro_utils.py:150-164): for every character of text the index of the word of
+    split_words(text) it belongs to; a separator belongs to the word before it (-1 before the first word)."""
+    out, n, inside = [], 0, False
+    for ch in text:
+        if _is_space(ch):
+            inside = False
+        elif not inside:
+            n += 1
+            inside = True
+        out.append(n - 1)
+    return out
+
+
+def orig_to_tok_index(tok_to_orig_index, n_words):
+    """prepare()'s orig_to_tok_index from its inverse: the position of every word's first piece among all pieces (a word
+    without pieces gets the position of the next word's first piece, as the reference's running length gives it)."""
+    out, k = [], 0
+    for w in range(n_words):
+        while k < len(tok_to_orig_index) and tok_to_orig_index[k] < w:
+            k += 1
+        out.append(k)
+    return out
+
+
+def match_answer_span(p, answer, tokenizer, match="string"):
+    """The strings of the (normalised) passage p that match the answers (qa/prepro_dense.py:30-42, 57-74), SORTED -- the
+    reference returns them in `set` order, which changes from run to run.  string: every run of the SimpleTokenizer's
+    tokens of p whose lower-cased text equals an answer's, as the passage spells it; regex: every match of answer[0]."""
+    if match == "string":
+        tokens = tokenizer.tokenize(p)
+        text = tokens.words(uncased=True)
+        matched = set()
+        for single in answer:
+            single = tokenizer.tokenize(normalize(single)).words(uncased=True)
+            for i in range(0, len(text) - len(single) + 1):
+                if single == text[i:i + len(single)]:
+                    matched.add(tokens.slice(i, i + len(single)).untokenize())
+        return sorted(matched)
+    if match == "regex":
+        pattern = normalize(answer[0])
+        try:
+            compiled = re.compile(pattern, flags=re.IGNORECASE + re.UNICODE + re.MULTILINE)
+        except BaseException:
+            print("Regular expression failed to compile: %s" % pattern)
+            return []
+        return sorted({m.group() for m in re.finditer(compiled, p)})
+    raise ValueError(f"match must be 'string' or 'regex', got {match!r}")
+
+
+def _improve_answer_span(all_doc_tokens, input_start, input_end, tok_answer_text):
+    """The narrowest run of pieces inside [input_start, input_end] that spells the tokenised answer, leftmost start first
+    and longest end first (qa/prepro_utils.py:62-72); the input span when there is none."""
+    for new_start in range(input_start, input_end + 1):
+        for new_end in range(input_end, new_start - 1, -1):
+            if " ".join(all_doc_tokens[new_start:new_end + 1]) == tok_answer_text:
+                return new_start, new_end
+    return input_start, input_end
+
+
+def find_ans_span_with_char_offsets(detected_ans, char_to_word, doc_tokens, all_doc_tokens, orig_to_tok, tokenize):
+    """detected_ans = {"text", "char_spans": [(first char, LAST char)]} -> [(first piece, last piece)] per char span
+    (qa/prepro_utils.py:74-99): the pieces of the words the characters lie in, narrowed to the pieces that spell the
+    answer.  tokenize: text -> WordPiece tokens (the tokenizer's own `tokenize`).  The reference's "Could not find answer"
+    print is left out."""
+    tok_answer_text = " ".join(tokenize(detected_ans["text"]))
+    spans = []
+    for char_start, char_end in detected_ans["char_spans"]:
+        tok_start, tok_end = char_to_word[char_start], char_to_word[char_end]
+        sub_start = orig_to_tok[tok_start]
+        sub_end = orig_to_tok[tok_end + 1] - 1 if tok_end < len(doc_tokens) - 1 else len(all_doc_tokens) - 1
+        spans.append(_improve_answer_span(all_doc_tokens, sub_start, sub_end, tok_answer_text))
+    return spans
+
+
 def build_pair(q_ids, p_ids, max_seq_length, cls_id, sep_id):
     """q_ids = tokenizer.encode(question) ([CLS] ... [SEP]), p_ids = the passage's piece ids ->
     (input_ids, segment_ids, para_offset, n_passage_pieces_kept).  The passage is cut to max_seq_length - para_offset - 1

@@ -1,0 +1,374 @@
+"""`python train_reader.py --raw-train-data train.txt --raw-eval-data dev.txt --matched-para-path matched.txt ...`: reader
+training, the --do_train loop of qa/train_retrieve_qa.py:170-265 on one MI355X.
+
+Same flags (qa/config.py, plus --index2paraid as predict_qa has it), same output directory, model_name and log.txt, the
+same seeds, accumulation rule (batch_step counts a failed retrieval, which therefore uses up an update slot), the
+per-epoch `Failed retrieval: x/N` line, evaluation every --eval_period updates and after every epoch, best-model.pt,
+model-{epoch+1}-{em}.pt after epoch 16, wait_step / stop_training.  The model is TrainableReader with the config's two
+dropout rates, the optimizer FusedAdamW with the reference's two parameter groups, a dynamic loss scale and the clip of
+--max_grad_norm inside the fused step; the batches come from proqa_amd.online_sampler.OnlineSampler, whose per-question
+retrieval stays on the device.
+
+Intended differences: the sampler's (its question pass in eval(), the exact search, sorted matched
+strings); activations are fp16 with or without --fp16 and --fp16_opt_level is ignored; the host never reads a loss inside
+the loop (they are read at an evaluation, at the end of an epoch and at the end); the dev evaluation is predict_qa.evaluate
+-- all questions at once over the BertReader that TrainableReader builds for eval(), on the SAME IndexFlatIP the sampler
+searches (the model is back in train() after it, as after the reference's predict()); the initial weights come from --init_checkpoint, or from the local
+--bert_model_name directory plus --retriever-path (nothing is fetched); --do_predict alone, --local_rank, --no_cuda,
+--use-spanbert, --separate and --add-select are refused.  `train_retrieve_qa.py` keeps its refusal of the training flags.
+"""
+import argparse
+import json
+import logging
+import os
+import random
+import time
+
+from .pretrain_retriever import _Losses, _tensorboard, is_update_step, load_bert_weights, load_model_config, parameter_groups
+
+LAST_RUN_STATS = {}
+
+# test hooks: parameters whose name contains one of these substrings are frozen (the word-embedding gradient is summed
+# with atomics, the module's one run-to-run difference); a callable that receives every non-empty batch before the
+# forward; False = per-forward casts in the retriever's towers instead of the fp16 working copies
+FROZEN_PARAMETERS = ()
+ON_BATCH = None
+USE_HALF_COPIES = True
+
+logger = logging.getLogger(__name__)
+
+
+# ---- pure pieces (no GPU) ------------------------------------------------------------------------------------------------
+
+def build_parser():
+    """the flags of qa/config.py, plus --index2paraid"""
+    p = argparse.ArgumentParser(description="ProQA reader training (qa/train_retrieve_qa.py --do_train) on MI355X")
+    p.add_argument("--bert_model_name", default="bert-base-uncased", type=str)
+    p.add_argument("--output_dir", default="logs", type=str)
+    p.add_argument("--weight_decay", default=0.0, type=float)
+    p.add_argument("--load", default=False, action="store_true")
+    p.add_argument("--num_workers", default=5, type=int)
+    p.add_argument("--train_file", type=str, default="../../data/mrqa-train/HotpotQA-tokenized.jsonl")
+    p.add_argument("--predict_file", type=str, default="../../data/mrqa-dev/HotpotQA-tokenized.jsonl")
+    p.add_argument("--init_checkpoint", type=str, default="")
+    p.add_argument("--do_lower_case", default=True, action="store_true")
+    p.add_argument("--max_seq_length", default=512, type=int)
+    p.add_argument("--max_query_length", default=50, type=int)
+    p.add_argument("--do_train", default=False, action="store_true")
+    p.add_argument("--do_predict", default=False, action="store_true")
+    p.add_argument("--train_batch_size", default=8, type=int)
+    p.add_argument("--predict_batch_size", default=100, type=int)
+    p.add_argument("--learning_rate", default=5e-5, type=float)
+    p.add_argument("--adam_epsilon", default=1e-8, type=float)
+    p.add_argument("--num_train_epochs", default=200, type=float)
+    p.add_argument("--wait_step", type=int, default=100)
+    p.add_argument("--save_checkpoints_steps", default=1000, type=int)
+    p.add_argument("--iterations_per_loop", default=1000, type=int)
+    p.add_argument("--no_cuda", default=False, action="store_true")
+    p.add_argument("--local_rank", type=int, default=-1)
+    p.add_argument("--accumulate_gradients", type=int, default=1)
+    p.add_argument("--seed", type=int, default=3)
+    p.add_argument("--gradient_accumulation_steps", type=int, default=1)
+    p.add_argument("--eval_period", type=int, default=1000, help="setting to -1: eval only after each epoch")
+    p.add_argument("--verbose", action="store_true", default=False)
+    p.add_argument("--efficient_eval", action="store_true", help="accepted: the evaluation always runs the fp16 reader")
+    p.add_argument("--max_answer_len", default=20, type=int)
+    p.add_argument("--max_grad_norm", default=5.0, type=float)
+    p.add_argument("--fp16", action="store_true")
+    p.add_argument("--fp16_opt_level", type=str, default="O1", help="ignored")
+    p.add_argument("--qa-drop", default=0, type=float)
+    p.add_argument("--rank-drop", default=0, type=float)
+    p.add_argument("--MI", action="store_true")
+    p.add_argument("--mi-k", default=10, type=int)
+    p.add_argument("--max-pool", action="store_true")
+    p.add_argument("--eval-workers", default=16, type=int, help="threads of the native WordPiece tokenizer")
+    p.add_argument("--save-pred", action="store_true")
+    p.add_argument("--retriever-path", type=str, default="")
+    p.add_argument("--raw-train-data", type=str, default="../data/nq-train.txt")
+    p.add_argument("--raw-eval-data", type=str, default="../data/nq-dev.txt")
+    p.add_argument("--fix-para-encoder", action="store_true")
+    p.add_argument("--db-path", type=str, default="../data/nq_paras.db")
+    p.add_argument("--index-path", type=str, default="retrieval/index_data/para_embed_100k.npy")
+    p.add_argument("--index2paraid", type=str, default="retrieval/index_data/idx_id.json",
+                   help="idx_id.json of the index (the reference's OnlineSampler default)")
+    p.add_argument("--matched-para-path", type=str, default="../data/wq_ft_train_matched.txt")
+    p.add_argument("--use-spanbert", action="store_true")
+    p.add_argument("--spanbert-path", default="../data/span_bert", type=str)
+    p.add_argument("--eval-k", default=5, type=int)
+    p.add_argument("--regex", action="store_true")
+    p.add_argument("--separate", action="store_true")
+    p.add_argument("--add-select", action="store_true")
+    p.add_argument("--drop-early", action="store_true")
+    p.add_argument("--shared-norm", action="store_true")
+    p.add_argument("--prefix", type=str, default="eval")
+    p.add_argument("--debug", action="store_true")
+    p.add_argument("--use-top-passage", action="store_true")
+    p.add_argument("--topk", default=30, type=int)
+    p.add_argument("--save-all", action="store_true")
+    p.add_argument("--candidates", default="", type=str)
+    return p
+
+
+def get_args(argv=None):
+    return build_parser().parse_args(argv)
+
+
+def model_name(args):
+    """the reference's run name (train_retrieve_qa.py:48), from the flags BEFORE train_batch_size is divided"""
+    return (f"dense-seed{args.seed}-bsz{args.train_batch_size}-fp16{args.fp16}-{args.prefix}-lr{args.learning_rate}-"
+            f"{args.bert_model_name}-qdrop{args.qa_drop}-sn{args.shared_norm}-sep{args.separate}-as{args.add_select}-"
+            f"noearly{args.drop_early}")
+
+
+def check_args(args):
+    """The refusals, and --do_train implied.  Raises what the reference raises where it raises."""
+    from .online_sampler import MAX_HEAD
+    if args.accumulate_gradients < 1:
+        raise ValueError("Invalid accumulate_gradients parameter: {}, should be >= 1".format(args.accumulate_gradients))
+    if args.do_predict and not args.do_train:
+        raise SystemExit("train_reader.py: --do_predict alone is the evaluation of a checkpoint: run "
+                         "train_retrieve_qa.py --do_predict --init_checkpoint ...")
+    args.do_train = True
+    if not args.train_file:
+        raise ValueError("If `do_train` is True, then `train_file` must be specified.")
+    if not args.predict_file:
+        raise ValueError("If `do_train` is True, then `predict_file` must be specified.")
+    if args.local_rank != -1:
+        raise SystemExit("train_reader.py: --local_rank (DistributedDataParallel) is not supported: one GPU per run")
+    if args.no_cuda:
+        raise SystemExit("train_reader.py: --no_cuda: proqa_amd has no CPU path")
+    if args.use_spanbert:
+        raise SystemExit("train_reader.py: --use-spanbert (a cased reader beside the uncased retriever) is not built")
+    if args.separate or args.add_select:
+        raise SystemExit("train_reader.py: --separate / --add-select are not built: they need a select term in the loss "
+                         "kernels (DESIGN.md section 3h)")
+    if args.gradient_accumulation_steps < 1:
+        raise ValueError(f"Invalid gradient_accumulation_steps parameter: {args.gradient_accumulation_steps}, should be >= 1")
+    per_question = int(args.train_batch_size / args.accumulate_gradients)
+    if not 1 <= per_question <= MAX_HEAD:
+        raise ValueError(f"--train_batch_size {args.train_batch_size} / --accumulate_gradients {args.accumulate_gradients}: "
+                         f"the passages per question must be in [1, {MAX_HEAD}]")
+    if args.matched_para_path == "":
+        raise ValueError("--matched-para-path is required: the sampler's labels come from it")
+    return args
+
+
+def update_schedule(n_batches, gradient_accumulation_steps, failed=()):
+    """[batch_step of every optimizer step] over n_batches questions, batch_step counted from 1 across epochs;
+    `failed`: the batch steps whose retrieval failed ({}).  batch_step is incremented BEFORE the empty-batch `continue`
+    (train_retrieve_qa.py:185-188), so a failed retrieval uses up its slot of (batch_step + 1) % G == 0 and the update of
+    that slot does not happen: the gradients go on accumulating until the next slot."""
+    failed = set(failed)
+    return [b for b in range(1, n_batches + 1) if b not in failed and is_update_step(b, gradient_accumulation_steps)]
+
+
+def initial_state_dict(cfg, bert_weights):
+    """{`bert.*`: the pre-trained BertModel} of the reference's untrained BertRetrieveQA; qa_outputs keeps the module's
+    own initialisation and the retriever comes from --retriever-path"""
+    import torch
+    from .retriever import tower_keys
+    sd = {}
+    for key in tower_keys("bert", cfg.num_hidden_layers):
+        bare = key[len("bert."):]
+        if bare not in bert_weights:
+            raise SystemExit(f"train_reader.py: the BERT weights lack {bare!r}")
+        sd[key] = bert_weights[bare].detach().to(torch.float32).clone()
+    return sd
+
+
+# ---- the command -------------------------------------------------------------------------------------------------------------
+
+def main(argv=None):
+    args = check_args(get_args(argv))
+    import numpy as np
+    import torch
+    from transformers import BertTokenizer
+    from . import predict_qa
+    from .index import IndexFlatIP
+    from .online_sampler import OnlineSampler
+    from .optim import FusedAdamW
+    from .trainable_reader import TrainableReader
+    from .utils import DocDB
+
+    name = model_name(args)
+    tb_dir = os.path.join(args.output_dir, "tflogs", "dense", name)
+    args.output_dir = os.path.join(args.output_dir, name)
+    if os.path.exists(args.output_dir) and os.listdir(args.output_dir):
+        print(f"output directory {args.output_dir} already exists and is not empty.")
+    os.makedirs(args.output_dir, exist_ok=True)
+    handlers = [logging.FileHandler(os.path.join(args.output_dir, "log.txt")), logging.StreamHandler()]
+    for h in handlers:
+        h.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S"))
+        logger.addHandler(h)
+    logger.setLevel(logging.INFO)
+    logger.propagate = False
+    tb = None
+    para_db = None
+    try:
+        logger.info(args)
+        if not torch.cuda.is_available():
+            raise RuntimeError("no MI355X visible: reader training has no CPU fallback")
+        device = torch.device("cuda", torch.cuda.current_device())
+        logger.info("device %s n_gpu %d distributed training %r", device, 1, False)
+        args.train_batch_size = int(args.train_batch_size / args.accumulate_gradients)     # passages per question
+        random.seed(args.seed)
+        np.random.seed(args.seed)
+        torch.manual_seed(args.seed)
+        torch.cuda.manual_seed_all(args.seed)
+
+        cfg, p_hidden, p_attention = load_model_config(args.bert_model_name)
+        tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
+        logger.info("Loading para db and pretrained index ...")
+        para_db = DocDB(args.db_path)
+        if args.max_seq_length > cfg.max_position_embeddings:
+            raise ValueError("Cannot use sequence length %d because the BERT model was only trained up to sequence length %d"
+                             % (args.max_seq_length, cfg.max_position_embeddings))
+        # ONE copy of the rows in HBM: the sampler searches it and the dev evaluation searches it
+        index = IndexFlatIP(128)
+        index.add_npy(args.index_path)
+        with open(args.index2paraid) as f:
+            index2paraid = json.load(f)
+        eval_data = predict_qa.load_qa(args.raw_eval_data)
+
+        if args.init_checkpoint != "":
+            retriever_path, args.retriever_path = args.retriever_path, ""       # the checkpoint carries the retriever
+            model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
+                                              attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
+            args.retriever_path = retriever_path
+            model.load_state_dict(torch.load(args.init_checkpoint, map_location="cpu"))
+        else:
+            state = initial_state_dict(cfg, load_bert_weights(args.bert_model_name))
+            model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
+                                              attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
+            model.load_state_dict(state, strict=False)
+        logger.info(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+        if args.fix_para_encoder:
+            model.freeze_c_encoder()
+        for n, p in model.named_parameters():
+            if any(s in n for s in FROZEN_PARAMETERS):
+                p.requires_grad_(False)
+
+        groups = parameter_groups(model, args.weight_decay)
+        half_copies = None
+        if USE_HALF_COPIES:
+            # fp16 working copies of the retriever's matrices (the sampler's question pass reads them); the step writes
+            # the copies of the parameters it owns, the frozen passage tower's are cast once and never go stale
+            owned = {id(p) for g in groups for p in g["params"]}
+            half_copies = {p: h for p, h in model.retriever.half_weights().items() if id(p) in owned}
+        optimizer = FusedAdamW(groups, lr=args.learning_rate, eps=args.adam_epsilon, max_grad_norm=args.max_grad_norm,
+                               loss_scale="dynamic", half_copies=half_copies)
+        logger.info("activations and their gradients are fp16 with or without --fp16 (fp32 masters, dynamic loss scale); "
+                    "--fp16_opt_level is ignored")
+        tb = _tensorboard(tb_dir)
+
+        def evaluate():
+            """the dev EM of the current weights: BertReader over an fp16 copy of them, on the sampler's index"""
+            meter.flush(tb)
+            model.eval()
+            try:
+                em = predict_qa.evaluate(args, model.inference_reader(), tokenizer, eval_data, index, index2paraid)
+            finally:
+                model.train()       # (the copy is dropped: the next evaluation takes the weights of its own time)
+            return float(em)
+
+        args.search, args.reader_batch = "exact", 256        # what predict_qa.evaluate reads beside the shared flags
+        global_step = 0      # gradient update step
+        batch_step = 0       # forward batch count
+        best_em = 0
+        wait_step = 0
+        stop_training = False
+        meter = _Losses()
+        evals, failed_per_epoch, failed_steps, update_steps = [], [], [], []
+        G = args.gradient_accumulation_steps
+        logger.info("Start training....")
+        model.train()
+        train_dataloader = OnlineSampler(args.raw_train_data, tokenizer, args.max_query_length, args.max_seq_length, para_db,
+                                         index, index2paraid=index2paraid, matched_para_path=args.matched_para_path,
+                                         regex=args.regex, device=device)
+        t_start = time.perf_counter()
+        for epoch in range(int(args.num_train_epochs)):
+            train_dataloader.shuffle()
+            failed_retrieval = 0
+            for batch in train_dataloader.load(model.retriever, k=args.train_batch_size):
+                batch_step += 1
+                if batch == {}:
+                    failed_retrieval += 1
+                    failed_steps.append(batch_step)
+                    continue
+                if ON_BATCH is not None:
+                    ON_BATCH(batch)
+                outputs = model(batch["net_input"])
+                loss = outputs["loss"]
+                if G > 1:
+                    loss = loss / G
+                optimizer.scale_loss(loss).backward()
+                meter.add(loss.detach(), global_step)
+
+                if is_update_step(batch_step, G):
+                    optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
+                    model.zero_grad()
+                    global_step += 1
+                    update_steps.append(batch_step)
+
+                    if args.eval_period != -1 and global_step % args.eval_period == 0:
+                        em = evaluate()
+                        logger.info("Step %d Train loss %.2f EM %.2f on epoch=%d" % (global_step, meter.avg, em * 100, epoch))
+                        evals.append({"step": global_step, "epoch": epoch, "em": em, "train_loss_avg": meter.avg})
+                        if tb is not None:
+                            tb.add_scalar("dev_em", em * 100, global_step)
+                        if best_em < em:
+                            logger.info("Saving model with best EM: %.2f -> EM %.2f on epoch=%d" % (best_em * 100, em * 100, epoch))
+                            torch.save({k: v.cpu() for k, v in model.state_dict().items()},
+                                       os.path.join(args.output_dir, "best-model.pt"))
+                            best_em = em
+                            wait_step = 0
+                            stop_training = False
+                        else:
+                            wait_step += 1
+                            if wait_step == args.wait_step:
+                                stop_training = True
+
+            logger.info(f"Failed retrieval: {failed_retrieval}/{len(train_dataloader)} ...")
+            failed_per_epoch.append(failed_retrieval)
+            em = evaluate()
+            evals.append({"step": global_step, "epoch": epoch, "em": em, "train_loss_avg": meter.avg, "end_of_epoch": True})
+            if tb is not None:
+                tb.add_scalar("dev_em", em * 100, global_step)
+            logger.info(f"average training loss {meter.avg}")
+            if best_em < em:
+                logger.info("Saving model with best EM: %.2f  -> %.2f on epoch=%d" % (best_em * 100, em * 100, epoch))
+                torch.save(model.state_dict(), os.path.join(args.output_dir, "best-model.pt"))
+                best_em = em
+                wait_step = 0
+            if epoch > 15:
+                logger.info(f"Saving model after epoch {epoch + 1}")
+                torch.save(model.state_dict(), os.path.join(args.output_dir, f"model-{epoch+1}-{em}.pt"))
+            if stop_training:
+                break
+        meter.flush(tb)
+        fused = optimizer.state_dict()["fused"]
+        seconds = time.perf_counter() - t_start
+        logger.info("Training finished!")
+
+        stats = LAST_RUN_STATS
+        stats.clear()
+        stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
+                     failed_retrieval=failed_per_epoch, failed_steps=failed_steps, update_steps=update_steps, skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"],
+                     seconds=seconds, best_em=best_em, output_dir=args.output_dir,
+                     sampler_seconds=dict(train_dataloader.seconds), sampler_transfers=dict(train_dataloader.transfers))
+        if os.environ.get("PROQA_STATS_JSON"):
+            with open(os.environ["PROQA_STATS_JSON"], "w") as f:
+                json.dump(stats, f)
+        return stats
+    finally:
+        if tb is not None:
+            tb.close()
+        if para_db is not None:
+            para_db.close()
+        for h in handlers:
+            logger.removeHandler(h)
+            h.close()
+
+
+if __name__ == "__main__":
+    main()

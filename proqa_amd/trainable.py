@@ -515,14 +515,16 @@ def inbatch_loss(q, c, target=None):
 # ---- one tower pass, shared by TrainableRetriever and TrainableReader ----------------------------------------------------------
 
 def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None, drop=(0.0, 0.0, 0, 0), probe_extra=None,
-              half=None):
+              half=None, seq_lens_host=None):
     """One BERT tower with gradients.  P: {key: fp32 master}; `tower` the key prefix of the tower's parameters (bert_q,
     bert_c, bert).  input_ids / input_mask [B, S] right-padded CUDA tensors, B >= 1; type_ids [B, S] or None (every token
     of type 0: the untyped embedding operator).  drop = (hidden rate, attention rate, seed, call) of this pass; a rate of 0
     runs the dropout-free operator.  probe_extra(lens) -> (device bool scalar, message): one more condition for the pass's
     single host round trip to check (ValueError(message) when it holds).  half: {tuple of weight keys: fp16 working copy
     of those masters stacked by rows} for EVERY product of the pass (HalfWeights.views), or None: each product casts its
-    masters itself.
+    masters itself.  seq_lens_host: the rows' lengths as a list of B ints that the caller vouches for (the mask is a
+    prefix of that many ones per row): the pass then makes NO host round trip -- the mask is not read or checked, and
+    probe_extra must be None.
     -> proj given (the key prefix of the projection): the [B, 128] fp16 embedding of pooler + projection;
        proj None: (h, cu_seqlens, lens, max_len), the packed last hidden state [T, H] fp16 and its geometry."""
     B, S = input_ids.shape
@@ -532,19 +534,29 @@ def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None,
     mask = input_mask.to(torch.bool)
     # as BertForRetriever.encode: a row without a valid token is evaluated as its first token; the mask of every row
     # must be a prefix of ones (re_collate pads on the right); one host round trip for the check and the sizes
-    lens = mask.sum(dim=1).clamp_(min=1).to(torch.int32)
-    bad = (mask[:, 1:] & ~mask[:, :-1]).any() if S > 1 else torch.zeros((), dtype=torch.bool, device=mask.device)
-    flags = [bad.to(torch.int64), lens.sum(dtype=torch.int64), lens.max().to(torch.int64)]
-    extra_message = None
-    if probe_extra is not None:
-        extra_bad, extra_message = probe_extra(lens)
-        flags.append(extra_bad.to(torch.int64))
-    probe = torch.stack(flags).cpu()
-    if bool(probe[0]):
-        raise ValueError("input_mask must be right-padded (a prefix of True per row), as re_collate produces")
-    if extra_message is not None and bool(probe[3]):
-        raise ValueError(extra_message)
-    n_tokens, max_len = int(probe[1]), int(probe[2])
+    if seq_lens_host is not None:
+        host = [int(n) for n in seq_lens_host]
+        if probe_extra is not None or len(host) != B or not all(1 <= n <= S for n in host):
+            raise ValueError(f"seq_lens_host must be {B} lengths in [1, {S}] (and excludes probe_extra)")
+        if len(set(host)) == 1:          # one length (a single question): a fill on the device, nothing is copied up
+            lens = torch.full((B,), host[0], dtype=torch.int32, device=ids.device)
+        else:
+            lens = torch.tensor(host, dtype=torch.int32).to(ids.device)
+        n_tokens, max_len = sum(host), max(host)
+    else:
+        lens = mask.sum(dim=1).clamp_(min=1).to(torch.int32)
+        bad = (mask[:, 1:] & ~mask[:, :-1]).any() if S > 1 else torch.zeros((), dtype=torch.bool, device=mask.device)
+        flags = [bad.to(torch.int64), lens.sum(dtype=torch.int64), lens.max().to(torch.int64)]
+        extra_message = None
+        if probe_extra is not None:
+            extra_bad, extra_message = probe_extra(lens)
+            flags.append(extra_bad.to(torch.int64))
+        probe = torch.stack(flags).cpu()
+        if bool(probe[0]):
+            raise ValueError("input_mask must be right-padded (a prefix of True per row), as re_collate produces")
+        if extra_message is not None and bool(probe[3]):
+            raise ValueError(extra_message)
+        n_tokens, max_len = int(probe[1]), int(probe[2])
     cu = torch.zeros(B + 1, dtype=torch.int32, device=ids.device)
     cu[1:] = torch.cumsum(lens, 0)
     eps, n_heads = float(cfg.layer_norm_eps), cfg.num_attention_heads
@@ -792,12 +804,16 @@ class TrainableRetriever(torch.nn.Module):
         return {"q": self._tower("bert_q", "proj_q", batch["input_ids_q"], batch["input_mask_q"]),
                 "c": self._tower("bert_c", "proj_c", batch["input_ids_c"], batch["input_mask_c"])}
 
-    def get_embed(self, batch, is_query_embed):
-        """The reference's get_embed (retriever.py:33-43); call it under torch.no_grad() for evaluation."""
+    def get_embed(self, batch, is_query_embed, check_mask=True, seq_lens_host=None):
+        """The reference's get_embed (retriever.py:33-43); call it under torch.no_grad() for evaluation.  With
+        check_mask=False and seq_lens_host (the rows' lengths, as BertForRetriever.get_embed takes them) the pass does not
+        read the mask and makes no host round trip."""
         tower, proj = ("bert_q", "proj_q") if is_query_embed else ("bert_c", "proj_c")
-        return {"embed": self._tower(tower, proj, batch["input_ids"], batch["input_mask"])}
+        if check_mask and seq_lens_host is not None:
+            seq_lens_host = None        # the mask is checked: its own lengths are used
+        return {"embed": self._tower(tower, proj, batch["input_ids"], batch["input_mask"], seq_lens_host)}
 
-    def _tower(self, tower, proj, input_ids, input_mask):
+    def _tower(self, tower, proj, input_ids, input_mask, seq_lens_host=None):
         if not input_ids.is_cuda:
             raise RuntimeError("TrainableRetriever expects CUDA tensors (the reference feeds move_to_cuda(batch))")
         if input_ids.shape[0] == 0:
@@ -809,4 +825,4 @@ class TrainableRetriever(torch.nn.Module):
         if p_hid > 0 or p_att > 0:
             self._dropout_call = (call + 1) & 0xFFFFFF
         return run_tower(self._flat, tower, self.config, input_ids, input_mask, proj=proj, drop=(p_hid, p_att, seed, call),
-                         half=self._half.views if self._half is not None else None)
+                         half=self._half.views if self._half is not None else None, seq_lens_host=seq_lens_host)

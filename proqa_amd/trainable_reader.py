@@ -205,16 +205,25 @@ class TrainableReader(torch.nn.Module):
                            geometry["para_offset"], cu_seqlens=cu, shared_norm=self.shared_norm, early=not self.drop_early,
                            qa_drop=p_qa, dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
 
+    def inference_reader(self):
+        """The BertReader that eval() forwards run: the inference class over an fp16 copy of the parameters, taken at the
+        first use after eval() was entered (train(), a load or a move drops it).  For evaluations that drive the inference
+        class themselves (predict_qa.evaluate in train_reader.py); in train() mode the copy would go stale: refused."""
+        if self.training:
+            raise RuntimeError("TrainableReader.inference_reader(): call eval() first; the copy is taken per evaluation")
+        if self._inference is None:
+            with torch.no_grad():
+                self._inference = BertReader(self.config, self.device).load_state_dict(
+                    {k: p.detach() for k, p in self.named_parameters()})
+        return self._inference
+
     @torch.no_grad()
     def _predict(self, net_input, pmask):
         """eval(): the reference's keys, computed by the inference class over an fp16 copy of the parameters (taken at the
         first eval() forward after train() or a load), so that what is evaluated during training is what BertReader and
         --do_predict serve.  start / end logits [B, L] fp16 carry the bits of proqa_reader_span_f16's logits, -inf outside
         the paragraph mask; rank_logits [1, P] fp32.  One host round trip (the lengths and the checks of the masks)."""
-        if self._inference is None:
-            self._inference = BertReader(self.config, self.device).load_state_dict(
-                {k: p.detach() for k, p in self.named_parameters()})
-        reader = self._inference
+        reader = self.inference_reader()
         dev = self.device
         ids = net_input["input_ids"]
         B, S = ids.shape
