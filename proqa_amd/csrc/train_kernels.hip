@@ -34,13 +34,14 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // ---- slabs -> sums ------------------------------------------------------------------------------------------------------
-// out_k[c] (+)= sum over the slabs, in ascending order, of ws[slab][k][c]; one thread per (k, column)
+// out_k[c] (+)= sum over the slabs, in ascending order, of ws[slab][k][c], k < n_k <= 4; one thread per (k, column); a null
+// out_k is skipped
 __global__ __launch_bounds__(256) void reduce_slabs(const float* __restrict__ ws, int n_slabs, int n_k, int cols,
                                                     float* out0, float* out1, float* out2, float* out3, int accumulate) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= n_k * cols) return;
   const int k = t / cols, c = t - k * cols;
-  float* out = k == 0 ? out0 : (k == 1 ? out1 : out2);
+  float* out = k == 0 ? out0 : (k == 1 ? out1 : (k == 2 ? out2 : out3));
   // compensated (Kahan) sum: the slabs of a long batch are many and of one sign more often than not
   float s = 0.f, comp = 0.f;
   for (int b = 0; b < n_slabs; ++b) {
@@ -49,19 +50,22 @@ __global__ __launch_bounds__(256) void reduce_slabs(const float* __restrict__ ws
     comp = (t - s) - y;
     s = t;
   }
-  if (out) out[c] = accumulate ? out[c] + s : s;
-  if (k == 2 && out3) out3[c] = accumulate ? out3[c] + s : s;   // (embedding: the position partials are the type-0 gradient too)
+  if (out) out[c] = accumulate ? out[c] + s : s;   // (looked at after the loop: the pointers' loads overlap it)
 }
 
 // ---- LayerNorm backward of one register-resident row -------------------------------------------------------------------
 // z = the normalised operand (x + bias + residual, or the embedding sum); dz = rstd (a - mean(a) - xhat mean(a xhat)),
 // a = dy gamma; dgam += dy xhat, dbet += dy.  Lanes hold chunks lane, lane + 64 of the row (8 columns each).
+// Every fused multiply-add is written out and contraction is off: which products the compiler fuses on its own depends on
+// how it happens to pack these loops in the kernel they are inlined into, and the kernels that share this row (with and
+// without dropout, typed and untyped) must give the same bits.
 __device__ __forceinline__ void layernorm_backward_row(const float (&z)[kMaxChunksPerLane][8],
                                                        const float (&dy)[kMaxChunksPerLane][8],
                                                        const float (&gam)[kMaxChunksPerLane][8], int lane, int n_chunks,
                                                        int cols, float eps, float (&dz)[kMaxChunksPerLane][8],
                                                        float (&dgam)[kMaxChunksPerLane][8],
                                                        float (&dbet)[kMaxChunksPerLane][8]) {
+#pragma clang fp contract(off)
   const float inv_n = 1.0f / (float)cols;
   float s = 0.f;
 #pragma unroll
@@ -81,7 +85,7 @@ __device__ __forceinline__ void layernorm_backward_row(const float (&z)[kMaxChun
         v += d * d;
       }
     }
-  const float rstd = rsqrtf(wave_sum(v) * inv_n + eps);
+  const float rstd = rsqrtf(__builtin_fmaf(wave_sum(v), inv_n, eps));
   float s1 = 0.f, s2 = 0.f;
 #pragma unroll
   for (int c = 0; c < kMaxChunksPerLane; ++c)
@@ -102,9 +106,8 @@ __device__ __forceinline__ void layernorm_backward_row(const float (&z)[kMaxChun
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float xhat = (z[c][i] - mean) * rstd;
-        const float a = dy[c][i] * gam[c][i];
-        dz[c][i] = rstd * (a - s1 - xhat * s2);
-        dgam[c][i] += dy[c][i] * xhat;
+        dz[c][i] = rstd * __builtin_fmaf(-s2, xhat, __builtin_fmaf(dy[c][i], gam[c][i], -s1));
+        dgam[c][i] = __builtin_fmaf(dy[c][i], xhat, dgam[c][i]);
         dbet[c][i] += dy[c][i];
       }
     }
@@ -116,13 +119,12 @@ __device__ __forceinline__ void load8(const _Float16* p, float (&dst)[8]) {
   for (int i = 0; i < 8; ++i) dst[i] = (float)v[i];
 }
 
-// the three per-wave column partials of a 4-wave workgroup -> ws[slab][0..2][cols], waves added in ascending order
-__device__ __forceinline__ void reduce_waves_to_slab(float (*red)[3][64 * kMaxChunksPerLane * 8],
-                                                     const float (&p0)[kMaxChunksPerLane][8],
-                                                     const float (&p1)[kMaxChunksPerLane][8],
-                                                     const float (&p2)[kMaxChunksPerLane][8], int lane, int wave,
-                                                     int n_chunks, int cols, float* __restrict__ slab,
-                                                     float (&total2)[kMaxChunksPerLane][8]) {
+// the N per-wave column partials of a 4-wave workgroup -> ws[slab][0..N-1][cols], waves added in ascending order; wave 0
+// is left holding the sums
+template <int N>
+__device__ __forceinline__ void reduce_waves_to_slab(float (*red)[N][64 * kMaxChunksPerLane * 8],
+                                                     float (&part)[N][kMaxChunksPerLane][8], int lane, int wave, int n_chunks,
+                                                     int cols, float* __restrict__ slab) {
   if (wave > 0) {
 #pragma unroll
     for (int c = 0; c < kMaxChunksPerLane; ++c) {
@@ -130,9 +132,8 @@ __device__ __forceinline__ void reduce_waves_to_slab(float (*red)[3][64 * kMaxCh
       if (chunk < n_chunks) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          red[wave - 1][0][chunk * 8 + i] = p0[c][i];
-          red[wave - 1][1][chunk * 8 + i] = p1[c][i];
-          red[wave - 1][2][chunk * 8 + i] = p2[c][i];
+#pragma unroll
+          for (int k = 0; k < N; ++k) red[wave - 1][k][chunk * 8 + i] = part[k][c][i];
         }
       }
     }
@@ -145,16 +146,11 @@ __device__ __forceinline__ void reduce_waves_to_slab(float (*red)[3][64 * kMaxCh
       if (chunk < n_chunks) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          float a = p0[c][i], b = p1[c][i], d = p2[c][i];
-          for (int w = 0; w < 3; ++w) {
-            a += red[w][0][chunk * 8 + i];
-            b += red[w][1][chunk * 8 + i];
-            d += red[w][2][chunk * 8 + i];
+#pragma unroll
+          for (int k = 0; k < N; ++k) {
+            for (int w = 0; w < 3; ++w) part[k][c][i] += red[w][k][chunk * 8 + i];
+            slab[k * cols + chunk * 8 + i] = part[k][c][i];
           }
-          slab[chunk * 8 + i] = a;
-          slab[cols + chunk * 8 + i] = b;
-          slab[2 * cols + chunk * 8 + i] = d;
-          total2[c][i] = d;
         }
       }
     }
@@ -165,16 +161,18 @@ __device__ __forceinline__ void reduce_waves_to_slab(float (*red)[3][64 * kMaxCh
 // workgroup = slab of rows_per_slab rows, wave = one row at a time; partials (dgamma, dbeta, dbias) -> ws[slab][3][cols]
 // DROP: the forward was LN(dropout(x + bias) + residual).  dz (to dz_out) is the gradient of the residual; the gradient of
 // x is dx = dz * keep * factor (to dx_out), and dbias is the column sum of dx before its rounding.
-__global__ __launch_bounds__(256) void bias_residual_layernorm_dropout_bwd(
+template <bool DROP>
+__device__ __forceinline__ void bias_residual_layernorm_bwd_body(
     const _Float16* __restrict__ dy_in, const _Float16* __restrict__ xin, const _Float16* __restrict__ bias,
     const _Float16* __restrict__ residual, const _Float16* __restrict__ gamma, float eps, long long rows, int cols,
     long long rows_per_slab, _Float16* __restrict__ dz_out, _Float16* __restrict__ dx_out, float* __restrict__ ws,
-    DropoutParams drop) {
+    const DropoutParams& drop) {
   __shared__ float red[3][3][64 * kMaxChunksPerLane * 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_chunks = cols >> 3;
   float gam[kMaxChunksPerLane][8], bia[kMaxChunksPerLane][8];
-  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dbia[kMaxChunksPerLane][8];
+  float part[3][kMaxChunksPerLane][8];                 // dgamma, dbeta, dbias
+  auto &dgam = part[0], &dbet = part[1], &dbia = part[2];
 #pragma unroll
   for (int c = 0; c < kMaxChunksPerLane; ++c) {
     const int chunk = lane + 64 * c;
@@ -189,7 +187,7 @@ __global__ __launch_bounds__(256) void bias_residual_layernorm_dropout_bwd(
   const long long row1 = row0 + rows_per_slab < rows ? row0 + rows_per_slab : rows;
   for (long long row = row0 + wave; row < row1; row += 4) {
     float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
-    Philox4 bits[kMaxChunksPerLane];                   // the row's decisions: read again for dx
+    Philox4 bits[kMaxChunksPerLane];                   // (DROP only) the row's decisions: read again for dx
 #pragma unroll
     for (int c = 0; c < kMaxChunksPerLane; ++c) {
       const int chunk = lane + 64 * c;
@@ -198,10 +196,15 @@ __global__ __launch_bounds__(256) void bias_residual_layernorm_dropout_bwd(
         load8(xin + row * cols + chunk * 8, a);
         load8(residual + row * cols + chunk * 8, r);
         load8(dy_in + row * cols + chunk * 8, dy[c]);
-        bits[c] = dropout_hidden_call(drop, (uint32_t)row, (uint32_t)chunk);
+        if constexpr (DROP) {
+          bits[c] = dropout_hidden_call(drop, (uint32_t)row, (uint32_t)chunk);
 #pragma unroll
-        for (int i = 0; i < 8; ++i)   // the forward's expression
-          z[c][i] = (dropout_hidden_keep(drop, bits[c], i) ? (a[i] + bia[c][i]) * drop.factor : 0.f) + r[i];
+          for (int i = 0; i < 8; ++i)   // the forward's expression
+            z[c][i] = (dropout_hidden_keep(drop, bits[c], i) ? (a[i] + bia[c][i]) * drop.factor : 0.f) + r[i];
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) z[c][i] = a[i] + bia[c][i] + r[i];
+        }
       }
     }
     layernorm_backward_row(z, dy, gam, lane, n_chunks, cols, eps, dz, dgam, dbet);
@@ -209,22 +212,30 @@ __global__ __launch_bounds__(256) void bias_residual_layernorm_dropout_bwd(
     for (int c = 0; c < kMaxChunksPerLane; ++c) {
       const int chunk = lane + 64 * c;
       if (chunk < n_chunks) {
-        f16x8 o, ox;
+        f16x8 o;
+        if constexpr (DROP) {
+          f16x8 ox;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          // a dropped element has no gradient, whatever dz is (0 * inf would be NaN)
-          const float dx = dropout_hidden_keep(drop, bits[c], i) ? dz[c][i] * drop.factor : 0.f;
-          o[i] = (_Float16)dz[c][i];
-          ox[i] = (_Float16)dx;
-          dbia[c][i] += dx;
+          for (int i = 0; i < 8; ++i) {
+            // a dropped element has no gradient, whatever dz is (0 * inf would be NaN)
+            const float dx = dropout_hidden_keep(drop, bits[c], i) ? dz[c][i] * drop.factor : 0.f;
+            o[i] = (_Float16)dz[c][i];
+            ox[i] = (_Float16)dx;
+            dbia[c][i] += dx;
+          }
+          *(f16x8*)(dx_out + row * cols + chunk * 8) = ox;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            o[i] = (_Float16)dz[c][i];
+            dbia[c][i] += dz[c][i];
+          }
         }
-        *(f16x8*)(dx_out + row * cols + chunk * 8) = ox;
         *(f16x8*)(dz_out + row * cols + chunk * 8) = o;
       }
     }
   }
-  float unused[kMaxChunksPerLane][8];
-  reduce_waves_to_slab(red, dgam, dbet, dbia, lane, wave, n_chunks, cols, ws + (long long)blockIdx.x * 3 * cols, unused);
+  reduce_waves_to_slab<3>(red, part, lane, wave, n_chunks, cols, ws + (long long)blockIdx.x * 3 * cols);
 }
 
 __global__ __launch_bounds__(256) void bias_residual_layernorm_bwd(const _Float16* __restrict__ dy_in,
@@ -234,54 +245,17 @@ __global__ __launch_bounds__(256) void bias_residual_layernorm_bwd(const _Float1
                                                                    const _Float16* __restrict__ gamma, float eps,
                                                                    long long rows, int cols, long long rows_per_slab,
                                                                    _Float16* __restrict__ dz_out, float* __restrict__ ws) {
-  __shared__ float red[3][3][64 * kMaxChunksPerLane * 8];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n_chunks = cols >> 3;
-  float gam[kMaxChunksPerLane][8], bia[kMaxChunksPerLane][8];
-  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dbia[kMaxChunksPerLane][8];
-#pragma unroll
-  for (int c = 0; c < kMaxChunksPerLane; ++c) {
-    const int chunk = lane + 64 * c;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gam[c][i] = bia[c][i] = dgam[c][i] = dbet[c][i] = dbia[c][i] = 0.f;
-    if (chunk < n_chunks) {
-      load8(gamma + chunk * 8, gam[c]);
-      load8(bias + chunk * 8, bia[c]);
-    }
-  }
-  const long long row0 = (long long)blockIdx.x * rows_per_slab;
-  const long long row1 = row0 + rows_per_slab < rows ? row0 + rows_per_slab : rows;
-  for (long long row = row0 + wave; row < row1; row += 4) {
-    float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
-#pragma unroll
-    for (int c = 0; c < kMaxChunksPerLane; ++c) {
-      const int chunk = lane + 64 * c;
-      if (chunk < n_chunks) {
-        float a[8], r[8];
-        load8(xin + row * cols + chunk * 8, a);
-        load8(residual + row * cols + chunk * 8, r);
-        load8(dy_in + row * cols + chunk * 8, dy[c]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) z[c][i] = a[i] + bia[c][i] + r[i];
-      }
-    }
-    layernorm_backward_row(z, dy, gam, lane, n_chunks, cols, eps, dz, dgam, dbet);
-#pragma unroll
-    for (int c = 0; c < kMaxChunksPerLane; ++c) {
-      const int chunk = lane + 64 * c;
-      if (chunk < n_chunks) {
-        f16x8 o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          o[i] = (_Float16)dz[c][i];
-          dbia[c][i] += dz[c][i];
-        }
-        *(f16x8*)(dz_out + row * cols + chunk * 8) = o;
-      }
-    }
-  }
-  float unused[kMaxChunksPerLane][8];
-  reduce_waves_to_slab(red, dgam, dbet, dbia, lane, wave, n_chunks, cols, ws + (long long)blockIdx.x * 3 * cols, unused);
+  bias_residual_layernorm_bwd_body<false>(dy_in, xin, bias, residual, gamma, eps, rows, cols, rows_per_slab, dz_out, nullptr, ws,
+                                          DropoutParams{});
+}
+
+__global__ __launch_bounds__(256) void bias_residual_layernorm_dropout_bwd(
+    const _Float16* __restrict__ dy_in, const _Float16* __restrict__ xin, const _Float16* __restrict__ bias,
+    const _Float16* __restrict__ residual, const _Float16* __restrict__ gamma, float eps, long long rows, int cols,
+    long long rows_per_slab, _Float16* __restrict__ dz_out, _Float16* __restrict__ dx_out, float* __restrict__ ws,
+    DropoutParams drop) {
+  bias_residual_layernorm_bwd_body<true>(dy_in, xin, bias, residual, gamma, eps, rows, cols, rows_per_slab, dz_out, dx_out, ws,
+                                         drop);
 }
 
 // ---- embedding + LayerNorm backward --------------------------------------------------------------------------------------
@@ -289,32 +263,44 @@ __global__ __launch_bounds__(256) void bias_residual_layernorm_bwd(const _Float1
 // row of its id (fp32 atomics, the one non-deterministic output) and into the position's own sum; d_pos[s] is final when
 // the workgroup ends, and (dgamma, dbeta, d_pos[s]) are slab s of the workspace: the type-0 gradient is the sum of the
 // position gradients.
-__global__ __launch_bounds__(256) void embed_layernorm_bwd(const _Float16* __restrict__ dy_in, const long long* __restrict__ ids,
-                                                           const int* __restrict__ cu_seqlens, int batch, int seq_len,
-                                                           int hidden, const _Float16* __restrict__ word, long long vocab,
-                                                           const _Float16* __restrict__ pos,
-                                                           const _Float16* __restrict__ type0,
-                                                           const _Float16* __restrict__ gamma, float eps, long long n_tokens,
-                                                           float* __restrict__ d_word, float* __restrict__ d_pos,
-                                                           float* __restrict__ ws) {
-  __shared__ float red[3][3][64 * kMaxChunksPerLane * 8];
+// TYPED (the reader's [CLS] q [SEP] p [SEP]): a fourth per-wave accumulator.  The position's sum is kept in two parts, the
+// tokens of type 0 and those of type 1 (a type id outside [0, n_types) read row 0 in the forward and counts as type 0 here).
+// Slab s of the workspace is (dgamma, dbeta, d_types[0], d_types[1]) of position s; d_pos[s] += part 0 + part 1.  With
+// type_ids == nullptr part 1 is +0 and every sum is the sum the untyped kernel takes, in its order.
+template <bool TYPED>
+__device__ __forceinline__ void embed_layernorm_bwd_body(
+    const _Float16* __restrict__ dy_in, const long long* __restrict__ ids, const long long* __restrict__ type_ids,
+    const int* __restrict__ cu_seqlens, int batch, int seq_len, int hidden, const _Float16* __restrict__ word, long long vocab,
+    const _Float16* __restrict__ pos, const _Float16* __restrict__ type_table, int n_types,
+    const _Float16* __restrict__ gamma, float eps, long long n_tokens, float* __restrict__ d_word, float* __restrict__ d_pos,
+    float* __restrict__ ws) {
+  constexpr int N = TYPED ? 4 : 3;
+  __shared__ float red[3][N][64 * kMaxChunksPerLane * 8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_chunks = hidden >> 3;
   const int s = blockIdx.x;
-  float gam[kMaxChunksPerLane][8], base[kMaxChunksPerLane][8];   // base = pos[s] + type[0]
-  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dpos[kMaxChunksPerLane][8];
+  float gam[kMaxChunksPerLane][8], base[kMaxChunksPerLane][8];   // base = pos[s] (TYPED) or pos[s] + type[0]
+  float part[N][kMaxChunksPerLane][8];                           // dgamma, dbeta, the position's sum (TYPED: by type)
 #pragma unroll
   for (int c = 0; c < kMaxChunksPerLane; ++c) {
     const int chunk = lane + 64 * c;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) gam[c][i] = base[c][i] = dgam[c][i] = dbet[c][i] = dpos[c][i] = 0.f;
-    if (chunk < n_chunks) {
-      float p[8], t[8];
-      load8(gamma + chunk * 8, gam[c]);
-      load8(pos + (long long)s * hidden + chunk * 8, p);
-      load8(type0 + chunk * 8, t);
+    for (int i = 0; i < 8; ++i) {
+      gam[c][i] = base[c][i] = 0.f;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) base[c][i] = p[i] + t[i];
+      for (int k = 0; k < N; ++k) part[k][c][i] = 0.f;
+    }
+    if (chunk < n_chunks) {
+      load8(gamma + chunk * 8, gam[c]);
+      if constexpr (TYPED) {
+        load8(pos + (long long)s * hidden + chunk * 8, base[c]);
+      } else {
+        float p[8], t[8];
+        load8(pos + (long long)s * hidden + chunk * 8, p);
+        load8(type_table + chunk * 8, t);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) base[c][i] = p[i] + t[i];
+      }
     }
   }
   for (int b = wave; b < batch; b += 4) {
@@ -323,6 +309,11 @@ __global__ __launch_bounds__(256) void embed_layernorm_bwd(const _Float16* __res
     if (s >= cu_seqlens[b + 1] - first || row >= n_tokens) continue;   // wave-uniform
     long long id = ids[(long long)b * seq_len + s];
     if (id < 0 || id >= vocab) id = 0;   // the forward read row 0 for such an id
+    long long tt = 0;
+    if constexpr (TYPED) {
+      if (type_ids) tt = type_ids[(long long)b * seq_len + s];
+      if (tt < 0 || tt >= n_types) tt = 0;   // and row 0 of the type table
+    }
     float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
 #pragma unroll
     for (int c = 0; c < kMaxChunksPerLane; ++c) {
@@ -331,159 +322,65 @@ __global__ __launch_bounds__(256) void embed_layernorm_bwd(const _Float16* __res
         float w[8];
         load8(word + id * hidden + chunk * 8, w);
         load8(dy_in + row * hidden + chunk * 8, dy[c]);
+        if constexpr (TYPED) {
+          float t[8];
+          load8(type_table + tt * hidden + chunk * 8, t);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) z[c][i] = w[i] + base[c][i];
+          for (int i = 0; i < 8; ++i) z[c][i] = w[i] + (base[c][i] + t[i]);   // the untyped association
+        } else {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) z[c][i] = w[i] + base[c][i];
+        }
       }
     }
-    layernorm_backward_row(z, dy, gam, lane, n_chunks, hidden, eps, dz, dgam, dbet);
+    layernorm_backward_row(z, dy, gam, lane, n_chunks, hidden, eps, dz, part[0], part[1]);
 #pragma unroll
     for (int c = 0; c < kMaxChunksPerLane; ++c) {
       const int chunk = lane + 64 * c;
       if (chunk < n_chunks) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-          dpos[c][i] += dz[c][i];
+          if (!TYPED || tt == 0) part[2][c][i] += dz[c][i];   // wave-uniform
+          else part[N - 1][c][i] += dz[c][i];
           atomicAdd(d_word + id * hidden + chunk * 8 + i, dz[c][i]);
         }
       }
     }
   }
-  float total[kMaxChunksPerLane][8];
-  reduce_waves_to_slab(red, dgam, dbet, dpos, lane, wave, n_chunks, hidden, ws + (long long)s * 3 * hidden, total);
+  reduce_waves_to_slab<N>(red, part, lane, wave, n_chunks, hidden, ws + (long long)s * N * hidden);
   if (wave == 0) {
 #pragma unroll
     for (int c = 0; c < kMaxChunksPerLane; ++c) {
       const int chunk = lane + 64 * c;
       if (chunk < n_chunks) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) d_pos[(long long)s * hidden + chunk * 8 + i] += total[c][i];
+        for (int i = 0; i < 8; ++i)
+          d_pos[(long long)s * hidden + chunk * 8 + i] += TYPED ? part[2][c][i] + part[N - 1][c][i] : part[2][c][i];
       }
     }
   }
 }
 
-// ---- embedding + LayerNorm backward with token types (the reader's [CLS] q [SEP] p [SEP]) ---------------------------------
-// embed_layernorm_bwd with a fourth per-wave accumulator: the position's sum is kept in two parts, the tokens of type 0
-// and those of type 1 (a type id outside [0, n_types) read row 0 in the forward and counts as type 0 here).  Slab s of the
-// workspace is (dgamma, dbeta, d_types[0], d_types[1]) of position s; d_pos[s] = part 0 + part 1.  With type_ids == nullptr
-// part 1 is +0 and every sum is the sum embed_layernorm_bwd takes, in its order.
+__global__ __launch_bounds__(256) void embed_layernorm_bwd(const _Float16* __restrict__ dy_in, const long long* __restrict__ ids,
+                                                           const int* __restrict__ cu_seqlens, int batch, int seq_len,
+                                                           int hidden, const _Float16* __restrict__ word, long long vocab,
+                                                           const _Float16* __restrict__ pos,
+                                                           const _Float16* __restrict__ type0,
+                                                           const _Float16* __restrict__ gamma, float eps, long long n_tokens,
+                                                           float* __restrict__ d_word, float* __restrict__ d_pos,
+                                                           float* __restrict__ ws) {
+  embed_layernorm_bwd_body<false>(dy_in, ids, nullptr, cu_seqlens, batch, seq_len, hidden, word, vocab, pos, type0, 1, gamma,
+                                  eps, n_tokens, d_word, d_pos, ws);
+}
+
 __global__ __launch_bounds__(256) void embed_layernorm_typed_bwd(
     const _Float16* __restrict__ dy_in, const long long* __restrict__ ids, const long long* __restrict__ type_ids,
     const int* __restrict__ cu_seqlens, int batch, int seq_len, int hidden, const _Float16* __restrict__ word, long long vocab,
     const _Float16* __restrict__ pos, const _Float16* __restrict__ type_table, int n_types,
     const _Float16* __restrict__ gamma, float eps, long long n_tokens, float* __restrict__ d_word, float* __restrict__ d_pos,
     float* __restrict__ ws) {
-  __shared__ float red[3][4][64 * kMaxChunksPerLane * 8];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n_chunks = hidden >> 3;
-  const int s = blockIdx.x;
-  float gam[kMaxChunksPerLane][8], posr[kMaxChunksPerLane][8];
-  float dgam[kMaxChunksPerLane][8], dbet[kMaxChunksPerLane][8], dty0[kMaxChunksPerLane][8], dty1[kMaxChunksPerLane][8];
-#pragma unroll
-  for (int c = 0; c < kMaxChunksPerLane; ++c) {
-    const int chunk = lane + 64 * c;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gam[c][i] = posr[c][i] = dgam[c][i] = dbet[c][i] = dty0[c][i] = dty1[c][i] = 0.f;
-    if (chunk < n_chunks) {
-      load8(gamma + chunk * 8, gam[c]);
-      load8(pos + (long long)s * hidden + chunk * 8, posr[c]);
-    }
-  }
-  for (int b = wave; b < batch; b += 4) {
-    const int first = cu_seqlens[b];
-    const long long row = (long long)first + s;
-    if (s >= cu_seqlens[b + 1] - first || row >= n_tokens) continue;   // wave-uniform
-    long long id = ids[(long long)b * seq_len + s];
-    if (id < 0 || id >= vocab) id = 0;   // the forward read row 0 for such an id
-    long long tt = type_ids ? type_ids[(long long)b * seq_len + s] : 0;
-    if (tt < 0 || tt >= n_types) tt = 0;   // and row 0 of the type table
-    float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
-#pragma unroll
-    for (int c = 0; c < kMaxChunksPerLane; ++c) {
-      const int chunk = lane + 64 * c;
-      if (chunk < n_chunks) {
-        float w[8], t[8];
-        load8(word + id * hidden + chunk * 8, w);
-        load8(type_table + tt * hidden + chunk * 8, t);
-        load8(dy_in + row * hidden + chunk * 8, dy[c]);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) z[c][i] = w[i] + (posr[c][i] + t[i]);   // embed_layernorm_bwd's association
-      }
-    }
-    layernorm_backward_row(z, dy, gam, lane, n_chunks, hidden, eps, dz, dgam, dbet);
-#pragma unroll
-    for (int c = 0; c < kMaxChunksPerLane; ++c) {
-      const int chunk = lane + 64 * c;
-      if (chunk < n_chunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          if (tt == 0) dty0[c][i] += dz[c][i];   // wave-uniform
-          else dty1[c][i] += dz[c][i];
-          atomicAdd(d_word + id * hidden + chunk * 8 + i, dz[c][i]);
-        }
-      }
-    }
-  }
-  // the four per-wave partials -> slab s, waves added in ascending order (reduce_waves_to_slab with one more quantity)
-  if (wave > 0) {
-#pragma unroll
-    for (int c = 0; c < kMaxChunksPerLane; ++c) {
-      const int chunk = lane + 64 * c;
-      if (chunk < n_chunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          red[wave - 1][0][chunk * 8 + i] = dgam[c][i];
-          red[wave - 1][1][chunk * 8 + i] = dbet[c][i];
-          red[wave - 1][2][chunk * 8 + i] = dty0[c][i];
-          red[wave - 1][3][chunk * 8 + i] = dty1[c][i];
-        }
-      }
-    }
-  }
-  __syncthreads();
-  if (wave == 0) {
-    float* __restrict__ slab = ws + (long long)s * 4 * hidden;
-#pragma unroll
-    for (int c = 0; c < kMaxChunksPerLane; ++c) {
-      const int chunk = lane + 64 * c;
-      if (chunk < n_chunks) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          float a = dgam[c][i], b = dbet[c][i], t0 = dty0[c][i], t1 = dty1[c][i];
-          for (int w = 0; w < 3; ++w) {
-            a += red[w][0][chunk * 8 + i];
-            b += red[w][1][chunk * 8 + i];
-            t0 += red[w][2][chunk * 8 + i];
-            t1 += red[w][3][chunk * 8 + i];
-          }
-          slab[chunk * 8 + i] = a;
-          slab[hidden + chunk * 8 + i] = b;
-          slab[2 * hidden + chunk * 8 + i] = t0;
-          slab[3 * hidden + chunk * 8 + i] = t1;
-          d_pos[(long long)s * hidden + chunk * 8 + i] += t0 + t1;
-        }
-      }
-    }
-  }
-}
-
-// out_k[c] += sum over the slabs, in ascending order, of ws[slab][k][c], k < 4 (reduce_slabs' compensated sum); a null
-// out_k is skipped
-__global__ __launch_bounds__(256) void reduce_slabs_typed(const float* __restrict__ ws, int n_slabs, int cols, float* out0,
-                                                          float* out1, float* out2, float* out3) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 4 * cols) return;
-  const int k = t / cols, c = t - k * cols;
-  float* out = k == 0 ? out0 : (k == 1 ? out1 : (k == 2 ? out2 : out3));
-  if (!out) return;
-  float s = 0.f, comp = 0.f;
-  for (int b = 0; b < n_slabs; ++b) {
-    const float y = ws[((long long)b * 4 + k) * cols + c] - comp;
-    const float t = s + y;
-    comp = (t - s) - y;
-    s = t;
-  }
-  out[c] = out[c] + s;
+  embed_layernorm_bwd_body<true>(dy_in, ids, type_ids, cu_seqlens, batch, seq_len, hidden, word, vocab, pos, type_table,
+                                 n_types, gamma, eps, n_tokens, d_word, d_pos, ws);
 }
 
 // ---- column-owning kernels: column sum, bias + GELU backward --------------------------------------------------------------
@@ -844,18 +741,17 @@ __global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dq(const _Float1
   attention_bwd_dq_body<true>(qkv, qkv_bias, dctx, cu_seqlens, max_seq_len, n_heads, n_qc, n_tokens, dqkv, ws_lse, ws_delta, drop);
 }
 
-// attention_bwd_dkv with dropout (a kernel of its own: as a template instance the existing kernel's register allocation moved)
-__global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dkv(const _Float16* __restrict__ qkv,
-                                                                    const _Float16* __restrict__ qkv_bias,
-                                                                    const _Float16* __restrict__ dctx,
-                                                                    const int* __restrict__ cu_seqlens, int max_seq_len,
-                                                                    int n_heads, int n_kc, long long n_tokens,
-                                                                    _Float16* __restrict__ dqkv, const float* __restrict__ ws_lse,
-                                                                    const float* __restrict__ ws_delta, DropoutParams drop) {
+// dob_lds (DROP only; [kQChunk] floats of LDS, the kernel's own): dO_q . b_v of the staged queries
+template <bool DROP>
+__device__ __forceinline__ void attention_bwd_dkv_body(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
+                                                       const _Float16* __restrict__ dctx, const int* __restrict__ cu_seqlens,
+                                                       int max_seq_len, int n_heads, int n_kc, long long n_tokens,
+                                                       _Float16* __restrict__ dqkv, const float* __restrict__ ws_lse,
+                                                       const float* __restrict__ ws_delta, float* dob_lds,
+                                                       const DropoutParams& drop) {
   constexpr int t_stride = kQChunk + kTPad;
   __shared__ __attribute__((aligned(16))) _Float16 smem[2 * kQChunk * kRowStride + 2 * kHeadDim * t_stride];
   __shared__ float lse_lds[kQChunk], delta_lds[kQChunk];
-  __shared__ float dob_lds[kQChunk];                   // dO_q . b_v of the staged queries
   _Float16* q_lds = smem;                                                   // [64][72]  Q + b_q
   _Float16* do_lds = smem + kQChunk * kRowStride;                           // [64][72]  d_ctx
   _Float16* qt_lds = smem + 2 * kQChunk * kRowStride;                       // [64][68]  (Q + b_q)^T
@@ -905,7 +801,7 @@ __global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dkv(const _Float
           dreg[it] = *(const f16x8*)(dbase + (long long)row * hidden + c * 8);
         }
       }
-      {
+      if constexpr (DROP) {
         // the eight pieces of a row sit in eight consecutive lanes
 #pragma unroll
         for (int it = 0; it < kIters; ++it) {
@@ -953,7 +849,7 @@ __global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dkv(const _Float
         dp = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(drow + j * 16), vf[j], dp, 0, 0, 0);
       }
       f16x8 pf[2], dsf[2];
-      {
+      if constexpr (DROP) {
         // registers 4g .. 4g+3 are four consecutive queries of the lane's key: two generator calls (a call covers queries
         // 2n, 2n + 1).  pf holds the kept probabilities; the factor enters dV once, at the store
 #pragma unroll
@@ -971,6 +867,15 @@ __global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dkv(const _Float
             dsf[r >> 3][r & 7] = (_Float16)(p * (dpd - delta_lds[qi]));
           }
         }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int qi = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -lse_lds[qi]));
+          p = key < len ? p : 0.f;                     // a key row that does not exist was masked in the forward
+          pf[r >> 3][r & 7] = (_Float16)p;
+          dsf[r >> 3][r & 7] = (_Float16)(p * (dp[r] - delta_lds[qi]));
+        }
       }
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
@@ -987,7 +892,7 @@ __global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dkv(const _Float
   _Float16* tile = smem + wave * 32 * kRowStride;      // 4 x 32 x 72 = the two row-major arrays
   _Float16* out = dqkv + tok0 * row_stride + head * kHeadDim;
   store_tile(dk0, dk1, 0.125f, tile, lane, out + hidden, row_stride, kb * 32, len);
-  store_tile(dv0, dv1, drop.factor, tile, lane, out + 2 * hidden, row_stride, kb * 32, len);
+  store_tile(dv0, dv1, DROP ? drop.factor : 1.0f, tile, lane, out + 2 * hidden, row_stride, kb * 32, len);
 }
 
 __global__ __launch_bounds__(256, 2) void attention_bwd_dkv(const _Float16* __restrict__ qkv, const _Float16* __restrict__ qkv_bias,
@@ -995,113 +900,20 @@ __global__ __launch_bounds__(256, 2) void attention_bwd_dkv(const _Float16* __re
                                                             int max_seq_len, int n_heads, int n_kc, long long n_tokens,
                                                             _Float16* __restrict__ dqkv, const float* __restrict__ ws_lse,
                                                             const float* __restrict__ ws_delta) {
-  constexpr int t_stride = kQChunk + kTPad;
-  __shared__ __attribute__((aligned(16))) _Float16 smem[2 * kQChunk * kRowStride + 2 * kHeadDim * t_stride];
-  __shared__ float lse_lds[kQChunk], delta_lds[kQChunk];
-  _Float16* q_lds = smem;                                                   // [64][72]  Q + b_q
-  _Float16* do_lds = smem + kQChunk * kRowStride;                           // [64][72]  d_ctx
-  _Float16* qt_lds = smem + 2 * kQChunk * kRowStride;                       // [64][68]  (Q + b_q)^T
-  _Float16* dot_lds = smem + 2 * kQChunk * kRowStride + kHeadDim * t_stride; // [64][68]  d_ctx^T
-  const int pair = blockIdx.x / n_kc, kc = blockIdx.x - pair * n_kc;
-  const int b = pair / n_heads, head = pair - b * n_heads;
-  const int hidden = n_heads * kHeadDim;
-  const long long row_stride = 3ll * hidden;
-  const long long tok0 = cu_seqlens[b];
-  int len = cu_seqlens[b + 1] - cu_seqlens[b];
-  len = len < 1 ? 1 : (len > max_seq_len ? max_seq_len : len);
-  if (tok0 < 0 || tok0 + len > n_tokens) return;
-  if (kc * kChunk >= len) return;                      // (the whole workgroup: no barrier has been met)
-  const _Float16* base = qkv + tok0 * row_stride + head * kHeadDim;
-  const _Float16* dbase = dctx + tok0 * hidden + head * kHeadDim;
+  attention_bwd_dkv_body<false>(qkv, qkv_bias, dctx, cu_seqlens, max_seq_len, n_heads, n_kc, n_tokens, dqkv, ws_lse, ws_delta,
+                                nullptr, DropoutParams{});
+}
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, half = lane >> 5;
-  const int kb = kc * 4 + wave;
-  const bool active = kb * 32 < len;                   // wave-uniform
-  const int key = kb * 32 + li;
-  const f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-  f16x8 kf[4], vf[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    kf[j] = vf[j] = zero8;
-    if (key < len) {
-      const _Float16* src = base + key * row_stride + (2 * j + half) * 8;
-      kf[j] = *(const f16x8*)(src + hidden);           // (no key bias: the forward drops it)
-      vf[j] = *(const f16x8*)(src + 2 * hidden);
-    }
-  }
-  f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
-  const int n_qchunks = (len + kQChunk - 1) / kQChunk;
-  for (int qc = 0; qc < n_qchunks; ++qc) {
-    if (qc) __syncthreads();                           // every wave is done with the previous chunk
-    {
-      constexpr int kIters = kQChunk * 8 / 256;
-      f16x8 qreg[kIters], dreg[kIters];
-#pragma unroll
-      for (int it = 0; it < kIters; ++it) {
-        const int i = tid + it * 256;
-        const int row = qc * kQChunk + (i >> 3), c = i & 7;
-        qreg[it] = dreg[it] = zero8;
-        if (row < len) {
-          qreg[it] = *(const f16x8*)(base + row * row_stride + c * 8);
-          if (qkv_bias) qreg[it] = qreg[it] + *(const f16x8*)(qkv_bias + head * kHeadDim + c * 8);
-          dreg[it] = *(const f16x8*)(dbase + (long long)row * hidden + c * 8);
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < kIters; ++it) {
-        const int i = tid + it * 256;
-        const int r = i >> 3, c = i & 7;
-        *(f16x8*)(q_lds + r * kRowStride + c * 8) = qreg[it];
-        *(f16x8*)(do_lds + r * kRowStride + c * 8) = dreg[it];
-        stage_transposed(qreg[it], r, c, qt_lds, t_stride);
-        stage_transposed(dreg[it], r, c, dot_lds, t_stride);
-      }
-      if (tid < kQChunk) {
-        const int row = qc * kQChunk + tid;
-        // a query row that does not exist has P = exp2(s - inf) = 0
-        lse_lds[tid] = row < len ? ws_lse[(long long)head * n_tokens + tok0 + row] : __builtin_inff();
-        delta_lds[tid] = row < len ? ws_delta[(long long)head * n_tokens + tok0 + row] : 0.f;
-      }
-    }
-    __syncthreads();
-    if (!active) continue;
-    const int rows_here = len - qc * kQChunk < kQChunk ? len - qc * kQChunk : kQChunk;
-    const int tiles_here = (rows_here + 31) >> 5;
-    for (int qt = 0; qt < tiles_here; ++qt) {
-      // S = Q K^T and dP = dO V^T of query tile qt: lane = key, registers = queries (r & 3) + 8 (r >> 2) + 4 half
-      f32x16 st = {0}, dp = {0};
-      const _Float16* qrow = q_lds + (qt * 32 + li) * kRowStride + half * 8;
-      const _Float16* drow = do_lds + (qt * 32 + li) * kRowStride + half * 8;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(qrow + j * 16), kf[j], st, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_f16(*(const f16x8*)(drow + j * 16), vf[j], dp, 0, 0, 0);
-      }
-      f16x8 pf[2], dsf[2];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int qi = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        float p = __builtin_amdgcn_exp2f(__builtin_fmaf(st[r], kExpScale, -lse_lds[qi]));
-        p = key < len ? p : 0.f;                       // a key row that does not exist was masked in the forward
-        pf[r >> 3][r & 7] = (_Float16)p;
-        dsf[r >> 3][r & 7] = (_Float16)(p * (dp[r] - delta_lds[qi]));
-      }
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        const int q0 = qt * 32 + 16 * jj + 4 * half;
-        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(dot_lds, t_stride, li, q0), pf[jj], dv0, 0, 0, 0);
-        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(dot_lds, t_stride, 32 + li, q0), pf[jj], dv1, 0, 0, 0);
-        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(qt_lds, t_stride, li, q0), dsf[jj], dk0, 0, 0, 0);
-        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(transposed_fragment(qt_lds, t_stride, 32 + li, q0), dsf[jj], dk1, 0, 0, 0);
-      }
-    }
-  }
-  __syncthreads();                                     // the last chunk is dead: Q and d_ctx rows become the output staging tiles
-  if (!active) return;
-  _Float16* tile = smem + wave * 32 * kRowStride;      // 4 x 32 x 72 = the two row-major arrays
-  _Float16* out = dqkv + tok0 * row_stride + head * kHeadDim;
-  store_tile(dk0, dk1, 0.125f, tile, lane, out + hidden, row_stride, kb * 32, len);
-  store_tile(dv0, dv1, 1.0f, tile, lane, out + 2 * hidden, row_stride, kb * 32, len);
+__global__ __launch_bounds__(256, 2) void attention_dropout_bwd_dkv(const _Float16* __restrict__ qkv,
+                                                                    const _Float16* __restrict__ qkv_bias,
+                                                                    const _Float16* __restrict__ dctx,
+                                                                    const int* __restrict__ cu_seqlens, int max_seq_len,
+                                                                    int n_heads, int n_kc, long long n_tokens,
+                                                                    _Float16* __restrict__ dqkv, const float* __restrict__ ws_lse,
+                                                                    const float* __restrict__ ws_delta, DropoutParams drop) {
+  __shared__ float dob_lds[kQChunk];
+  attention_bwd_dkv_body<true>(qkv, qkv_bias, dctx, cu_seqlens, max_seq_len, n_heads, n_kc, n_tokens, dqkv, ws_lse, ws_delta,
+                               dob_lds, drop);
 }
 
 // ---- in-batch loss gradient -------------------------------------------------------------------------------------------------
@@ -1212,6 +1024,102 @@ int launch_reduce(const float* ws, int n_slabs, int n_k, int cols, float* o0, fl
   return PROQA_OK;
 }
 
+// The launchers of the operator pairs.  An exported function checks its own pointers (and makes its DropoutParams), names
+// itself in `op` for the messages and says how much workspace it asks for; sizes, the empty cases and the launches are here.
+
+// drop == nullptr: without dropout (dx unused)
+static int launch_bias_residual_layernorm_backward(const char* op, const void* dy, const void* x, const void* bias,
+                                                   const void* residual, const void* gamma, float eps, int64_t rows, int cols,
+                                                   const DropoutParams* drop, void* dx, void* dz, float* dgamma, float* dbeta,
+                                                   float* dbias, void* ws, size_t ws_bytes, size_t ws_need, void* stream) {
+  if (rows < 0 || cols <= 0 || cols % 8 || cols > 64 * kMaxChunksPerLane * 8)
+    return fail(PROQA_EINVAL, "%s: cols=%d must be a multiple of 8 and <= %d%s", op, cols, 64 * kMaxChunksPerLane * 8,
+                drop ? ", rows < 2^32" : "");
+  if (ws_bytes < ws_need) return fail(PROQA_EINVAL, "%s: workspace too small", op);
+  hipStream_t st = as_stream(stream);
+  if (rows == 0) {
+    for (float* p : {dgamma, dbeta, dbias}) PROQA_HIP(hipMemsetAsync(p, 0, (size_t)cols * sizeof(float), st));
+    return PROQA_OK;
+  }
+  int64_t per;
+  const int n_slabs = slabs_for(rows, 16, &per);
+  if (drop)
+    hipLaunchKernelGGL(bias_residual_layernorm_dropout_bwd, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)dy,
+                       (const _Float16*)x, (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma, eps,
+                       (long long)rows, cols, (long long)per, (_Float16*)dz, (_Float16*)dx, (float*)ws, *drop);
+  else
+    hipLaunchKernelGGL(bias_residual_layernorm_bwd, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)dy,
+                       (const _Float16*)x, (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma, eps,
+                       (long long)rows, cols, (long long)per, (_Float16*)dz, (float*)ws);
+  PROQA_LAUNCH_CHECK();
+  return launch_reduce((const float*)ws, n_slabs, 3, cols, dgamma, dbeta, dbias, nullptr, 0, st);
+}
+
+// typed: d_types is [n_types][hidden] and type_ids may be null; else d_types is the type-0 row alone (n_types, type_ids unused)
+static int launch_embed_layernorm_backward(const char* op, bool typed, const void* dy, const int64_t* ids,
+                                           const int64_t* type_ids, const int32_t* cu_seqlens, int batch, int seq_len,
+                                           int hidden, int64_t n_tokens, const void* word, int64_t vocab, const void* pos,
+                                           const void* type_emb, int n_types, const void* gamma, float eps, float* dgamma,
+                                           float* dbeta, float* d_word, float* d_pos, float* d_types, void* ws, size_t ws_bytes,
+                                           size_t ws_need, void* stream) {
+  if (batch < 0 || seq_len <= 0 || seq_len > kMaxSlabs || vocab <= 0 || n_tokens < 0)
+    return fail(PROQA_EINVAL, "%s: bad sizes (seq_len <= %d)", op, kMaxSlabs);
+  if (hidden <= 0 || hidden % 8 || hidden > 64 * kMaxChunksPerLane * 8)
+    return fail(PROQA_EINVAL, "%s: hidden=%d must be a multiple of 8 and <= %d", op, hidden, 64 * kMaxChunksPerLane * 8);
+  if (ws_bytes < ws_need) return fail(PROQA_EINVAL, "%s: workspace too small", op);
+  if (batch == 0 || n_tokens == 0) return PROQA_OK;
+  hipStream_t st = as_stream(stream);
+  if (typed)
+    hipLaunchKernelGGL(embed_layernorm_typed_bwd, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
+                       (const long long*)ids, (const long long*)type_ids, (const int*)cu_seqlens, batch, seq_len, hidden,
+                       (const _Float16*)word, (long long)vocab, (const _Float16*)pos, (const _Float16*)type_emb, n_types,
+                       (const _Float16*)gamma, eps, (long long)n_tokens, d_word, d_pos, (float*)ws);
+  else
+    hipLaunchKernelGGL(embed_layernorm_bwd, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
+                       (const long long*)ids, (const int*)cu_seqlens, batch, seq_len, hidden, (const _Float16*)word,
+                       (long long)vocab, (const _Float16*)pos, (const _Float16*)type_emb, (const _Float16*)gamma, eps,
+                       (long long)n_tokens, d_word, d_pos, (float*)ws);
+  PROQA_LAUNCH_CHECK();
+  // slab s is (dgamma, dbeta, the position's sum [by type]) of position s: the position sums add up to the type gradients
+  return launch_reduce((const float*)ws, seq_len, typed ? 4 : 3, hidden, dgamma, dbeta, d_types,
+                       typed && n_types == 2 ? d_types + hidden : nullptr, 1, st);
+}
+
+// drop == nullptr: without dropout
+static int launch_attention_backward(const char* op, const void* qkv, const void* qkv_bias, const void* d_ctx,
+                                     const int32_t* cu_seqlens, int batch, int max_seq_len, int n_heads, int64_t n_tokens,
+                                     const DropoutParams* drop, void* d_qkv, void* ws, size_t ws_bytes, size_t ws_need,
+                                     void* stream) {
+  if (batch < 0 || max_seq_len <= 0 || max_seq_len > 512 || n_heads <= 0 || n_tokens < 0)
+    return fail(PROQA_EINVAL, "%s: bad sizes (max_seq_len <= 512)", op);
+  if (ws_bytes < ws_need) return fail(PROQA_EINVAL, "%s: workspace too small", op);
+  if (batch == 0 || n_tokens == 0) return PROQA_OK;
+  hipStream_t st = as_stream(stream);
+  const int n_c = (max_seq_len + kChunk - 1) / kChunk;
+  const unsigned grid = (unsigned)batch * (unsigned)n_heads * (unsigned)n_c;
+  float* ws_lse = (float*)ws;
+  float* ws_delta = ws_lse + n_tokens * n_heads;
+  if (drop)
+    hipLaunchKernelGGL(attention_dropout_bwd_dq, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                       (const _Float16*)d_ctx, (const int*)cu_seqlens, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                       (_Float16*)d_qkv, ws_lse, ws_delta, *drop);
+  else
+    hipLaunchKernelGGL(attention_bwd_dq, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                       (const _Float16*)d_ctx, (const int*)cu_seqlens, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                       (_Float16*)d_qkv, ws_lse, ws_delta);
+  PROQA_LAUNCH_CHECK();
+  if (drop)
+    hipLaunchKernelGGL(attention_dropout_bwd_dkv, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                       (const _Float16*)d_ctx, (const int*)cu_seqlens, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                       (_Float16*)d_qkv, (const float*)ws_lse, (const float*)ws_delta, *drop);
+  else
+    hipLaunchKernelGGL(attention_bwd_dkv, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
+                       (const _Float16*)d_ctx, (const int*)cu_seqlens, max_seq_len, n_heads, n_c, (long long)n_tokens,
+                       (_Float16*)d_qkv, (const float*)ws_lse, (const float*)ws_delta);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
 }  // namespace
 }  // namespace proqa
 
@@ -1276,23 +1184,9 @@ int proqa_bias_residual_layernorm_backward_f16(const void* dy, const void* x, co
                                                float* dbeta, float* dbias, void* ws, size_t ws_bytes, void* stream) {
   if (!dy || !x || !bias || !residual || !gamma || !dz || !dgamma || !dbeta || !dbias || !ws)
     return fail(PROQA_EINVAL, "bias_residual_layernorm_backward: NULL argument");
-  if (rows < 0 || cols <= 0 || cols % 8 || cols > 64 * kMaxChunksPerLane * 8)
-    return fail(PROQA_EINVAL, "bias_residual_layernorm_backward: cols=%d must be a multiple of 8 and <= %d", cols,
-                64 * kMaxChunksPerLane * 8);
-  if (ws_bytes < proqa_backward_workspace_bytes(cols))
-    return fail(PROQA_EINVAL, "bias_residual_layernorm_backward: workspace too small");
-  hipStream_t st = as_stream(stream);
-  if (rows == 0) {
-    for (float* p : {dgamma, dbeta, dbias}) PROQA_HIP(hipMemsetAsync(p, 0, (size_t)cols * sizeof(float), st));
-    return PROQA_OK;
-  }
-  int64_t per;
-  const int n_slabs = slabs_for(rows, 16, &per);
-  hipLaunchKernelGGL(bias_residual_layernorm_bwd, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)dy,
-                     (const _Float16*)x, (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma, eps,
-                     (long long)rows, cols, (long long)per, (_Float16*)dz, (float*)ws);
-  PROQA_LAUNCH_CHECK();
-  return launch_reduce((const float*)ws, n_slabs, 3, cols, dgamma, dbeta, dbias, nullptr, 0, st);
+  return launch_bias_residual_layernorm_backward("bias_residual_layernorm_backward", dy, x, bias, residual, gamma, eps, rows, cols,
+                                                 nullptr, nullptr, dz, dgamma, dbeta, dbias, ws, ws_bytes,
+                                                 proqa_backward_workspace_bytes(cols), stream);
 }
 
 int proqa_bias_residual_layernorm_dropout_backward_f16(const void* dy, const void* x, const void* bias, const void* residual,
@@ -1302,26 +1196,15 @@ int proqa_bias_residual_layernorm_dropout_backward_f16(const void* dy, const voi
                                                        void* stream) {
   if (!dy || !x || !bias || !residual || !gamma || !dx || !dresidual || !dgamma || !dbeta || !dbias || !ws)
     return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: NULL argument");
-  if (rows < 0 || rows > 0xffffffffll || cols <= 0 || cols % 8 || cols > 64 * kMaxChunksPerLane * 8)
+  if (rows > 0xffffffffll)   // the generator's row counter is 32 bits
     return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: cols=%d must be a multiple of 8 and <= %d, rows < 2^32",
                 cols, 64 * kMaxChunksPerLane * 8);
-  if (ws_bytes < proqa_backward_workspace_bytes(cols))
-    return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: workspace too small");
   DropoutParams drop;
   if (!make_dropout_params(p, seed, site, call, &drop))
     return fail(PROQA_EINVAL, "bias_residual_layernorm_dropout_backward: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
-  hipStream_t st = as_stream(stream);
-  if (rows == 0) {
-    for (float* q : {dgamma, dbeta, dbias}) PROQA_HIP(hipMemsetAsync(q, 0, (size_t)cols * sizeof(float), st));
-    return PROQA_OK;
-  }
-  int64_t per;
-  const int n_slabs = slabs_for(rows, 16, &per);
-  hipLaunchKernelGGL(bias_residual_layernorm_dropout_bwd, dim3((unsigned)n_slabs), dim3(256), 0, st, (const _Float16*)dy,
-                     (const _Float16*)x, (const _Float16*)bias, (const _Float16*)residual, (const _Float16*)gamma, eps,
-                     (long long)rows, cols, (long long)per, (_Float16*)dresidual, (_Float16*)dx, (float*)ws, drop);
-  PROQA_LAUNCH_CHECK();
-  return launch_reduce((const float*)ws, n_slabs, 3, cols, dgamma, dbeta, dbias, nullptr, 0, st);
+  return launch_bias_residual_layernorm_backward("bias_residual_layernorm_dropout_backward", dy, x, bias, residual, gamma, eps,
+                                                 rows, cols, &drop, dx, dresidual, dgamma, dbeta, dbias, ws, ws_bytes,
+                                                 proqa_backward_workspace_bytes(cols), stream);
 }
 
 int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids_dev, const int32_t* cu_seqlens_dev,
@@ -1332,20 +1215,9 @@ int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids
   if (!dy || !ids_dev || !cu_seqlens_dev || !word_emb || !pos_emb || !type_emb || !ln_gamma || !dgamma || !dbeta || !d_word ||
       !d_pos || !d_type0 || !ws)
     return fail(PROQA_EINVAL, "embed_layernorm_backward: NULL argument");
-  if (batch < 0 || seq_len <= 0 || seq_len > kMaxSlabs || vocab <= 0 || n_tokens < 0)
-    return fail(PROQA_EINVAL, "embed_layernorm_backward: bad sizes (seq_len <= %d)", kMaxSlabs);
-  if (hidden <= 0 || hidden % 8 || hidden > 64 * kMaxChunksPerLane * 8)
-    return fail(PROQA_EINVAL, "embed_layernorm_backward: hidden=%d must be a multiple of 8 and <= %d", hidden,
-                64 * kMaxChunksPerLane * 8);
-  if (ws_bytes < proqa_backward_workspace_bytes(hidden)) return fail(PROQA_EINVAL, "embed_layernorm_backward: workspace too small");
-  if (batch == 0 || n_tokens == 0) return PROQA_OK;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(embed_layernorm_bwd, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
-                     (const long long*)ids_dev, (const int*)cu_seqlens_dev, batch, seq_len, hidden, (const _Float16*)word_emb,
-                     (long long)vocab, (const _Float16*)pos_emb, (const _Float16*)type_emb, (const _Float16*)ln_gamma, eps,
-                     (long long)n_tokens, d_word, d_pos, (float*)ws);
-  PROQA_LAUNCH_CHECK();
-  return launch_reduce((const float*)ws, seq_len, 3, hidden, dgamma, dbeta, nullptr, d_type0, 1, st);
+  return launch_embed_layernorm_backward("embed_layernorm_backward", false, dy, ids_dev, nullptr, cu_seqlens_dev, batch, seq_len,
+                                         hidden, n_tokens, word_emb, vocab, pos_emb, type_emb, 1, ln_gamma, eps, dgamma, dbeta,
+                                         d_word, d_pos, d_type0, ws, ws_bytes, proqa_backward_workspace_bytes(hidden), stream);
 }
 
 size_t proqa_embed_layernorm_typed_backward_workspace_bytes(int hidden) {
@@ -1364,50 +1236,19 @@ int proqa_embed_layernorm_typed_varlen_backward_f16(const void* dy, const int64_
     return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: NULL argument");
   if (n_types != 1 && n_types != 2)
     return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: n_types=%d must be 1 or 2", n_types);
-  if (batch < 0 || seq_len <= 0 || seq_len > kMaxSlabs || vocab <= 0 || n_tokens < 0)
-    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: bad sizes (seq_len <= %d)", kMaxSlabs);
-  if (hidden <= 0 || hidden % 8 || hidden > 64 * kMaxChunksPerLane * 8)
-    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: hidden=%d must be a multiple of 8 and <= %d", hidden,
-                64 * kMaxChunksPerLane * 8);
-  if (ws_bytes < proqa_embed_layernorm_typed_backward_workspace_bytes(hidden))
-    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: workspace too small");
-  if (batch == 0 || n_tokens == 0) return PROQA_OK;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(embed_layernorm_typed_bwd, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
-                     (const long long*)ids_dev, (const long long*)type_ids_dev, (const int*)cu_seqlens_dev, batch, seq_len,
-                     hidden, (const _Float16*)word_emb, (long long)vocab, (const _Float16*)pos_emb,
-                     (const _Float16*)type_emb_table, n_types, (const _Float16*)ln_gamma, eps, (long long)n_tokens, d_word,
-                     d_pos, (float*)ws);
-  PROQA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(reduce_slabs_typed, dim3((unsigned)ceil_div<int>(4 * hidden, 256)), dim3(256), 0, st, (const float*)ws,
-                     seq_len, hidden, dgamma, dbeta, d_types, n_types == 2 ? d_types + hidden : (float*)nullptr);
-  PROQA_LAUNCH_CHECK();
-  return PROQA_OK;
+  return launch_embed_layernorm_backward("embed_layernorm_typed_backward", true, dy, ids_dev, type_ids_dev, cu_seqlens_dev, batch,
+                                         seq_len, hidden, n_tokens, word_emb, vocab, pos_emb, type_emb_table, n_types, ln_gamma,
+                                         eps, dgamma, dbeta, d_word, d_pos, d_types, ws, ws_bytes,
+                                         proqa_embed_layernorm_typed_backward_workspace_bytes(hidden), stream);
 }
 
 int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx, const int32_t* cu_seqlens_dev,
                                  int batch, int max_seq_len, int n_heads, int64_t n_tokens, void* d_qkv, void* ws,
                                  size_t ws_bytes, void* stream) {
   if (!qkv || !d_ctx || !cu_seqlens_dev || !d_qkv || !ws) return fail(PROQA_EINVAL, "attention_backward: NULL argument");
-  if (batch < 0 || max_seq_len <= 0 || max_seq_len > 512 || n_heads <= 0 || n_tokens < 0)
-    return fail(PROQA_EINVAL, "attention_backward: bad sizes (max_seq_len <= 512)");
-  if (ws_bytes < proqa_attention_backward_workspace_bytes(n_tokens, n_heads))
-    return fail(PROQA_EINVAL, "attention_backward: workspace too small");
-  if (batch == 0 || n_tokens == 0) return PROQA_OK;
-  hipStream_t st = as_stream(stream);
-  const int n_c = (max_seq_len + kChunk - 1) / kChunk;
-  const unsigned grid = (unsigned)batch * (unsigned)n_heads * (unsigned)n_c;
-  float* ws_lse = (float*)ws;
-  float* ws_delta = ws_lse + n_tokens * n_heads;
-  hipLaunchKernelGGL(attention_bwd_dq, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
-                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
-                     (_Float16*)d_qkv, ws_lse, ws_delta);
-  PROQA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attention_bwd_dkv, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
-                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
-                     (_Float16*)d_qkv, (const float*)ws_lse, (const float*)ws_delta);
-  PROQA_LAUNCH_CHECK();
-  return PROQA_OK;
+  return launch_attention_backward("attention_backward", qkv, qkv_bias, d_ctx, cu_seqlens_dev, batch, max_seq_len, n_heads,
+                                   n_tokens, nullptr, d_qkv, ws, ws_bytes,
+                                   proqa_attention_backward_workspace_bytes(n_tokens, n_heads), stream);
 }
 
 int proqa_attention_dropout_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx,
@@ -1415,28 +1256,12 @@ int proqa_attention_dropout_backward_f16(const void* qkv, const void* qkv_bias, 
                                          int64_t n_tokens, double p, uint64_t seed, int site, uint32_t call, void* d_qkv,
                                          void* ws, size_t ws_bytes, void* stream) {
   if (!qkv || !d_ctx || !cu_seqlens_dev || !d_qkv || !ws) return fail(PROQA_EINVAL, "attention_dropout_backward: NULL argument");
-  if (batch < 0 || max_seq_len <= 0 || max_seq_len > 512 || n_heads <= 0 || n_tokens < 0)
-    return fail(PROQA_EINVAL, "attention_dropout_backward: bad sizes (max_seq_len <= 512)");
-  if (ws_bytes < proqa_attention_backward_workspace_bytes(n_tokens, n_heads))
-    return fail(PROQA_EINVAL, "attention_dropout_backward: workspace too small");
   DropoutParams drop;
   if (!make_dropout_params(p, seed, site, call, &drop))
     return fail(PROQA_EINVAL, "attention_dropout_backward: p=%g must be in [0, 1) and site=%d in [0, 255]", p, site);
-  if (batch == 0 || n_tokens == 0) return PROQA_OK;
-  hipStream_t st = as_stream(stream);
-  const int n_c = (max_seq_len + kChunk - 1) / kChunk;
-  const unsigned grid = (unsigned)batch * (unsigned)n_heads * (unsigned)n_c;
-  float* ws_lse = (float*)ws;
-  float* ws_delta = ws_lse + n_tokens * n_heads;
-  hipLaunchKernelGGL(attention_dropout_bwd_dq, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
-                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
-                     (_Float16*)d_qkv, ws_lse, ws_delta, drop);
-  PROQA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attention_dropout_bwd_dkv, dim3(grid), dim3(256), 0, st, (const _Float16*)qkv, (const _Float16*)qkv_bias,
-                     (const _Float16*)d_ctx, (const int*)cu_seqlens_dev, max_seq_len, n_heads, n_c, (long long)n_tokens,
-                     (_Float16*)d_qkv, (const float*)ws_lse, (const float*)ws_delta, drop);
-  PROQA_LAUNCH_CHECK();
-  return PROQA_OK;
+  return launch_attention_backward("attention_dropout_backward", qkv, qkv_bias, d_ctx, cu_seqlens_dev, batch, max_seq_len, n_heads,
+                                   n_tokens, &drop, d_qkv, ws, ws_bytes,
+                                   proqa_attention_backward_workspace_bytes(n_tokens, n_heads), stream);
 }
 
 int proqa_inbatch_loss_grad_f16(const void* q, const void* c, const int32_t* target, const float* lse, const float* grad_in,

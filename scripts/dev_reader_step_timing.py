@@ -186,8 +186,8 @@ def child(reps):
 
 def short(name):
     name = name.split("(")[0]
-    for tag in ("embed_layernorm_typed_bwd", "reduce_slabs_typed", "attention_dropout_bwd_dq", "attention_dropout_bwd_dkv",
-                "attention_dropout_fwd", "bias_residual_layernorm_dropout_bwd", "bias_residual_layernorm_dropout", "dropout_rows",
+    for tag in ("embed_layernorm_typed_bwd", "attention_dropout_bwd_dq", "attention_dropout_bwd_dkv", "attention_dropout_fwd",
+                "bias_residual_layernorm_dropout_bwd", "bias_residual_layernorm_dropout", "dropout_rows",
                 "attention_bwd_dq", "attention_bwd_dkv", "attention_fwd", "bias_residual_layernorm_bwd", "bias_residual_layernorm",
                 "embed_layernorm_bwd", "embed_layernorm", "column_kernel", "reduce_slabs", "bias_gelu_out", "linear_wgrad",
                 "reader_loss_bwd_rows", "reader_loss_bwd_rank", "reader_loss_bwd_sum", "reader_loss_rows", "reader_loss_rank",
