@@ -446,7 +446,7 @@ int proqa_pool_project_f16(const void* h, int batch, int seq_len, int hidden, co
  * fp16 activation is written as fp16, a parameter-vector or embedding-table gradient as fp32; every operator is linear in
  * its incoming gradient and passes inf / NaN through (no data-dependent loop); no allocation, no host synchronisation;
  * everything on `stream`.  The forward operators save nothing: each backward recomputes what it needs from the forward's
- * own inputs.  Apart from d_word, every output is bit-identical from run to run.
+ * own inputs.  Apart from d_word, every output is bit-identical from run to run (d_word too through the *_det entry points).
  * ws / ws_bytes: caller-owned device scratch of at least proqa_backward_workspace_bytes(cols) bytes (the attention:
  * proqa_attention_backward_workspace_bytes), 16-byte aligned; contents undefined afterwards; calls that share a
  * workspace must be ordered on one stream.
@@ -497,6 +497,37 @@ int proqa_embed_layernorm_typed_varlen_backward_f16(const void* dy, const int64_
                                                     const void* ln_gamma, float eps, float* dgamma, float* dbeta,
                                                     float* d_word, float* d_pos, float* d_types, void* ws, size_t ws_bytes,
                                                     void* stream);
+/* The two embedding backwards with d_word summed in a FIXED ORDER: every output is then bit-identical from run to run.  The
+ * arguments, the ADDED-INTO rule and the refusals are those of the entry points above; dgamma, dbeta, d_pos and d_type0 /
+ * d_types carry the bits of those entry points.  d_word, so that a caller can predict its bits:
+ *   - the occurrences of a word id k are the tokens whose clamped id is k (an id outside [0, vocab) counts as 0; ids at or
+ *     past a sequence's length are never read), taken in ascending packed row cu_seqlens[b] + s: n_k of them;
+ *   - dz_t is the fp32 per-token gradient that the atomic entry points add (the same arithmetic, hence the same bits);
+ *   - the occurrences are cut into chunks of C = proqa_embed_word_grad_chunk(), counted from the id's first occurrence;
+ *   - a chunk's partial is the sequential fp32 sum ((dz_0 + dz_1) + dz_2) + ..., each add rounded to nearest;
+ *   - the id's sum is the sequential fp32 sum of its chunk partials in ascending order;
+ *   - d_word[k] = d_word[k] + that sum, one add; rows of ids that do not occur are neither read nor written.
+ * The association depends on n_k alone: not on the grid, on timing or on the other ids of the batch.  No float atomics;
+ * a device-side radix sort of (id, row) finds the occurrences; no allocation, no host synchronisation, no workgroup waits
+ * on another.  Linear in dy; inf / NaN reach the rows of their tokens' ids and no others.
+ * ws: at least proqa_embed_layernorm_backward_det_workspace_bytes(n_tokens, hidden, typed) bytes (typed = 1 for the typed
+ * entry point), which covers the atomic entry point's need and the sort's; non-decreasing in n_tokens.  PROQA_EINVAL
+ * before any launch for everything the entry points above refuse, for a short workspace, and for vocab or n_tokens of
+ * 2^31 - 1 or more (the sort's key holds each in 32 bits). */
+int proqa_embed_word_grad_chunk(void);
+size_t proqa_embed_layernorm_backward_det_workspace_bytes(int64_t n_tokens, int hidden, int typed);
+int proqa_embed_layernorm_varlen_backward_det_f16(const void* dy, const int64_t* ids_dev, const int32_t* cu_seqlens_dev,
+                                                  int batch, int seq_len, int hidden, int64_t n_tokens, const void* word_emb,
+                                                  int64_t vocab, const void* pos_emb, const void* type_emb,
+                                                  const void* ln_gamma, float eps, float* dgamma, float* dbeta, float* d_word,
+                                                  float* d_pos, float* d_type0, void* ws, size_t ws_bytes, void* stream);
+int proqa_embed_layernorm_typed_varlen_backward_det_f16(const void* dy, const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                                        const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden,
+                                                        int64_t n_tokens, const void* word_emb, int64_t vocab,
+                                                        const void* pos_emb, const void* type_emb_table, int n_types,
+                                                        const void* ln_gamma, float eps, float* dgamma, float* dbeta,
+                                                        float* d_word, float* d_pos, float* d_types, void* ws,
+                                                        size_t ws_bytes, void* stream);
 /* backward of proqa_attention_ex_f16 on the packed layout (cls_only = 0): qkv [n_tokens, 3*hidden] (the GEMM output before
  * the bias), qkv_bias [3*hidden] or NULL, d_ctx [n_tokens, hidden] -> d_qkv [n_tokens, 3*hidden], every element written.
  * The probabilities are recomputed with the forward's conventions (query bias added, key bias dropped, scores / 8, fp32

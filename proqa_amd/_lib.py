@@ -190,6 +190,16 @@ SIGNATURES = {
                                                                 c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                                                                 c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                                                 c_void_p, c_void_p, c_size_t, c_void_p]),
+    "proqa_embed_word_grad_chunk": (c_int, []),
+    "proqa_embed_layernorm_backward_det_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "proqa_embed_layernorm_varlen_backward_det_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64,
+                                                              c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_float,
+                                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                              c_size_t, c_void_p]),
+    "proqa_embed_layernorm_typed_varlen_backward_det_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                                    c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                                                    c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                                    c_void_p, c_void_p, c_size_t, c_void_p]),
     "proqa_attention_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_void_p,
                                              c_void_p, c_size_t, c_void_p]),
     "proqa_dropout_keep_host": (c_int, [c_int, c_double, c_uint64, c_int, c_uint32, c_int64, c_int64, c_int64, c_int64, c_void_p]),

@@ -57,6 +57,8 @@ _REFERENCE_FLAGS = (
 EXTRA_FLAGS = (
     # fp32 .npy output (the reference writes whatever dtype the model emitted: fp16 under --fp16)
     ("--embed_dtype", str, "auto"),
+    # pretrain_retriever.py: the word-embedding gradient summed in a fixed order (bit-reproducible training)
+    ("--deterministic", "flag", False),
 )
 
 

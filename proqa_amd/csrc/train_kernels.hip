@@ -7,7 +7,8 @@
 // Determinism.  Column sums over rows (bias, gamma, beta gradients) are taken in a fixed order: a workgroup owns a
 // contiguous slab of rows, its partial sums go to the caller's workspace ([slab][k][cols] fp32), and reduce_slabs adds the
 // slabs in ascending order.  The attention backward has no cross-workgroup sum at all: one kernel owns query rows (softmax
-// statistics and dQ), a second owns key rows (dK, dV).  The only atomics are the fp32 adds into the word-embedding gradient.
+// statistics and dQ), a second owns key rows (dK, dV).  The only atomics are the fp32 adds into the word-embedding gradient
+// of the default entry points; the *_det entry points sum it in a fixed order instead (word_grad_* below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -262,12 +263,12 @@ __global__ __launch_bounds__(256) void bias_residual_layernorm_dropout_bwd(
 // workgroup = position s, its waves take the sequences that are longer than s in turns: dx of token (b, s) goes to the word
 // row of its id (fp32 atomics, the one non-deterministic output) and into the position's own sum; d_pos[s] is final when
 // the workgroup ends, and (dgamma, dbeta, d_pos[s]) are slab s of the workspace: the type-0 gradient is the sum of the
-// position gradients.
+// position gradients.  ATOMIC false (the *_det entry points) leaves d_word to the word_grad_* kernels below.
 // TYPED (the reader's [CLS] q [SEP] p [SEP]): a fourth per-wave accumulator.  The position's sum is kept in two parts, the
 // tokens of type 0 and those of type 1 (a type id outside [0, n_types) read row 0 in the forward and counts as type 0 here).
 // Slab s of the workspace is (dgamma, dbeta, d_types[0], d_types[1]) of position s; d_pos[s] += part 0 + part 1.  With
 // type_ids == nullptr part 1 is +0 and every sum is the sum the untyped kernel takes, in its order.
-template <bool TYPED>
+template <bool TYPED, bool ATOMIC = true>
 __device__ __forceinline__ void embed_layernorm_bwd_body(
     const _Float16* __restrict__ dy_in, const long long* __restrict__ ids, const long long* __restrict__ type_ids,
     const int* __restrict__ cu_seqlens, int batch, int seq_len, int hidden, const _Float16* __restrict__ word, long long vocab,
@@ -342,7 +343,7 @@ __device__ __forceinline__ void embed_layernorm_bwd_body(
         for (int i = 0; i < 8; ++i) {
           if (!TYPED || tt == 0) part[2][c][i] += dz[c][i];   // wave-uniform
           else part[N - 1][c][i] += dz[c][i];
-          atomicAdd(d_word + id * hidden + chunk * 8 + i, dz[c][i]);
+          if constexpr (ATOMIC) atomicAdd(d_word + id * hidden + chunk * 8 + i, dz[c][i]);
         }
       }
     }
@@ -381,6 +382,261 @@ __global__ __launch_bounds__(256) void embed_layernorm_typed_bwd(
     float* __restrict__ ws) {
   embed_layernorm_bwd_body<true>(dy_in, ids, type_ids, cu_seqlens, batch, seq_len, hidden, word, vocab, pos, type_table,
                                  n_types, gamma, eps, n_tokens, d_word, d_pos, ws);
+}
+
+// the same two kernels without the adds into d_word (the *_det entry points: d_word is summed below)
+__global__ __launch_bounds__(256) void embed_layernorm_bwd_no_word(
+    const _Float16* __restrict__ dy_in, const long long* __restrict__ ids, const int* __restrict__ cu_seqlens, int batch,
+    int seq_len, int hidden, const _Float16* __restrict__ word, long long vocab, const _Float16* __restrict__ pos,
+    const _Float16* __restrict__ type0, const _Float16* __restrict__ gamma, float eps, long long n_tokens,
+    float* __restrict__ d_pos, float* __restrict__ ws) {
+  embed_layernorm_bwd_body<false, false>(dy_in, ids, nullptr, cu_seqlens, batch, seq_len, hidden, word, vocab, pos, type0, 1,
+                                         gamma, eps, n_tokens, nullptr, d_pos, ws);
+}
+
+__global__ __launch_bounds__(256) void embed_layernorm_typed_bwd_no_word(
+    const _Float16* __restrict__ dy_in, const long long* __restrict__ ids, const long long* __restrict__ type_ids,
+    const int* __restrict__ cu_seqlens, int batch, int seq_len, int hidden, const _Float16* __restrict__ word, long long vocab,
+    const _Float16* __restrict__ pos, const _Float16* __restrict__ type_table, int n_types,
+    const _Float16* __restrict__ gamma, float eps, long long n_tokens, float* __restrict__ d_pos, float* __restrict__ ws) {
+  embed_layernorm_bwd_body<true, false>(dy_in, ids, type_ids, cu_seqlens, batch, seq_len, hidden, word, vocab, pos, type_table,
+                                        n_types, gamma, eps, n_tokens, nullptr, d_pos, ws);
+}
+
+// ---- the word-embedding gradient in a fixed order (the *_det entry points) ----------------------------------------------------
+// The position-owning kernels above run with their atomics compiled out (dgamma, dbeta, d_pos, d_types keep their bits) and
+// d_word is summed by a route of its own, launch after launch on the one stream:
+//   word_grad_keys      key[r] = (clamped id << 32 | r) of every packed row r < n_tokens; a row that no sequence owns gets
+//                       the id `vocab`, which sorts behind every real id
+//   word_grad_sort_pass an LSD radix sort of the keys by their id, 8 bits a pass (x3 launches: count, scan, scatter).  A wave
+//                       owns kSortKeysPerWave consecutive keys and ranks them 64 at a time with ballots, so a pass is stable
+//                       and the rows of one id stay in ascending order
+//   word_grad_units     wave = sorted position i.  The occurrences of an id are cut into chunks of kWordGradChunk counted from
+//                       the id's first occurrence; a wave whose position does not start a chunk exits.  The others recompute
+//                       dz of their chunk's tokens one after the other (the same layernorm_backward_row on the same z, so the
+//                       bits the atomic route adds) and sum them in that order.  The only chunk of an id is added straight
+//                       into d_word; a chunk of several goes to the workspace
+//   word_grad_combine   workgroup = first occurrence of an id with several chunks: its partials in ascending order, then one add
+// The sums are written with __fadd_rn: dz ends in a multiply, and `acc += dz` would be contracted into another association.
+constexpr int kWordGradChunk = 16;
+constexpr int kSortKeysPerWave = 512;   // x 4 waves: a sort workgroup takes 2048 keys
+constexpr int kSortScanThreads = 1024;
+
+// the sequence that owns packed row r: the last b with cu_seqlens[b] <= r.  -> false when no valid token lies there
+__device__ __forceinline__ bool locate_row(const int* __restrict__ cu_seqlens, int batch, int seq_len, long long r, int* b_out,
+                                           int* s_out) {
+  int lo = 0, hi = batch;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (cu_seqlens[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  const int first = cu_seqlens[lo];
+  const long long s = r - first;
+  *b_out = lo;
+  *s_out = (int)s;
+  return s >= 0 && s < cu_seqlens[lo + 1] - first && s < seq_len;
+}
+
+__global__ __launch_bounds__(256) void word_grad_keys(const long long* __restrict__ ids, const int* __restrict__ cu_seqlens,
+                                                      int batch, int seq_len, long long vocab, int n_tokens,
+                                                      unsigned long long* __restrict__ keys) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_tokens) return;
+  int b, s;
+  long long id = vocab;
+  if (locate_row(cu_seqlens, batch, seq_len, r, &b, &s)) {
+    id = ids[(long long)b * seq_len + s];
+    if (id < 0 || id >= vocab) id = 0;
+  }
+  keys[r] = ((unsigned long long)id << 32) | (unsigned)r;
+}
+
+// SCATTER false: hist[digit][wave] = how many of the wave's keys have that digit.  SCATTER true: hist holds the exclusive
+// scan of those counts (digit-major), where the wave's first key of each digit goes; the keys follow in their order.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void word_grad_sort_pass(const unsigned long long* __restrict__ in, int n, int shift,
+                                                           int n_waves, int* __restrict__ hist,
+                                                           unsigned long long* __restrict__ out) {
+  __shared__ int cnt[4][256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int gw = blockIdx.x * 4 + wave;
+  if (gw >= n_waves) return;   // wave-uniform; no workgroup barrier below
+  int* my = cnt[wave];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) my[lane + 64 * k] = SCATTER ? hist[(long long)(lane + 64 * k) * n_waves + gw] : 0;
+  __builtin_amdgcn_wave_barrier();
+  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  const int first = gw * kSortKeysPerWave;
+  for (int round = 0; round < kSortKeysPerWave / 64; ++round) {
+    const int i = first + round * 64 + lane;
+    const bool valid = i < n;
+    const unsigned long long key = valid ? in[i] : 0ull;
+    const int digit = (int)((key >> shift) & 255u);
+    unsigned long long same = __ballot(valid);   // the lanes of this round whose digit is mine
+#pragma unroll
+    for (int bit = 0; bit < 8; ++bit) {
+      const unsigned long long has = __ballot(valid && ((digit >> bit) & 1));
+      same &= ((digit >> bit) & 1) ? has : ~has;
+    }
+    const int before = __popcll(same & below);
+    int at = 0;
+    if (valid) at = my[digit] + before;
+    __builtin_amdgcn_wave_barrier();
+    if (valid && before == 0) my[digit] = at + __popcll(same);
+    __builtin_amdgcn_wave_barrier();
+    if constexpr (SCATTER) {
+      if (valid) out[at] = key;   // at < n: the scan's total is n
+    }
+  }
+  if constexpr (!SCATTER) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hist[(long long)(lane + 64 * k) * n_waves + gw] = my[lane + 64 * k];
+  }
+}
+
+// data[0..n) -> its exclusive prefix sums, in place; one workgroup, a thread owns a contiguous piece
+__global__ __launch_bounds__(kSortScanThreads) void word_grad_scan(int* __restrict__ data, int n) {
+  __shared__ int sums[kSortScanThreads];
+  const int t = threadIdx.x;
+  const int per = (n + kSortScanThreads - 1) / kSortScanThreads;
+  const int lo = min(t * per, n), hi = min(lo + per, n);
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += data[i];
+  sums[t] = s;
+  __syncthreads();
+  for (int off = 1; off < kSortScanThreads; off <<= 1) {
+    const int v = t >= off ? sums[t - off] : 0;
+    __syncthreads();
+    sums[t] += v;
+    __syncthreads();
+  }
+  int run = sums[t] - s;
+  for (int i = lo; i < hi; ++i) {
+    const int v = data[i];
+    data[i] = run;
+    run += v;
+  }
+}
+
+// the first sorted position whose id is `id` (position i holds it)
+__device__ __forceinline__ int word_grad_run_start(const unsigned long long* __restrict__ sorted, int i, unsigned id) {
+  int lo = -1, hi = i;   // sorted[lo] has a smaller id (or lo == -1), sorted[hi] has `id`
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((unsigned)(sorted[mid] >> 32) < id) lo = mid;
+    else hi = mid;
+  }
+  return hi;
+}
+
+// where the partial of the chunk at sorted position i of an id with several chunks lies: two chunk starts of such ids can
+// share a window of kWordGradChunk positions only as the tail of one id and the first chunk of the next
+__device__ __forceinline__ long long word_grad_slot(int i, bool first_of_id) {
+  return 2ll * (i / kWordGradChunk) + (first_of_id ? 1 : 0);
+}
+
+template <bool TYPED>
+__global__ __launch_bounds__(256) void word_grad_units(
+    const _Float16* __restrict__ dy_in, const long long* __restrict__ type_ids, const int* __restrict__ cu_seqlens, int batch,
+    int seq_len, int hidden, const _Float16* __restrict__ word, long long vocab, const _Float16* __restrict__ pos,
+    const _Float16* __restrict__ type_table, int n_types, const _Float16* __restrict__ gamma, float eps, int n_tokens,
+    const unsigned long long* __restrict__ sorted, float* __restrict__ d_word, float* __restrict__ partials) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n_tokens) return;
+  const unsigned id = (unsigned)(sorted[i] >> 32);
+  if (id >= vocab) return;   // the rows that no sequence owns
+  int start = i;
+  if (i > 0 && (unsigned)(sorted[i - 1] >> 32) == id) {
+    start = word_grad_run_start(sorted, i, id);
+    if ((i - start) % kWordGradChunk) return;
+  }
+  const int n_chunks = hidden >> 3;
+  float gam[kMaxChunksPerLane][8], acc[kMaxChunksPerLane][8], unused[2][kMaxChunksPerLane][8];
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) gam[c][k] = acc[c][k] = unused[0][c][k] = unused[1][c][k] = 0.f;
+    if (lane + 64 * c < n_chunks) load8(gamma + (lane + 64 * c) * 8, gam[c]);
+  }
+  int j = 0;
+  for (; j < kWordGradChunk && i + j < n_tokens; ++j) {
+    const unsigned long long key = sorted[i + j];
+    if ((unsigned)(key >> 32) != id) break;
+    const long long row = (long long)(unsigned)key;
+    int b, s;
+    locate_row(cu_seqlens, batch, seq_len, row, &b, &s);   // valid: word_grad_keys gave the row a real id
+    long long tt = 0;
+    if constexpr (TYPED) {
+      if (type_ids) tt = type_ids[(long long)b * seq_len + s];
+      if (tt < 0 || tt >= n_types) tt = 0;
+    }
+    float z[kMaxChunksPerLane][8], dy[kMaxChunksPerLane][8], dz[kMaxChunksPerLane][8];
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      const int chunk = lane + 64 * c;
+      if (chunk < n_chunks) {
+        float w[8], p[8], t[8];
+        load8(word + (long long)id * hidden + chunk * 8, w);
+        load8(dy_in + row * hidden + chunk * 8, dy[c]);
+        load8(pos + (long long)s * hidden + chunk * 8, p);
+        load8(type_table + tt * hidden + chunk * 8, t);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) z[c][k] = w[k] + (p[k] + t[k]);   // the association of embed_layernorm_bwd_body
+      }
+    }
+    layernorm_backward_row(z, dy, gam, lane, n_chunks, hidden, eps, dz, unused[0], unused[1]);
+#pragma unroll
+    for (int c = 0; c < kMaxChunksPerLane; ++c) {
+      if (lane + 64 * c < n_chunks) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[c][k] = j == 0 ? dz[c][k] : __fadd_rn(acc[c][k], dz[c][k]);
+      }
+    }
+  }
+  const bool more = j == kWordGradChunk && i + j < n_tokens && (unsigned)(sorted[i + j] >> 32) == id;
+  const bool single = start == i && !more;
+  float* dst = single ? d_word + (long long)id * hidden : partials + word_grad_slot(i, start == i) * hidden;
+#pragma unroll
+  for (int c = 0; c < kMaxChunksPerLane; ++c) {
+    const int chunk = lane + 64 * c;
+    if (chunk < n_chunks) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) dst[chunk * 8 + k] = single ? __fadd_rn(dst[chunk * 8 + k], acc[c][k]) : acc[c][k];
+    }
+  }
+}
+
+// workgroup = sorted position i, thread = 4 columns: the chain of adds is as long as the id has chunks, so the columns are
+// spread as thin as the workgroup allows and the partials of the next chunks are loaded ahead of the adds
+__global__ __launch_bounds__(256) void word_grad_combine(int hidden, long long vocab, int n_tokens,
+                                                         const unsigned long long* __restrict__ sorted,
+                                                         const float* __restrict__ partials, float* __restrict__ d_word) {
+  const int i = blockIdx.x;   // < n_tokens: the grid
+  const unsigned id = (unsigned)(sorted[i] >> 32);
+  if (id >= vocab) return;
+  if (i > 0 && (unsigned)(sorted[i - 1] >> 32) == id) return;   // not the id's first occurrence
+  if (i + kWordGradChunk >= n_tokens || (unsigned)(sorted[i + kWordGradChunk] >> 32) != id) return;   // a single chunk
+  int lo = i + kWordGradChunk, hi = n_tokens;   // sorted[lo] has `id`, sorted[hi] (or the end) does not
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((unsigned)(sorted[mid] >> 32) == id) lo = mid;
+    else hi = mid;
+  }
+  const int col = threadIdx.x * 4;
+  if (col >= hidden) return;   // hidden is a multiple of 8, <= 1024
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  f32x4 sum = *(const f32x4*)(partials + word_grad_slot(i, true) * hidden + col);
+#pragma unroll 8
+  for (int at = i + kWordGradChunk; at < hi; at += kWordGradChunk) {
+    const f32x4 p = *(const f32x4*)(partials + word_grad_slot(at, false) * hidden + col);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sum[k] = __fadd_rn(sum[k], p[k]);
+  }
+  float* dst = d_word + (long long)id * hidden + col;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) dst[k] = __fadd_rn(dst[k], sum[k]);
 }
 
 // ---- column-owning kernels: column sum, bias + GELU backward --------------------------------------------------------------
@@ -1055,8 +1311,27 @@ static int launch_bias_residual_layernorm_backward(const char* op, const void* d
   return launch_reduce((const float*)ws, n_slabs, 3, cols, dgamma, dbeta, dbias, nullptr, 0, st);
 }
 
+// The workspace of the *_det entry points: the position kernel's slabs, then the plan's pieces (each 256-byte aligned)
+struct WordGradPlan {
+  size_t keys_a, keys_b, hist, partials, total;   // byte offsets
+  int n_waves;
+};
+
+WordGradPlan word_grad_plan(size_t slabs_bytes, int64_t n_tokens, int hidden) {
+  WordGradPlan p;
+  const size_t t = n_tokens > 0 ? (size_t)n_tokens : 0;
+  p.n_waves = (int)ceil_div<size_t>(t, kSortKeysPerWave);
+  p.keys_a = round_up<size_t>(slabs_bytes, 256);
+  p.keys_b = p.keys_a + round_up<size_t>(t * sizeof(unsigned long long), 256);
+  p.hist = p.keys_b + round_up<size_t>(t * sizeof(unsigned long long), 256);
+  p.partials = p.hist + round_up<size_t>((size_t)256 * p.n_waves * sizeof(int), 256);
+  p.total = p.partials + 2 * ceil_div<size_t>(t, kWordGradChunk) * (size_t)(hidden > 0 ? hidden : 0) * sizeof(float);
+  return p;
+}
+
 // typed: d_types is [n_types][hidden] and type_ids may be null; else d_types is the type-0 row alone (n_types, type_ids unused)
-static int launch_embed_layernorm_backward(const char* op, bool typed, const void* dy, const int64_t* ids,
+// det: d_word is summed in a fixed order (ws_need then covers word_grad_plan)
+static int launch_embed_layernorm_backward(const char* op, bool typed, bool det, const void* dy, const int64_t* ids,
                                            const int64_t* type_ids, const int32_t* cu_seqlens, int batch, int seq_len,
                                            int hidden, int64_t n_tokens, const void* word, int64_t vocab, const void* pos,
                                            const void* type_emb, int n_types, const void* gamma, float eps, float* dgamma,
@@ -1066,10 +1341,22 @@ static int launch_embed_layernorm_backward(const char* op, bool typed, const voi
     return fail(PROQA_EINVAL, "%s: bad sizes (seq_len <= %d)", op, kMaxSlabs);
   if (hidden <= 0 || hidden % 8 || hidden > 64 * kMaxChunksPerLane * 8)
     return fail(PROQA_EINVAL, "%s: hidden=%d must be a multiple of 8 and <= %d", op, hidden, 64 * kMaxChunksPerLane * 8);
+  if (det && (vocab >= 0x7fffffffll || n_tokens >= 0x7fffffffll))   // the sort key is (id, row) in 32 bits each
+    return fail(PROQA_EINVAL, "%s: vocab and n_tokens must be below 2^31 - 1", op);
   if (ws_bytes < ws_need) return fail(PROQA_EINVAL, "%s: workspace too small", op);
   if (batch == 0 || n_tokens == 0) return PROQA_OK;
   hipStream_t st = as_stream(stream);
-  if (typed)
+  if (typed && det)
+    hipLaunchKernelGGL(embed_layernorm_typed_bwd_no_word, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
+                       (const long long*)ids, (const long long*)type_ids, (const int*)cu_seqlens, batch, seq_len, hidden,
+                       (const _Float16*)word, (long long)vocab, (const _Float16*)pos, (const _Float16*)type_emb, n_types,
+                       (const _Float16*)gamma, eps, (long long)n_tokens, d_pos, (float*)ws);
+  else if (det)
+    hipLaunchKernelGGL(embed_layernorm_bwd_no_word, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
+                       (const long long*)ids, (const int*)cu_seqlens, batch, seq_len, hidden, (const _Float16*)word,
+                       (long long)vocab, (const _Float16*)pos, (const _Float16*)type_emb, (const _Float16*)gamma, eps,
+                       (long long)n_tokens, d_pos, (float*)ws);
+  else if (typed)
     hipLaunchKernelGGL(embed_layernorm_typed_bwd, dim3((unsigned)seq_len), dim3(256), 0, st, (const _Float16*)dy,
                        (const long long*)ids, (const long long*)type_ids, (const int*)cu_seqlens, batch, seq_len, hidden,
                        (const _Float16*)word, (long long)vocab, (const _Float16*)pos, (const _Float16*)type_emb, n_types,
@@ -1081,8 +1368,50 @@ static int launch_embed_layernorm_backward(const char* op, bool typed, const voi
                        (long long)n_tokens, d_word, d_pos, (float*)ws);
   PROQA_LAUNCH_CHECK();
   // slab s is (dgamma, dbeta, the position's sum [by type]) of position s: the position sums add up to the type gradients
-  return launch_reduce((const float*)ws, seq_len, typed ? 4 : 3, hidden, dgamma, dbeta, d_types,
-                       typed && n_types == 2 ? d_types + hidden : nullptr, 1, st);
+  if (int rc = launch_reduce((const float*)ws, seq_len, typed ? 4 : 3, hidden, dgamma, dbeta, d_types,
+                             typed && n_types == 2 ? d_types + hidden : nullptr, 1, st))
+    return rc;
+  if (!det) return PROQA_OK;
+
+  const int T = (int)n_tokens;
+  const WordGradPlan plan = word_grad_plan((size_t)kMaxSlabs * (typed ? 4 : 3) * (size_t)hidden * sizeof(float), n_tokens, hidden);
+  unsigned long long* keys = (unsigned long long*)((char*)ws + plan.keys_a);
+  unsigned long long* spare = (unsigned long long*)((char*)ws + plan.keys_b);
+  int* hist = (int*)((char*)ws + plan.hist);
+  float* partials = (float*)((char*)ws + plan.partials);
+  hipLaunchKernelGGL(word_grad_keys, dim3((unsigned)ceil_div<int>(T, 256)), dim3(256), 0, st, (const long long*)ids,
+                     (const int*)cu_seqlens, batch, seq_len, (long long)vocab, T, keys);
+  PROQA_LAUNCH_CHECK();
+  int id_bits = 1;   // of the ids 0 .. vocab (vocab itself marks the rows that no sequence owns)
+  while ((vocab >> id_bits) != 0) ++id_bits;
+  const unsigned sort_grid = (unsigned)ceil_div<int>(plan.n_waves, 4);
+  for (int shift = 32; shift < 32 + id_bits; shift += 8) {
+    hipLaunchKernelGGL(word_grad_sort_pass<false>, dim3(sort_grid), dim3(256), 0, st, (const unsigned long long*)keys, T, shift,
+                       plan.n_waves, hist, (unsigned long long*)nullptr);
+    PROQA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(word_grad_scan, dim3(1), dim3(kSortScanThreads), 0, st, hist, 256 * plan.n_waves);
+    PROQA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(word_grad_sort_pass<true>, dim3(sort_grid), dim3(256), 0, st, (const unsigned long long*)keys, T, shift,
+                       plan.n_waves, hist, spare);
+    PROQA_LAUNCH_CHECK();
+    std::swap(keys, spare);
+  }
+  const unsigned wave_grid = (unsigned)ceil_div<int>(T, 4);
+  if (typed)
+    hipLaunchKernelGGL(word_grad_units<true>, dim3(wave_grid), dim3(256), 0, st, (const _Float16*)dy,
+                       (const long long*)type_ids, (const int*)cu_seqlens, batch, seq_len, hidden, (const _Float16*)word,
+                       (long long)vocab, (const _Float16*)pos, (const _Float16*)type_emb, n_types, (const _Float16*)gamma, eps,
+                       T, (const unsigned long long*)keys, d_word, partials);
+  else
+    hipLaunchKernelGGL(word_grad_units<false>, dim3(wave_grid), dim3(256), 0, st, (const _Float16*)dy,
+                       (const long long*)nullptr, (const int*)cu_seqlens, batch, seq_len, hidden, (const _Float16*)word,
+                       (long long)vocab, (const _Float16*)pos, (const _Float16*)type_emb, 1, (const _Float16*)gamma, eps, T,
+                       (const unsigned long long*)keys, d_word, partials);
+  PROQA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(word_grad_combine, dim3((unsigned)T), dim3(256), 0, st, hidden, (long long)vocab, T,
+                     (const unsigned long long*)keys, (const float*)partials, d_word);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
 }
 
 // drop == nullptr: without dropout
@@ -1215,7 +1544,7 @@ int proqa_embed_layernorm_varlen_backward_f16(const void* dy, const int64_t* ids
   if (!dy || !ids_dev || !cu_seqlens_dev || !word_emb || !pos_emb || !type_emb || !ln_gamma || !dgamma || !dbeta || !d_word ||
       !d_pos || !d_type0 || !ws)
     return fail(PROQA_EINVAL, "embed_layernorm_backward: NULL argument");
-  return launch_embed_layernorm_backward("embed_layernorm_backward", false, dy, ids_dev, nullptr, cu_seqlens_dev, batch, seq_len,
+  return launch_embed_layernorm_backward("embed_layernorm_backward", false, false, dy, ids_dev, nullptr, cu_seqlens_dev, batch, seq_len,
                                          hidden, n_tokens, word_emb, vocab, pos_emb, type_emb, 1, ln_gamma, eps, dgamma, dbeta,
                                          d_word, d_pos, d_type0, ws, ws_bytes, proqa_backward_workspace_bytes(hidden), stream);
 }
@@ -1236,10 +1565,50 @@ int proqa_embed_layernorm_typed_varlen_backward_f16(const void* dy, const int64_
     return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: NULL argument");
   if (n_types != 1 && n_types != 2)
     return fail(PROQA_EINVAL, "embed_layernorm_typed_backward: n_types=%d must be 1 or 2", n_types);
-  return launch_embed_layernorm_backward("embed_layernorm_typed_backward", true, dy, ids_dev, type_ids_dev, cu_seqlens_dev, batch,
+  return launch_embed_layernorm_backward("embed_layernorm_typed_backward", true, false, dy, ids_dev, type_ids_dev, cu_seqlens_dev, batch,
                                          seq_len, hidden, n_tokens, word_emb, vocab, pos_emb, type_emb_table, n_types, ln_gamma,
                                          eps, dgamma, dbeta, d_word, d_pos, d_types, ws, ws_bytes,
                                          proqa_embed_layernorm_typed_backward_workspace_bytes(hidden), stream);
+}
+
+int proqa_embed_word_grad_chunk(void) { return kWordGradChunk; }
+
+size_t proqa_embed_layernorm_backward_det_workspace_bytes(int64_t n_tokens, int hidden, int typed) {
+  if (hidden <= 0) return 0;
+  return word_grad_plan(typed ? proqa_embed_layernorm_typed_backward_workspace_bytes(hidden) : proqa_backward_workspace_bytes(hidden),
+                        n_tokens, hidden).total;
+}
+
+int proqa_embed_layernorm_varlen_backward_det_f16(const void* dy, const int64_t* ids_dev, const int32_t* cu_seqlens_dev,
+                                                  int batch, int seq_len, int hidden, int64_t n_tokens, const void* word_emb,
+                                                  int64_t vocab, const void* pos_emb, const void* type_emb,
+                                                  const void* ln_gamma, float eps, float* dgamma, float* dbeta, float* d_word,
+                                                  float* d_pos, float* d_type0, void* ws, size_t ws_bytes, void* stream) {
+  if (!dy || !ids_dev || !cu_seqlens_dev || !word_emb || !pos_emb || !type_emb || !ln_gamma || !dgamma || !dbeta || !d_word ||
+      !d_pos || !d_type0 || !ws)
+    return fail(PROQA_EINVAL, "embed_layernorm_backward_det: NULL argument");
+  return launch_embed_layernorm_backward("embed_layernorm_backward_det", false, true, dy, ids_dev, nullptr, cu_seqlens_dev, batch,
+                                         seq_len, hidden, n_tokens, word_emb, vocab, pos_emb, type_emb, 1, ln_gamma, eps, dgamma,
+                                         dbeta, d_word, d_pos, d_type0, ws, ws_bytes,
+                                         proqa_embed_layernorm_backward_det_workspace_bytes(n_tokens, hidden, 0), stream);
+}
+
+int proqa_embed_layernorm_typed_varlen_backward_det_f16(const void* dy, const int64_t* ids_dev, const int64_t* type_ids_dev,
+                                                        const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden,
+                                                        int64_t n_tokens, const void* word_emb, int64_t vocab,
+                                                        const void* pos_emb, const void* type_emb_table, int n_types,
+                                                        const void* ln_gamma, float eps, float* dgamma, float* dbeta,
+                                                        float* d_word, float* d_pos, float* d_types, void* ws,
+                                                        size_t ws_bytes, void* stream) {
+  if (!dy || !ids_dev || !cu_seqlens_dev || !word_emb || !pos_emb || !type_emb_table || !ln_gamma || !dgamma || !dbeta ||
+      !d_word || !d_pos || !d_types || !ws)
+    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward_det: NULL argument");
+  if (n_types != 1 && n_types != 2)
+    return fail(PROQA_EINVAL, "embed_layernorm_typed_backward_det: n_types=%d must be 1 or 2", n_types);
+  return launch_embed_layernorm_backward("embed_layernorm_typed_backward_det", true, true, dy, ids_dev, type_ids_dev,
+                                         cu_seqlens_dev, batch, seq_len, hidden, n_tokens, word_emb, vocab, pos_emb,
+                                         type_emb_table, n_types, ln_gamma, eps, dgamma, dbeta, d_word, d_pos, d_types, ws,
+                                         ws_bytes, proqa_embed_layernorm_backward_det_workspace_bytes(n_tokens, hidden, 1), stream);
 }
 
 int proqa_attention_backward_f16(const void* qkv, const void* qkv_bias, const void* d_ctx, const int32_t* cu_seqlens_dev,

@@ -22,8 +22,9 @@ import time
 
 LAST_RUN_STATS = {}
 
-# test hook: parameters whose name contains one of these substrings are frozen (the word-embedding gradient is summed
-# with atomics, the module's one run-to-run difference; frozen, two runs of one seed log identical losses)
+# test hook: parameters whose name contains one of these substrings are frozen (without --deterministic the word-embedding
+# gradient is summed with atomics, the module's one run-to-run difference; frozen, or with --deterministic, two runs of one
+# seed log identical losses)
 FROZEN_PARAMETERS = ()
 
 logger = logging.getLogger(__name__)
@@ -269,7 +270,10 @@ def main(argv=None):
         device = torch.device("cuda", torch.cuda.current_device())
         logger.info("device %s n_gpu %d distributed training %r", device, 1, False)
         model = TrainableRetriever(cfg, device=device, hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention,
-                                   dropout_seed=args.seed)
+                                   dropout_seed=args.seed, deterministic=args.deterministic)
+        if args.deterministic:
+            logger.info("--deterministic: the word-embedding gradient is summed in a fixed order (no atomics); a run is a "
+                        "function of the data, the seed and the checkpoint, bit for bit")
         if args.init_checkpoint != "":
             state = torch.load(args.init_checkpoint, map_location="cpu")
         else:
@@ -347,7 +351,7 @@ def main(argv=None):
         stats.clear()
         stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
                      skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"], seconds=seconds,
-                     best_acc=best_acc, output_dir=args.output_dir)
+                     best_acc=best_acc, output_dir=args.output_dir, deterministic=bool(args.deterministic))
         if os.environ.get("PROQA_STATS_JSON"):
             with open(os.environ["PROQA_STATS_JSON"], "w") as f:
                 json.dump(stats, f)

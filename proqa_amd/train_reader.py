@@ -28,9 +28,9 @@ from .pretrain_retriever import _Losses, _tensorboard, is_update_step, load_bert
 
 LAST_RUN_STATS = {}
 
-# test hooks: parameters whose name contains one of these substrings are frozen (the word-embedding gradient is summed
-# with atomics, the module's one run-to-run difference); a callable that receives every non-empty batch before the
-# forward; False = per-forward casts in the retriever's towers instead of the fp16 working copies
+# test hooks: parameters whose name contains one of these substrings are frozen (without --deterministic the word-embedding
+# gradient is summed with atomics, the module's one run-to-run difference); a callable that receives every non-empty batch
+# before the forward; False = per-forward casts in the retriever's towers instead of the fp16 working copies
 FROZEN_PARAMETERS = ()
 ON_BATCH = None
 USE_HALF_COPIES = True
@@ -106,6 +106,8 @@ def build_parser():
     p.add_argument("--topk", default=30, type=int)
     p.add_argument("--save-all", action="store_true")
     p.add_argument("--candidates", default="", type=str)
+    p.add_argument("--deterministic", action="store_true", default=False,
+                   help="sum the word-embedding gradients in a fixed order: a run reproduces bit for bit")
     return p
 
 
@@ -242,6 +244,9 @@ def main(argv=None):
                                               attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
             model.load_state_dict(state, strict=False)
         logger.info(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
+        if args.deterministic:
+            logger.info("--deterministic: the word-embedding gradient is summed in a fixed order (no atomics); a run is a "
+                        "function of the data, the seed and the checkpoint, bit for bit")
         if args.fix_para_encoder:
             model.freeze_c_encoder()
         for n, p in model.named_parameters():
@@ -354,7 +359,7 @@ def main(argv=None):
         stats.clear()
         stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
                      failed_retrieval=failed_per_epoch, failed_steps=failed_steps, update_steps=update_steps, skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"],
-                     seconds=seconds, best_em=best_em, output_dir=args.output_dir,
+                     seconds=seconds, best_em=best_em, output_dir=args.output_dir, deterministic=bool(args.deterministic),
                      sampler_seconds=dict(train_dataloader.seconds), sampler_transfers=dict(train_dataloader.transfers))
         if os.environ.get("PROQA_STATS_JSON"):
             with open(os.environ["PROQA_STATS_JSON"], "w") as f:

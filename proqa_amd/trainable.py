@@ -139,8 +139,9 @@ def embed_layernorm(ids, cu_seqlens, n_tokens, word, pos, type0, gamma, beta, ep
     return out
 
 
-def embed_layernorm_backward(dy, ids, cu_seqlens, word, pos, type0, gamma, eps):
-    """-> fp32 (dgamma [hidden], dbeta [hidden], d_word [vocab, hidden], d_pos [positions, hidden], d_type0 [hidden])"""
+def embed_layernorm_backward(dy, ids, cu_seqlens, word, pos, type0, gamma, eps, deterministic=False):
+    """-> fp32 (dgamma [hidden], dbeta [hidden], d_word [vocab, hidden], d_pos [positions, hidden], d_type0 [hidden])
+    deterministic: d_word is summed in a fixed order (proqa_embed_layernorm_varlen_backward_det_f16), not with atomics"""
     lib = _lib.load()
     dy = _f16(dy, "dy")
     batch, seq_len = ids.shape
@@ -151,8 +152,13 @@ def embed_layernorm_backward(dy, ids, cu_seqlens, word, pos, type0, gamma, eps):
     dgamma, dbeta, d_type0 = (torch.zeros(hidden, dtype=torch.float32, device=dev) for _ in range(3))
     d_word = torch.zeros(word.shape, dtype=torch.float32, device=dev)
     d_pos = torch.zeros(pos.shape, dtype=torch.float32, device=dev)
-    ws = _workspace(dev, lib.proqa_backward_workspace_bytes(hidden))
-    _call(lib.proqa_embed_layernorm_varlen_backward_f16, dev, dy.data_ptr(), ids.data_ptr(), cu_seqlens.data_ptr(), batch,
+    if deterministic:
+        fn = lib.proqa_embed_layernorm_varlen_backward_det_f16
+        ws = _workspace(dev, lib.proqa_embed_layernorm_backward_det_workspace_bytes(n_tokens, hidden, 0))
+    else:
+        fn = lib.proqa_embed_layernorm_varlen_backward_f16
+        ws = _workspace(dev, lib.proqa_backward_workspace_bytes(hidden))
+    _call(fn, dev, dy.data_ptr(), ids.data_ptr(), cu_seqlens.data_ptr(), batch,
           seq_len, hidden, n_tokens, _f16(word, "word").data_ptr(), word.shape[0], _f16(pos, "pos").data_ptr(),
           _f16(type0, "type0").data_ptr(), _f16(gamma, "gamma").data_ptr(), float(eps), dgamma.data_ptr(), dbeta.data_ptr(),
           d_word.data_ptr(), d_pos.data_ptr(), d_type0.data_ptr(), ws.data_ptr(), ws.numel())
@@ -172,8 +178,9 @@ def embed_layernorm_typed(ids, type_ids, cu_seqlens, n_tokens, word, pos, types,
     return out
 
 
-def embed_layernorm_typed_backward(dy, ids, type_ids, cu_seqlens, word, pos, types, gamma, eps):
-    """-> fp32 (dgamma [hidden], dbeta [hidden], d_word [vocab, hidden], d_pos [positions, hidden], d_types [n_types, hidden])"""
+def embed_layernorm_typed_backward(dy, ids, type_ids, cu_seqlens, word, pos, types, gamma, eps, deterministic=False):
+    """-> fp32 (dgamma [hidden], dbeta [hidden], d_word [vocab, hidden], d_pos [positions, hidden], d_types [n_types, hidden])
+    deterministic: d_word is summed in a fixed order (proqa_embed_layernorm_typed_varlen_backward_det_f16)"""
     lib = _lib.load()
     dy = _f16(dy, "dy")
     batch, seq_len = ids.shape
@@ -187,8 +194,13 @@ def embed_layernorm_typed_backward(dy, ids, type_ids, cu_seqlens, word, pos, typ
     d_word = torch.zeros(word.shape, dtype=torch.float32, device=dev)
     d_pos = torch.zeros(pos.shape, dtype=torch.float32, device=dev)
     d_types = torch.zeros(types.shape, dtype=torch.float32, device=dev)
-    ws = _workspace(dev, lib.proqa_embed_layernorm_typed_backward_workspace_bytes(hidden))
-    _call(lib.proqa_embed_layernorm_typed_varlen_backward_f16, dev, dy.data_ptr(), ids.data_ptr(),
+    if deterministic:
+        fn = lib.proqa_embed_layernorm_typed_varlen_backward_det_f16
+        ws = _workspace(dev, lib.proqa_embed_layernorm_backward_det_workspace_bytes(n_tokens, hidden, 1))
+    else:
+        fn = lib.proqa_embed_layernorm_typed_varlen_backward_f16
+        ws = _workspace(dev, lib.proqa_embed_layernorm_typed_backward_workspace_bytes(hidden))
+    _call(fn, dev, dy.data_ptr(), ids.data_ptr(),
           type_ids.data_ptr() if type_ids is not None else None, cu_seqlens.data_ptr(), batch, seq_len, hidden, n_tokens,
           _f16(word, "word").data_ptr(), word.shape[0], _f16(pos, "pos").data_ptr(), _f16(types, "types").data_ptr(),
           types.shape[0], _f16(gamma, "gamma").data_ptr(), float(eps), dgamma.data_ptr(), dbeta.data_ptr(), d_word.data_ptr(),
@@ -348,38 +360,40 @@ def inbatch_loss_grad(q, c, target, lse, grad_in):
 
 class _EmbedLayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ids, cu_seqlens, n_tokens, word, pos, types, gamma, beta, eps):
+    def forward(ctx, ids, cu_seqlens, n_tokens, word, pos, types, gamma, beta, eps, deterministic=False):
         w16, p16, t16, g16 = word.half(), pos.half(), types[0].half().contiguous(), gamma.half()
         ctx.save_for_backward(ids, cu_seqlens, w16, p16, t16, g16)
-        ctx.eps, ctx.n_types = eps, types.shape[0]
+        ctx.eps, ctx.n_types, ctx.deterministic = eps, types.shape[0], bool(deterministic)
         return embed_layernorm(ids, cu_seqlens, n_tokens, w16, p16, t16, g16, beta.half(), eps)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         ids, cu, w16, p16, t16, g16 = ctx.saved_tensors
-        dgamma, dbeta, d_word, d_pos, d_type0 = embed_layernorm_backward(dy, ids, cu, w16, p16, t16, g16, ctx.eps)
+        dgamma, dbeta, d_word, d_pos, d_type0 = embed_layernorm_backward(dy, ids, cu, w16, p16, t16, g16, ctx.eps,
+                                                                         ctx.deterministic)
         d_types = torch.zeros((ctx.n_types, d_type0.shape[0]), dtype=torch.float32, device=dy.device)
         d_types[0] = d_type0          # token_type_ids are never passed: row 0 only
-        return None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None
+        return None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None, None
 
 
 class _EmbedLayerNormTyped(torch.autograd.Function):
     """The reader's embeddings: token types from `type_ids`; the gradient of the type table is the full [n_types, hidden]."""
 
     @staticmethod
-    def forward(ctx, ids, type_ids, cu_seqlens, n_tokens, word, pos, types, gamma, beta, eps):
+    def forward(ctx, ids, type_ids, cu_seqlens, n_tokens, word, pos, types, gamma, beta, eps, deterministic=False):
         w16, p16, t16, g16 = word.half(), pos.half(), types.half().contiguous(), gamma.half()
         ctx.save_for_backward(ids, type_ids, cu_seqlens, w16, p16, t16, g16)
-        ctx.eps = eps
+        ctx.eps, ctx.deterministic = eps, bool(deterministic)
         return embed_layernorm_typed(ids, type_ids, cu_seqlens, n_tokens, w16, p16, t16, g16, beta.half(), eps)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         ids, type_ids, cu, w16, p16, t16, g16 = ctx.saved_tensors
-        dgamma, dbeta, d_word, d_pos, d_types = embed_layernorm_typed_backward(dy, ids, type_ids, cu, w16, p16, t16, g16, ctx.eps)
-        return None, None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None
+        dgamma, dbeta, d_word, d_pos, d_types = embed_layernorm_typed_backward(dy, ids, type_ids, cu, w16, p16, t16, g16, ctx.eps,
+                                                                               ctx.deterministic)
+        return None, None, None, None, d_word, d_pos, d_types, dgamma, dbeta, None, None
 
 
 class _Dropout(torch.autograd.Function):
@@ -515,7 +529,7 @@ def inbatch_loss(q, c, target=None):
 # ---- one tower pass, shared by TrainableRetriever and TrainableReader ----------------------------------------------------------
 
 def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None, drop=(0.0, 0.0, 0, 0), probe_extra=None,
-              half=None, seq_lens_host=None):
+              half=None, seq_lens_host=None, deterministic=False):
     """One BERT tower with gradients.  P: {key: fp32 master}; `tower` the key prefix of the tower's parameters (bert_q,
     bert_c, bert).  input_ids / input_mask [B, S] right-padded CUDA tensors, B >= 1; type_ids [B, S] or None (every token
     of type 0: the untyped embedding operator).  drop = (hidden rate, attention rate, seed, call) of this pass; a rate of 0
@@ -524,7 +538,8 @@ def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None,
     of those masters stacked by rows} for EVERY product of the pass (HalfWeights.views), or None: each product casts its
     masters itself.  seq_lens_host: the rows' lengths as a list of B ints that the caller vouches for (the mask is a
     prefix of that many ones per row): the pass then makes NO host round trip -- the mask is not read or checked, and
-    probe_extra must be None.
+    probe_extra must be None.  deterministic: the word-embedding gradient is summed in a fixed order (DESIGN.md section 3e,
+    Determinism) and not with atomics, so that every gradient of the pass is bit-identical from run to run.
     -> proj given (the key prefix of the projection): the [B, 128] fp16 embedding of pooler + projection;
        proj None: (h, cu_seqlens, lens, max_len), the packed last hidden state [T, H] fp16 and its geometry."""
     B, S = input_ids.shape
@@ -572,9 +587,9 @@ def run_tower(P, tower, cfg, input_ids, input_mask, *, type_ids=None, proj=None,
     tables = (P[f"{e}.word_embeddings.weight"], P[f"{e}.position_embeddings.weight"], P[f"{e}.token_type_embeddings.weight"],
               P[f"{e}.LayerNorm.weight"], P[f"{e}.LayerNorm.bias"])
     if type_ids is None:
-        h = _EmbedLayerNorm.apply(ids, cu, n_tokens, *tables, eps)
+        h = _EmbedLayerNorm.apply(ids, cu, n_tokens, *tables, eps, deterministic)
     else:
-        h = _EmbedLayerNormTyped.apply(ids, type_ids.contiguous().to(torch.int64), cu, n_tokens, *tables, eps)
+        h = _EmbedLayerNormTyped.apply(ids, type_ids.contiguous().to(torch.int64), cu, n_tokens, *tables, eps, deterministic)
     if p_hid > 0:
         h = _Dropout.apply(h, hid(0))
     for i in range(cfg.num_hidden_layers):
@@ -694,7 +709,7 @@ class TrainableRetriever(torch.nn.Module):
     input_mask_c, right-padded) and returns {'q': [B, 128], 'c': [B, 128]} in fp16 with gradients."""
 
     def __init__(self, config, device=None, dropout=0.0, *, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
-                 dropout_seed=None):
+                 dropout_seed=None, deterministic=False):
         super().__init__()
         cfg = config if not isinstance(config, dict) else config_from_dict(config)
         if dropout != 0:
@@ -720,6 +735,7 @@ class TrainableRetriever(torch.nn.Module):
         self.device = dev
         self.hidden_dropout_prob = float(hidden_dropout_prob)
         self.attention_probs_dropout_prob = float(attention_probs_dropout_prob)
+        self.deterministic = bool(deterministic)     # the word-embedding gradient in a fixed order (no atomics)
         # the masks' (seed, call): plain Python numbers, not part of state_dict() (which keeps the reference's keys)
         self._dropout_seed = int(torch.initial_seed() if dropout_seed is None else dropout_seed) & 0xFFFFFFFFFFFFFFFF
         self._dropout_call = 0
@@ -825,4 +841,5 @@ class TrainableRetriever(torch.nn.Module):
         if p_hid > 0 or p_att > 0:
             self._dropout_call = (call + 1) & 0xFFFFFF
         return run_tower(self._flat, tower, self.config, input_ids, input_mask, proj=proj, drop=(p_hid, p_att, seed, call),
-                         half=self._half.views if self._half is not None else None, seq_lens_host=seq_lens_host)
+                         half=self._half.views if self._half is not None else None, seq_lens_host=seq_lens_host,
+                         deterministic=self.deterministic)

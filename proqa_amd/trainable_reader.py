@@ -64,7 +64,8 @@ class TrainableReader(torch.nn.Module):
     "early"}, eval(): {"start_logits", "end_logits", "rank_logits"}."""
 
     def __init__(self, config, device=None, *, shared_norm=True, drop_early=False, qa_drop=0.0, hidden_dropout_prob=0.0,
-                 attention_probs_dropout_prob=0.0, dropout_seed=None, separate=False, add_select=False):
+                 attention_probs_dropout_prob=0.0, dropout_seed=None, separate=False, add_select=False,
+                 deterministic=False):
         super().__init__()
         cfg = config if not isinstance(config, dict) else config_from_dict(config)
         if separate or add_select:
@@ -77,13 +78,14 @@ class TrainableReader(torch.nn.Module):
         if dev.type != "cuda":
             raise RuntimeError("proqa_amd.TrainableReader runs on MI355X only; there is no CPU path")
         self.shared_norm, self.drop_early = bool(shared_norm), bool(drop_early)
+        self.deterministic = bool(deterministic)     # the word-embedding gradients in a fixed order, in both towers
         self._dropout_seed = int(torch.initial_seed() if dropout_seed is None else dropout_seed) & 0xFFFFFFFFFFFFFFFF
         self._dropout_call = 0
         self._inference = None
         # the towers of the retriever (and every check of the geometry and of the device)
         retriever = TrainableRetriever(cfg, device=dev, hidden_dropout_prob=hidden_dropout_prob,
                                        attention_probs_dropout_prob=attention_probs_dropout_prob,
-                                       dropout_seed=self._dropout_seed)
+                                       dropout_seed=self._dropout_seed, deterministic=self.deterministic)
         dev = retriever.device
         self.config, self.device = cfg, dev
         self._flat = {}
@@ -112,10 +114,12 @@ class TrainableReader(torch.nn.Module):
     @classmethod
     def from_args(cls, config, args, device=None, **kwargs):
         """The reference's flags (qa/train_retrieve_qa.py): shared_norm, drop_early, qa_drop, separate, add_select and
-        retriever_path; BERT's two dropout rates come from kwargs (the reference takes them from the pretrained config)."""
+        retriever_path, and this project's `deterministic`; BERT's two dropout rates come from kwargs (the reference takes them
+        from the pretrained config)."""
         model = cls(config, device, shared_norm=getattr(args, "shared_norm", False), drop_early=getattr(args, "drop_early", False),
                     qa_drop=getattr(args, "qa_drop", 0.0), separate=getattr(args, "separate", False),
-                    add_select=getattr(args, "add_select", False), **kwargs)
+                    add_select=getattr(args, "add_select", False), deterministic=getattr(args, "deterministic", False),
+                    **kwargs)
         if getattr(args, "retriever_path", ""):
             model.load_pretrained_retriever(args.retriever_path)
         return model
@@ -196,10 +200,10 @@ class TrainableReader(torch.nn.Module):
 
         hidden, cu, lens, max_len = run_tower(self._flat, "bert", self.config, ids, net_input["input_mask"],
                                               type_ids=net_input["segment_ids"], drop=(p_hid, p_att, seed, call),
-                                              probe_extra=paragraph_probe)
+                                              probe_extra=paragraph_probe, deterministic=self.deterministic)
         # the question tower on row 0 alone: the reference encodes B identical rows and uses q[0]
         q = run_tower(self.retriever._flat, "bert_q", self.config, net_input["input_ids_q"][:1], net_input["input_mask_q"][:1],
-                      proj="proj_q", drop=(p_hid, p_att, seed, (call + 1) & 0xFFFFFF))
+                      proj="proj_q", drop=(p_hid, p_att, seed, (call + 1) & 0xFFFFFF), deterministic=self.deterministic)
         return reader_loss(hidden, self._flat["qa_outputs.weight"], self._flat["qa_outputs.bias"], q, net_input["para_embed"],
                            net_input["top5000_labels"], net_input["start_positions"], net_input["end_positions"],
                            geometry["para_offset"], cu_seqlens=cu, shared_norm=self.shared_norm, early=not self.drop_early,

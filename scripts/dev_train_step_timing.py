@@ -2,7 +2,7 @@
 batches at the reference's --train_batch_size 640 (retrieval/train_retriever_single.sh) and at 64.
 
     python scripts/dev_train_step_timing.py [--out DIR] [--batches 640,64] [--steps 5] [--skip-trace] [--dropout P]
-                                            [--half-weights [--accumulate N]]
+                                            [--deterministic] [--half-weights [--accumulate N]]
 
 Three measurements, each in a fresh child process of this script:
   events   forward + backward + zero_grad per step between CUDA events, median of --steps after 2 warm-up steps;
@@ -15,6 +15,9 @@ Three measurements, each in a fresh child process of this script:
 dropout and a step without (the rates set to 0: the dropout-free kernels) take turns in one process, each --steps times
 after the warm-up.  `events` adds step_ms_median_dropout and dropout_step_ratio; `trace` adds dropout_kernel_ratios: the
 time of each dropout kernel over its dropout-free counterpart (the three attention kernels and the LayerNorm pair).
+--deterministic (what the fixed-order word-embedding gradient costs in a step): in `events` a step of the default module
+and a step with deterministic=True take turns in one process; adds step_ms_median_deterministic and
+deterministic_step_ratio.  Not combined with --dropout; the trace is of the default module.
 --half-weights (what the fp16 working copies are worth): the step becomes --accumulate N micro-batches of forward +
 backward, one FusedAdamW step (clip 2.0, dynamic scale) and zero_grad.  Two modules of the same weights take turns in one
 process, one casting its masters in every forward, the other with half_weights() and FusedAdamW(half_copies=...): `events`
@@ -94,7 +97,7 @@ class TorchTower:
                 "c": self.tower("bert_c", "proj_c", batch["input_ids_c"], batch["input_mask_c"])}
 
 
-def child(mode, batches, steps, dropout=0.0):
+def child(mode, batches, steps, dropout=0.0, deterministic=False):
     sys.path.insert(0, ROOT)
     import torch
     import torch.nn.functional as F
@@ -103,6 +106,8 @@ def child(mode, batches, steps, dropout=0.0):
     dev = torch.device("cuda", 0)
     model = TrainableRetriever(BERT_BASE, device=dev, dropout_seed=0)
     turns = [0.0, dropout] if dropout > 0 and mode != "torch" else [0.0]
+    fixed_order = [False, True] if deterministic and mode == "events" and len(turns) == 1 else [False]
+    turns = turns * len(fixed_order)
     result = {}
     for pairs in batches:
         batch, lq, lc = make_batch(pairs, pairs, dev)
@@ -110,6 +115,7 @@ def child(mode, batches, steps, dropout=0.0):
         times = []
         for step in range((WARMUP + steps) * len(turns)):
             model.hidden_dropout_prob = model.attention_probs_dropout_prob = turns[step % len(turns)]
+            model.deterministic = fixed_order[step % len(fixed_order)]
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             out = forward(batch)
@@ -126,7 +132,11 @@ def child(mode, batches, steps, dropout=0.0):
         result[str(pairs)] = {"step_ms_median": statistics.median(plain), "step_ms_min": min(plain),
                               "loss": float(loss), "tokens": sum(lq) + sum(lc),
                               "attention_backward_flops": attention_flops(lq, 12, 12) + attention_flops(lc, 12, 12)}
-        if len(turns) > 1:
+        if len(fixed_order) > 1:
+            fixed = times[1::2][WARMUP:]
+            result[str(pairs)].update(step_ms_median_deterministic=statistics.median(fixed),
+                                      deterministic_step_ratio=statistics.median(fixed) / statistics.median(plain))
+        elif len(turns) > 1:
             dropped = times[1::2][WARMUP:]
             result[str(pairs)].update(dropout=dropout, step_ms_median_dropout=statistics.median(dropped),
                                       dropout_step_ratio=statistics.median(dropped) / statistics.median(plain))
@@ -179,6 +189,8 @@ def child_half(mode, batches, steps, accumulate, variant):
 def run_child(mode, args, prefix=(), variant=None):
     cmd = list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", mode, "--batches", args.batches, "--steps", str(args.steps),
                           "--dropout", str(args.dropout)]
+    if getattr(args, "deterministic", False):
+        cmd += ["--deterministic"]
     if getattr(args, "half_weights", False):
         cmd += ["--half-weights", "--accumulate", str(args.accumulate)] + (["--variant", variant] if variant else [])
     out = subprocess.run(cmd, check=True, timeout=900, capture_output=True, text=True).stdout
@@ -242,6 +254,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--skip-trace", action="store_true")
     ap.add_argument("--dropout", type=float, default=0.0, help="also time steps with both dropout rates at this value")
+    ap.add_argument("--deterministic", action="store_true", help="also time steps with the word-embedding gradient in a fixed order")
     ap.add_argument("--half-weights", action="store_true", help="optimizer steps with and without the fp16 working copies")
     ap.add_argument("--accumulate", type=int, default=1, help="micro-batches per optimizer step (with --half-weights)")
     ap.add_argument("--variant", default=None, choices=["casts", "copies"], help=argparse.SUPPRESS)
@@ -250,7 +263,7 @@ def main():
     if args.child and args.half_weights:
         return child_half(args.child, batches, args.steps, args.accumulate, args.variant)
     if args.child:
-        return child(args.child, batches, args.steps, args.dropout)
+        return child(args.child, batches, args.steps, args.dropout, args.deterministic)
     if args.half_weights:
         return main_half(args, batches)
     result = {"rocm": open("/opt/rocm/.info/version").read().strip() if os.path.exists("/opt/rocm/.info/version") else "",
