@@ -654,12 +654,17 @@ __device__ __forceinline__ unsigned column_rows_mask(int rows_left) {
 // blocks are replicated over the 8 waves, the R = 8 / q_blocks waves of a block take every R-th unit each and append to
 // the block's lists (one per query and accumulator half, as ever) through list lengths kept in LDS -- an LDS atomic per
 // logged record, and records are rare where queries are few; the merge sees the same lists as from any other launch.
+//
+// The same eight-wave shape for QW = 2: FOUR four-wave workgroups of 256 queries per CU (one 128-row stage per pair, a SIMD
+// holding one wave of each of four barrier domains instead of two of each of two) measured 3 % slower (ABLATIONS R17.1).
 template <int QW, bool SPLIT = false>
 __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8 a) {
   static_assert(QW == 1 || QW == 2, "8 waves x 32 / 64 queries");
   static_assert(!SPLIT || QW == 1, "row-split launches keep one query block per wave");
-  __shared__ __attribute__((aligned(16))) char lds[4 * kStageBytesI8];
   constexpr int NW = kFilterWaves;
+  constexpr int kPairUnits = 2 * (kStageRows / kSubRows);   // 32-row units between two barriers
+  constexpr int kPairBytes = 2 * kStageBytesI8;
+  __shared__ __attribute__((aligned(16))) char lds[2 * kPairBytes];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -711,32 +716,48 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
   wave_live = __any(wave_live);
   const unsigned lane_cap = a.store.lane_cap;
 
+  // (of the pair buffer being read: the buffer bit is toggled at the end of every pair, so that a unit's fragment reads
+  // are this register plus an immediate)
   unsigned rd_off[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) rd_off[j] = li * kRowBytesI8 + (((2 * j + half) ^ ((li >> 1) & 7)) << 4);
 
-  constexpr int kDmaPerWave = (kStageBytesI8 / 1024) / NW;   // 2 per stage
-  int dma_rel[kDmaPerWave];
-  int dma_piece_off[kDmaPerWave];
+  // A wave's four LDS-DMA instructions of a pair: 1 KiB each (8 rows: 8 lanes x 16 B per row), the 4 KiB run at wave * 4 KiB
+  // of the pair's rows -- contiguous in the chunk and in the pair buffer alike, so instruction e is the first one displaced
+  // by e KiB on BOTH sides: the instruction's immediate offset, which the hardware adds to the global and to the LDS
+  // address.  Rows 8 apart alternate between two swizzles ((row >> 1) & 7 differs by 4): two per-lane byte offsets for the
+  // wave's lifetime; the pair itself is a scalar byte offset that advances by a constant.  Only the chunk's last pair can
+  // reach past its rows: there, behind a scalar condition, the row is clamped per lane (and stages past the last are skipped).
+  constexpr int kDmaPerWave = (kPairBytes / 1024) / NW;   // 4 per pair
+  static_assert(kDmaPerWave == 4 && (kDmaPerWave - 1) * 1024 < 4096, "the immediate offset of a global instruction: < 4 KiB");
+  const int dma_row0 = wave * kDmaPerWave * 8 + (lane >> 3);   // of instruction 0, in its pair
+  unsigned dma_off[2];
 #pragma unroll
-  for (int e = 0; e < kDmaPerWave; ++e) {
-    dma_rel[e] = (wave * kDmaPerWave + e) * 8 + (lane >> 3);
-    dma_piece_off[e] = ((lane & 7) ^ ((dma_rel[e] >> 1) & 7)) * 16;
-  }
-  auto issue_pair = [&](int p) {   // stages 2p, 2p+1 -> the pair buffer p % 2
+  for (int par = 0; par < 2; ++par)
+    dma_off[par] = (unsigned)(dma_row0 * kRowBytesI8 + (((lane & 7) ^ (((dma_row0 >> 1) & 7) ^ (par * 4))) * 16));
+  auto issue_pair = [&](int p) {   // the rows of pair p -> the pair buffer p % 2
+    __attribute__((address_space(3))) char* dst =
+        (__attribute__((address_space(3))) char*)(lds + (p & 1) * kPairBytes + wave * (kDmaPerWave * 1024));
+    if (__builtin_expect((p + 1) * (kPairUnits * kSubRows) <= n_rows, 1)) {
+      const signed char* pair_base = chunk_base + (long long)p * kPairBytes;
+#define PROQA_DMA(e)                                                                                                              \
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pair_base + (size_t)dma_off[(e) & 1]),         \
+                                   (__attribute__((address_space(3))) void*)dst, 16, (e) * 1024, QW == 1 ? kDmaAux : 0)
+      PROQA_DMA(0);
+      PROQA_DMA(1);
+      PROQA_DMA(2);
+      PROQA_DMA(3);
+#undef PROQA_DMA
+    } else {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int s = 2 * p + h;
-      if (s < nstages) {
-#pragma unroll
-        for (int e = 0; e < kDmaPerWave; ++e) {
-          int rel = s * kStageRows + dma_rel[e];
+      for (int e = 0; e < kDmaPerWave; ++e) {
+        const int row0 = p * (kPairUnits * kSubRows) + (wave * kDmaPerWave + e) * 8;   // wave-uniform
+        if (row0 < nstages * kStageRows) {
+          int rel = row0 + (lane >> 3);
           rel = rel < n_rows ? rel : n_rows - 1;
-          const signed char* src = chunk_base + (long long)rel * kRowBytesI8 + dma_piece_off[e];
+          const signed char* src = chunk_base + (long long)rel * kRowBytesI8 + (dma_off[e & 1] & 127u);
           __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                           (__attribute__((address_space(3))) void*)(lds + ((p & 1) * 2 + h) * kStageBytesI8 +
-                                                                                     (wave * kDmaPerWave + e) * 1024),
-                                           16, 0, QW == 1 ? kDmaAux : 0);
+                                           (__attribute__((address_space(3))) void*)(dst + e * 1024), 16, 0, QW == 1 ? kDmaAux : 0);
         }
       }
     }
@@ -782,35 +803,35 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
   // before the pair's barrier: scalar loads return out of order with LDS reads, so any lgkmcnt wait for a fragment read is
   // a wait for this load too -- at the barrier the wave waits anyway, mid-pair (the former place) every wave stalled for
   // the scalar round trip behind its unit 2.
-  auto load_blocks = [&](int p) {
-    const unsigned long long addr = (unsigned long long)(a.blk + (row_begin >> 5) + 8ll * p);
+  // (The address is made wave-uniform ONCE and runs on as a scalar.)
+  unsigned long long blk_addr;
+  {
+    const unsigned long long addr = (unsigned long long)(a.blk + (row_begin >> 5));
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)addr);
     const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(addr >> 32));
-    const unsigned long long uaddr = ((unsigned long long)hi << 32) | lo;
-    return *(const __attribute__((address_space(4))) f32x16*)uaddr;
-  };
+    blk_addr = ((unsigned long long)hi << 32) | lo;
+  }
   for (int p = 0; wave_live && p < npairs; ++p) {
-    const f32x16 bc = load_blocks(p);
+    const f32x16 bc = *(const __attribute__((address_space(4))) f32x16*)blk_addr;
+    blk_addr += kPairUnits * sizeof(float2);
     publish();
     if (p + 1 < npairs) issue_pair(p + 1);
-    const char* base = lds + (p & 1) * 2 * kStageBytesI8;
     const int nunits = (nstages - 2 * p >= 2 ? 2 : 1) * (kStageRows / kSubRows);
     i32x4 af[4];
     if constexpr (!SPLIT) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) af[j] = *(const i32x4*)(base + rd_off[j]);
+      for (int j = 0; j < 4; ++j) af[j] = *(const i32x4*)(lds + rd_off[j]);
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
+    for (int u = 0; u < kPairUnits; ++u) {
       if (u == 4 && nunits <= 4) break;   // (the chunk's last pair may hold one stage)
       if constexpr (SPLIT) {
         // this wave's units of the pair: every n_slices-th (wave-uniform); its fragments are read on the spot -- with an
         // eighth / a quarter / half of the units per wave nothing here is on the critical path of the stream
         if (((unsigned)u & (n_slices - 1u)) != slice) continue;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) af[j] = *(const i32x4*)(base + u * kSubBytesI8 + rd_off[j]);
+        for (int j = 0; j < 4; ++j) af[j] = *(const i32x4*)(lds + rd_off[j] + u * kSubBytesI8);
       }
-      const char* nxt = base + (u + 1 < nunits ? u + 1 : u) * kSubBytesI8;
       i32x16 acc[QW];
 #pragma unroll
       for (int blk = 0; blk < QW; ++blk) acc[blk] = i32x16{0};
@@ -820,9 +841,14 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
         for (int blk = 0; blk < QW; ++blk)
           acc[blk] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[j], qf[blk][j], acc[blk], 0, 0, 0);
       }
+      // the next unit's fragments, under the MFMAs just issued.  (The pair's last unit has none to read: the next pair is
+      // not published yet.  A one-stage last pair re-reads its unit 3, as ever: no branch for it.)
       if constexpr (!SPLIT) {
+        if (u + 1 < kPairUnits) {
+          const int nxt = (u + 1 < nunits ? u + 1 : u) * kSubBytesI8;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) af[j] = *(const i32x4*)(nxt + rd_off[j]);
+          for (int j = 0; j < 4; ++j) af[j] = *(const i32x4*)(lds + rd_off[j] + nxt);
+        }
       }
       bool hit[QW];
       float tb[QW];
@@ -834,7 +860,7 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
         any_hit = any_hit || hit[blk];
       }
       if (__builtin_expect(__any(any_hit), 0)) {
-        int rel0 = (2 * p * 4 + u) * kSubRows;
+        int rel0 = (p * kPairUnits + u) * kSubRows;
         asm volatile("" : "+v"(rel0));
         const int rel = rel0 + 4 * half;
 #pragma unroll
@@ -857,9 +883,9 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
               // (the empty asm keeps the region a BRANCH: without it hipcc hoists and if-converts it -- the ~40 VALU instructions
               // of column_rows_mask ran at the head of every hit path, selected away by a v_cndmask at the end: ABLATIONS R6.8)
 #ifdef PROQA_TAILMASK_HOISTED   // developer A/B build: the round-5 form
-              if ((2 * p * 4 + u + 1) * kSubRows > n_rows) mask &= column_rows_mask(n_rows - rel);
+              if ((p * kPairUnits + u + 1) * kSubRows > n_rows) mask &= column_rows_mask(n_rows - rel);
 #else
-              if ((2 * p * 4 + u + 1) * kSubRows > n_rows) {
+              if ((p * kPairUnits + u + 1) * kSubRows > n_rows) {
                 int rows_left = n_rows - rel;
                 asm volatile("" : "+v"(rows_left));   // (an opaque value born inside the region: nothing of it can be hoisted)
                 mask &= column_rows_mask(rows_left);
@@ -872,6 +898,8 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
         }
       }
     }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rd_off[j] ^= (unsigned)kPairBytes;   // the other pair buffer
   }
   if constexpr (SPLIT) {
     // the lengths of the shared lists: complete once every wave of the workgroup is here.  The waves of slice 0 report their
