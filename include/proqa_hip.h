@@ -349,6 +349,27 @@ int proqa_reader_span_f16(const void* hidden, const int32_t* seq_lens_dev, const
                           int seq_len, int hidden_size, const int32_t* para_offset_dev, const void* qa_w, const void* qa_b,
                           int max_answer_len, int32_t* start_out, int32_t* end_out, float* score_out, void* logits_out,
                           void* stream);
+/* proqa_reader_span_f16 with the first n_best spans of every sequence and the log-partitions of its logits, in the same
+ * single launch (hidden is read once, no [L, L] tensor).  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive).
+ *   Layouts, logits (same device function, same bits), paragraph mask and candidates are those of proqa_reader_span_f16: a
+ *   candidate is (i, j), para_offset[b] <= i <= j < len(b) - 1, j - i <= max_answer_len, score = fp32(start[i]) +
+ *   fp32(end[j]), and a score that is -inf or NaN is no candidate (+inf is one).
+ *   ORDER: score descending (-0 equals +0), then start ascending, then end ascending -- a total order, so the result does not
+ *   depend on scheduling.  Row b of start_out / end_out / score_out [batch, n_best] holds the first n_best candidates in that
+ *   order and (-1, -1, -inf) where there are fewer; entry 0 equals proqa_reader_span_f16's output in all three fields, bit
+ *   for bit.  score_out holds the fp32 sum itself.
+ *   lse_out [batch, 2] fp32 = (Z^s_b, Z^e_b): the log-sum-exp of the fp16 start / end logits over the paragraph rows
+ *   [para_offset[b], len(b) - 1) of sequence b alone -- what proqa_reader_loss_f16 keeps in stats without the shared norm,
+ *   not bit for bit: here max + log(sum exp(x - max)) with every sum in a fixed order (no atomics, bit-identical from run to
+ *   run).  -inf for an empty paragraph or one whose logits are all -inf; +inf when a logit is +inf; NaN when one is NaN.
+ *   P(span | sequence) = exp(score - Z^s - Z^e) under a per-passage norm; the shared norm of training is the host's
+ *   log-sum-exp of these over a question's sequences (proqa_amd.qa_utils.marginal_answers).
+ * Limits: 1 <= n_best <= 32, max_answer_len >= 0, otherwise those of proqa_reader_span_f16; anything else is PROQA_EINVAL
+ * before the device is touched.  logits_out optional, as there. */
+int proqa_reader_span_nbest_f16(const void* hidden, const int32_t* seq_lens_dev, const int32_t* cu_seqlens_dev, int batch,
+                                int seq_len, int hidden_size, const int32_t* para_offset_dev, const void* qa_w,
+                                const void* qa_b, int max_answer_len, int n_best, int32_t* start_out, int32_t* end_out,
+                                float* score_out, float* lse_out, void* logits_out, void* stream);
 /* select_outputs = Linear(hidden, 1) on the pooled output (--add-select): out[b] = fp16(pooled[b] . select_w + select_b),
  * returned as fp32 [batch] (device).  pooled [batch, hidden] and select_w [hidden] fp16, 16-byte aligned. */
 int proqa_reader_select_f16(const void* pooled, int batch, int hidden_size, const void* select_w, const void* select_b,

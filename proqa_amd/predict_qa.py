@@ -9,6 +9,10 @@ Same command line, same printed lines in the same order.  Where the reference ru
     4. the reader over packed batches of up to --reader-batch sequences (proqa_encoder_forward_hidden +
        proqa_reader_span_f16: the best span of each sequence comes back, never the [B, L, L] score tensor),
     5. answer texts and the alpha sweep on the host.
+With --n-best N (not in the reference) step 4 runs proqa_reader_span_nbest_f16 instead -- the N best spans of every
+sequence and its two log-partitions, still one launch per batch -- and after the unchanged alpha sweep one more line
+reports the EM of marginal decoding (qa_utils.marginal_answers: an answer's probability summed over its mentions in all
+of the question's passages, normalised per --marginal).
 The rank score of a passage is its fp32 dot product with the fp16 question embedding (the search score of the exact
 index; under --search ivf the inner product the IVF search returns beside its L2 distance, as the reference's rank_logits
 is q . para_embed of the gathered rows, qa/bert_retrieve_qa.py:76); under --efficient_eval the reference rounds it to
@@ -29,6 +33,7 @@ TRAINING_FLAGS = ("--do_train", "--train_file", "--raw-train-data", "--learning_
                   "--matched-para-path", "--fix-para-encoder", "--MI", "--drop-early", "--save-all")
 
 LAST_RUN_STATS = {}
+N_BEST_MAX = 32       # proqa_reader_span_nbest_f16's limit
 
 
 def build_parser():
@@ -62,11 +67,18 @@ def build_parser():
                         "inner-product quantizer, qa/online_sampler.py:75-79; not in the reference's command line)")
     p.add_argument("--nlist", type=int, default=100, help="--search ivf: inverted lists (the reference's 100)")
     p.add_argument("--nprobe", type=int, default=20, help="--search ivf: lists probed per question (the reference's 20)")
+    p.add_argument("--n-best", type=int, default=0,
+                   help="spans per passage for marginal answer decoding, 1..32; 0 = off (not in the reference)")
+    p.add_argument("--marginal", choices=("shared", "passage"), default="shared",
+                   help="--n-best: span probabilities normalised over all passages of a question, as --shared-norm trains "
+                        "them (default), or per passage")
     return p
 
 
 def check_search_args(args):
-    """Refuses --search ivf settings the index cannot run, before any GPU work."""
+    """Refuses --n-best / --search ivf settings the kernels cannot run, before any GPU work."""
+    if not 0 <= getattr(args, "n_best", 0) <= N_BEST_MAX:
+        raise SystemExit(f"--n-best {args.n_best} outside [0, {N_BEST_MAX}]")
     if args.search != "ivf":
         return
     from .index import IVF_MAX_K
@@ -95,13 +107,16 @@ def evaluate(args, reader, tokenizer, qa_data, index, index2paraid, stats=None, 
     """Steps 1-5 of the module's docstring over loaded pieces: reader (a BertReader), the questions of qa_data, an index that
     holds the rows (IndexFlatIP, or IndexIVFFlat under args.search == "ivf") and its idx_id.json mapping.  Prints the alpha
     sweep's lines through `say`, fills the per-stage seconds into `stats`, returns the best EM.  Also the dev evaluation of
-    train_reader.py, over the index its sampler searches."""
+    train_reader.py, over the index its sampler searches.  args.n_best > 0 (absent = 0): one more line after the sweep, the
+    EM of marginal decoding under args.marginal (absent = "shared"), and stats["marginal_em"]; the return value stays the
+    sweep's."""
     import torch
     from . import qa_utils as qu
     from .datasets import TokenizeCollate
     from .utils import DocDB
     stats = {} if stats is None else stats
     dev = reader.device
+    n_best, norm = int(getattr(args, "n_best", 0) or 0), getattr(args, "marginal", "shared")
     # 1 + 2: all questions through the question tower, one search
     t0 = time.perf_counter()
     questions = [qa["question"] for qa in qa_data]
@@ -140,7 +155,7 @@ def evaluate(args, reader, tokenizer, qa_data, index, index2paraid, stats=None, 
     t2 = time.perf_counter()
 
     # 4: the reader over packed batches
-    spans, selects = [], []
+    spans, selects, nbest = [], [], []
     for b0 in range(0, len(items), args.reader_batch):
         chunk = items[b0:b0 + args.reader_batch]
         L = max(len(it[3]) for it in chunk)
@@ -150,17 +165,25 @@ def evaluate(args, reader, tokenizer, qa_data, index, index2paraid, stats=None, 
             ids[k, :len(it[3])] = it[3]
             seg[k, :len(it[4])] = it[4]
         out = reader.forward({"input_ids": torch.from_numpy(ids).to(dev), "segment_ids": torch.from_numpy(seg).to(dev),
-                              "seq_lens": [len(it[3]) for it in chunk], "para_offset": [it[5] for it in chunk]})
+                              "seq_lens": [len(it[3]) for it in chunk], "para_offset": [it[5] for it in chunk]},
+                             n_best=n_best)
+        if n_best:
+            nbest.append(torch.cat([out["nbest_start"], out["nbest_end"], out["nbest_score"].view(torch.int32),
+                                    out["span_lse"].view(torch.int32)], 1))
         spans.append(torch.stack([out["start"], out["end"], out["span_score"].view(torch.int32)], 1))
         if out["select"] is not None:
             selects.append(out["select"])
     spans = torch.cat(spans).cpu().numpy() if spans else np.zeros((0, 3), np.int32)
     selects = torch.cat(selects).cpu().numpy().tolist() if selects else None
+    nbest = torch.cat(nbest).cpu().numpy() if nbest else np.zeros((0, 3 * n_best + 2), np.int32)   # starts, ends, scores, lse
     t3 = time.perf_counter()
 
     # 5: texts, grouping by question hash, alpha sweep
-    qid2results, qid2ground = {}, {}
+    qid2results, qid2ground, qid2passages = {}, {}, {}
     scores = spans[:, 2].copy().view(np.float32).tolist()
+    if n_best:
+        nb_score = nbest[:, 2 * n_best:3 * n_best].copy().view(np.float32)
+        nb_lse = nbest[:, 3 * n_best:].copy().view(np.float32)
     for n, (qi, r, d, _, _, po) in enumerate(items):
         p = prepared[r]
         text = qu.answer_text(int(spans[n, 0]), int(spans[n, 1]), po, p["doc_tokens"], p["all_doc_tokens"],
@@ -171,8 +194,28 @@ def evaluate(args, reader, tokenizer, qa_data, index, index2paraid, stats=None, 
             "span_score": scores[n] if spans[n, 0] >= 0 else None,
             "passage": " ".join(p["doc_tokens"]), "question": questions[qi]})
         qid2ground[qid] = qa_data[qi]["answer"]
+        if n_best:
+            cand = [(text if k == 0 else
+                     qu.answer_text(int(nbest[n, k]), int(nbest[n, n_best + k]), po, p["doc_tokens"], p["all_doc_tokens"],
+                                    p["tok_to_orig_index"], args.do_lower_case), float(nb_score[n, k]))
+                    for k in range(n_best) if nbest[n, k] >= 0]
+            qid2passages.setdefault(qid, []).append({"rank_score": selects[n] if args.add_select else d,
+                                                     "lse": nb_lse[n].tolist(), "candidates": cand})
     _, best = qu.alpha_sweep(qid2results, qid2ground, regex=args.regex,
                              save_prefix=args.prefix if args.save_pred else None, out=say)
+    if n_best:
+        match_fn = qu.regex_match_score if args.regex else qu.exact_match_score
+        ems, saved = [], {}
+        for qid, passages in qid2passages.items():
+            answers = qu.marginal_answers(passages, norm)
+            top = answers[0]["text"] if answers else ""
+            ems.append(qu.metric_max_over_ground_truths(match_fn, top, qid2ground[qid]))
+            saved[qid] = [{"answer": a["text"], "prob": a["prob"]} for a in answers[:n_best]]
+        stats["marginal_em"] = float(np.mean(ems)) if ems else 0.0
+        say(f"marginal (n-best {n_best}, {norm} norm): avg. EM: {stats['marginal_em']}")
+        if args.save_pred:
+            with open(f"{args.prefix}_marginal.json", "w") as g:
+                json.dump(saved, g)
     t4 = time.perf_counter()
     stats.update(questions=len(questions), sequences=len(items), tokens=int(sum(len(it[3]) for it in items)),
                  search_seconds=t1 - t0, pair_building_seconds=t2 - t1, reader_seconds=t3 - t2, postprocess_seconds=t4 - t3)

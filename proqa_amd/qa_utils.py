@@ -7,6 +7,8 @@ Written for this project and pinned to the reference's behaviour by tests/golden
     normalize_answer, exact_match_score, regex_match_score, metric_max_over_ground_truths   qa/official_eval.py
     hash_question       qa/prepro_utils.py:12-14
     alpha_sweep         qa/train_retrieve_qa.py:365-397
+marginal_answers (answer probabilities summed over the n-best spans of a question's passages) is not in the reference: it
+is the decoding rule its training objective implies.
 """
 import ctypes
 import hashlib
@@ -360,3 +362,52 @@ def alpha_sweep(qid2results, qid2ground, regex=False, save_prefix=None, out=prin
                 for line in saved:
                     g.write(json.dumps(line) + "\n")
     return res, best
+
+
+# ---- marginal decoding over n-best spans --------------------------------------------------------------------------
+
+def _logsumexp(xs):
+    """float64 log-sum-exp of a list; -inf for an empty list or one of -inf only"""
+    m = max(xs, default=-np.inf)
+    if not np.isfinite(m):
+        return float(m)
+    return float(m + np.log(np.sum(np.exp(np.asarray(xs, np.float64) - m))))
+
+
+def marginal_answers(results, norm="shared"):
+    """The decoding rule of the training objective (proqa_reader_loss_f16): the probability of an answer is the sum over
+    its mentions, across the passages of one question, of exp(l), l = span score - Z + log r_b.
+
+    results: the question's passages in retrieval order, each dict(rank_score: d_b, lse: (Z^s_b, Z^e_b), candidates:
+    [(text, score), ...] in n-best order).  log r_b is the log-softmax of the rank scores over these passages.  norm
+    "passage": Z = Z^s_b + Z^e_b, every passage normalised on its own; "shared": Z = logsumexp_b Z^s_b + logsumexp_b Z^e_b,
+    the shared norm of training over the question's sequences.  Everything in float64.
+
+    Returns [dict(key, prob, text)] sorted by prob descending: key = normalize_answer(text), text that of the key's first
+    mention in (passage, n) order, which also breaks ties.  Mentions with empty text are dropped unless there is nothing
+    else; a mention whose l is NaN (overflowed logits) is dropped."""
+    if norm not in ("shared", "passage"):
+        raise ValueError(f"norm must be 'shared' or 'passage', got {norm!r}")
+    if not results:
+        return []
+    log_r = np.asarray([x["rank_score"] for x in results], np.float64)
+    log_r = log_r - _logsumexp(log_r.tolist())
+    shared = _logsumexp([float(x["lse"][0]) for x in results]) + _logsumexp([float(x["lse"][1]) for x in results])
+    mentions = []       # (text, l) in (passage, n) order
+    with np.errstate(invalid="ignore", over="ignore"):
+        for b, x in enumerate(results):
+            z = shared if norm == "shared" else float(x["lse"][0]) + float(x["lse"][1])
+            for text, score in x["candidates"]:
+                l = np.float64(score) - z + log_r[b]
+                if not np.isnan(l):
+                    mentions.append((text, l))
+        mentions = [m for m in mentions if m[0].strip()] or mentions
+        order, prob, first = [], {}, {}
+        for text, l in mentions:
+            key = normalize_answer(text)
+            if key not in prob:
+                order.append(key)
+                prob[key], first[key] = 0.0, text
+            prob[key] += float(np.exp(l))
+    rank = {k: n for n, k in enumerate(order)}
+    return [{"key": k, "prob": prob[k], "text": first[k]} for k in sorted(order, key=lambda k: (-prob[k], rank[k]))]

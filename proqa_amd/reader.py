@@ -2,6 +2,7 @@
 
     reader = BertReader.load(checkpoint, config, device)
     out = reader.forward(batch)   # start, end (positions in the sequence), span_score, select[, logits]
+    out = reader.forward(batch, n_best=20)   # + nbest_start / nbest_end / nbest_score [B, 20], span_lse [B, 2]
 
 The reader's BertModel runs in libproqa_hip.so (`proqa_encoder_forward_hidden`: token-type embeddings, every layer for
 every token, last hidden state in the packed [T, hidden] layout, tanh pooler), and `proqa_reader_span_f16` turns the
@@ -88,9 +89,11 @@ class BertReader:
         return hid, pooled
 
     @torch.no_grad()
-    def span(self, hidden, seq_lens, para_offset, max_len, return_logits=False, padded=False):
+    def span(self, hidden, seq_lens, para_offset, max_len, return_logits=False, padded=False, n_best=None):
         """proqa_reader_span_f16 over packed hidden states (padded=True: hidden is [B * max_len, H])
-        -> (start int32 [B], end int32 [B], score fp32 [B], logits fp16 [rows, 2] or None), on the device."""
+        -> (start int32 [B], end int32 [B], score fp32 [B], logits fp16 [rows, 2] or None), on the device.
+        n_best > 0: proqa_reader_span_nbest_f16 instead, and a fifth element dict(nbest_start, nbest_end int32 [B, N],
+        nbest_score fp32 [B, N], span_lse fp32 [B, 2]); start / end / score are then views of column 0."""
         B = len(seq_lens)
         dev = self.device
         lens = torch.tensor(seq_lens, dtype=torch.int32)
@@ -98,30 +101,46 @@ class BertReader:
         cu[1:] = torch.cumsum(lens, 0)
         lens, cu = lens.to(dev), cu.to(dev)
         po = torch.tensor(para_offset, dtype=torch.int32).to(dev)
+        logits = torch.zeros((hidden.shape[0], 2), dtype=torch.float16, device=dev) if return_logits else None
+        layout = (hidden.data_ptr(), lens.data_ptr() if padded else None, None if padded else cu.data_ptr(), B, int(max_len),
+                  hidden.shape[1], po.data_ptr(), self.qa_w.data_ptr(), self.qa_b.data_ptr(), int(self.max_answer_len))
+        logits_ptr = logits.data_ptr() if logits is not None else None
+        if n_best:
+            N = int(n_best)
+            nb_start = torch.empty((B, N), dtype=torch.int32, device=dev)
+            nb_end = torch.empty((B, N), dtype=torch.int32, device=dev)
+            nb_score = torch.empty((B, N), dtype=torch.float32, device=dev)
+            lse = torch.empty((B, 2), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(self._lib.proqa_reader_span_nbest_f16(
+                    *layout, N, nb_start.data_ptr(), nb_end.data_ptr(), nb_score.data_ptr(), lse.data_ptr(), logits_ptr,
+                    _lib.current_stream_ptr()))
+            nbest = {"nbest_start": nb_start, "nbest_end": nb_end, "nbest_score": nb_score, "span_lse": lse}
+            return nb_start[:, 0], nb_end[:, 0], nb_score[:, 0], logits, nbest
         start = torch.empty(B, dtype=torch.int32, device=dev)
         end = torch.empty(B, dtype=torch.int32, device=dev)
         score = torch.empty(B, dtype=torch.float32, device=dev)
-        logits = torch.zeros((hidden.shape[0], 2), dtype=torch.float16, device=dev) if return_logits else None
         with torch.cuda.device(dev):
-            _lib.check(self._lib.proqa_reader_span_f16(
-                hidden.data_ptr(), lens.data_ptr() if padded else None, None if padded else cu.data_ptr(), B, int(max_len),
-                hidden.shape[1], po.data_ptr(), self.qa_w.data_ptr(), self.qa_b.data_ptr(), int(self.max_answer_len),
-                start.data_ptr(), end.data_ptr(), score.data_ptr(), logits.data_ptr() if logits is not None else None,
-                _lib.current_stream_ptr()))
+            _lib.check(self._lib.proqa_reader_span_f16(*layout, start.data_ptr(), end.data_ptr(), score.data_ptr(), logits_ptr,
+                                                       _lib.current_stream_ptr()))
         return start, end, score, logits
 
     @torch.no_grad()
-    def forward(self, batch, return_logits=False):
+    def forward(self, batch, return_logits=False, n_best=0):
         """batch: input_ids, segment_ids ([B, L] int64), seq_lens (host list), para_offset (host list)
         -> dict(start, end: int32 positions in the sequence (-1: no paragraph token), span_score fp32,
                 select fp32 [B] (select_outputs on the pooled output; None without it), logits [T, 2] fp16 packed
-                (return_logits), cu_seqlens (host list))."""
+                (return_logits), cu_seqlens (host list)).
+        n_best > 0 adds nbest_start / nbest_end int32 [B, N], nbest_score fp32 [B, N] (score descending, then start, then
+        end ascending; missing entries -1, -1, -inf) and span_lse fp32 [B, 2] (the log-sum-exp of the paragraph's start /
+        end logits); start / end / span_score are then column 0."""
         if self.tower is None:
             raise RuntimeError("load_state_dict must be called before forward")
         ids = batch["input_ids"]
         seq_lens = [int(x) for x in batch["seq_lens"]]
         hid, pooled = self.hidden(ids, batch["segment_ids"], seq_lens, want_pooled=self.add_select)
-        start, end, score, logits = self.span(hid, seq_lens, batch["para_offset"], ids.shape[1], return_logits)
+        start, end, score, logits, *nbest = self.span(hid, seq_lens, batch["para_offset"], ids.shape[1], return_logits,
+                                                      n_best=n_best)
         select = None
         if self.add_select:
             select = torch.empty(len(seq_lens), dtype=torch.float32, device=self.device)
@@ -132,7 +151,10 @@ class BertReader:
         cu = [0]
         for n in seq_lens:
             cu.append(cu[-1] + n)
-        return {"start": start, "end": end, "span_score": score, "select": select, "logits": logits, "cu_seqlens": cu}
+        out = {"start": start, "end": end, "span_score": score, "select": select, "logits": logits, "cu_seqlens": cu}
+        if nbest:
+            out.update(nbest[0])
+        return out
 
     __call__ = forward
 

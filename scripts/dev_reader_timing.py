@@ -9,10 +9,22 @@ same kernel's trace).
 
     python scripts/dev_reader_timing.py [--questions 2032] [--k 5] [--batch 256] [--peak-tflops 2500]
     python scripts/dev_reader_timing.py --cli [--passages 20000]   # the whole --do_predict command, phase by phase
+    python scripts/dev_reader_timing.py --cli --n-best 20          # the same with marginal decoding (postprocess_seconds)
+    python scripts/dev_reader_timing.py --n-best 1,5,20            # the n-best span kernel against the 1-best one
+
+--n-best without --cli: on the hidden states of one batch the 1-best kernel and the n-best kernel at every N of the list
+take turns in one process, 5 warm-up rounds and --span-reps timed ones.  The kernel times are those of a
+`rocprofv3 --kernel-trace` run of its own (this script starts it around a child of itself) and the figure is the median per
+variant; the yardstick is the 1-best kernel of the same run.  Prints one JSON line with the medians and their ratios.
 """
 import argparse
+import csv
+import glob
 import json
 import os
+import shutil
+import statistics
+import subprocess
 import sys
 import time
 
@@ -76,6 +88,8 @@ def run_cli(args):
                 "--index-path", f"{tmp}/embed.npy", "--db-path", f"{tmp}/docs.db", "--index2paraid", f"{tmp}/idx_id.json",
                 "--eval-k", str(args.k), "--max_seq_length", str(args.max_seq_length), "--bert_model_name", model_dir,
                 "--efficient_eval", "--reader-batch", str(args.batch)]
+        if args.n_best:
+            argv += ["--n-best", args.n_best]
         t0 = time.perf_counter()
         import contextlib
         import io
@@ -88,6 +102,71 @@ def run_cli(args):
                                                               for k, v in stats.items()}}))
 
 
+NBEST_WARMUP = 5
+
+
+def first_batch(args, dev):
+    """(reader, hidden states, seq_lens, para_offset, max_len) of the first --batch synthetic sequences"""
+    from proqa_amd.reader import BertReader, random_state_dict
+    from proqa_amd.retriever import BERT_BASE
+    reader = BertReader.load(random_state_dict(BERT_BASE, seed=0), BERT_BASE, dev)
+    chunk = synthetic_pairs(args.batch, args.max_seq_length)
+    W = max(len(c[0]) for c in chunk)
+    I = np.zeros((len(chunk), W), np.int64)
+    S = np.zeros((len(chunk), W), np.int64)
+    for k, (ids, seg, _) in enumerate(chunk):
+        I[k, :len(ids)], S[k, :len(seg)] = ids, seg
+    lens = [len(c[0]) for c in chunk]
+    hid, _ = reader.hidden(torch.from_numpy(I).to(dev), torch.from_numpy(S).to(dev), lens)
+    return reader, hid, lens, [c[2] for c in chunk], W
+
+
+def nbest_child(args, ns):
+    """the launches the trace is taken of: per round the 1-best kernel, then the n-best kernel at every N"""
+    dev = torch.device("cuda:0")
+    reader, hid, lens, po, W = first_batch(args, dev)
+    for _ in range(NBEST_WARMUP + args.span_reps):
+        reader.span(hid, lens, po, W)
+        for n in ns:
+            reader.span(hid, lens, po, W, n_best=n)
+    torch.cuda.synchronize()
+    print(json.dumps({"span_batch_tokens": int(hid.shape[0]), "sequences": len(lens)}))
+
+
+def nbest_trace(args, ns):
+    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    out_dir = args.out
+    if out_dir is None:
+        import tempfile
+        out_dir = tempfile.mkdtemp(prefix="reader_nbest_timing_")
+    os.makedirs(out_dir, exist_ok=True)
+    cmd = [prof, "--kernel-trace", "--output-format", "csv", "-d", out_dir, "--", sys.executable, os.path.abspath(__file__),
+           "--nbest-child", "--n-best", args.n_best, "--batch", str(args.batch), "--max-seq-length", str(args.max_seq_length),
+           "--span-reps", str(args.span_reps)]
+    child = subprocess.run(cmd, check=True, timeout=900, stdout=subprocess.PIPE, text=True)
+    launches = []           # (start, end, is n-best) of both span kernels, in time order
+    for path in glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path, newline="") as f:
+            for r in csv.DictReader(f):
+                if "reader_span" in r["Kernel_Name"]:
+                    launches.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "reader_span_nbest" in r["Kernel_Name"]))
+    launches.sort()
+    rounds, per = NBEST_WARMUP + args.span_reps, 1 + len(ns)
+    if len(launches) != rounds * per:
+        raise SystemExit(f"expected {rounds * per} span launches in the trace, found {len(launches)}")
+    names = ["1-best"] + [f"n={n}" for n in ns]
+    us = {}
+    for k, name in enumerate(names):
+        mine = launches[k::per]
+        if any(l[2] != (k > 0) for l in mine):
+            raise SystemExit("the trace's launches are not in the order they were issued")
+        us[name] = statistics.median(e - s for s, e, _ in mine[NBEST_WARMUP:]) / 1e3
+    result = json.loads(child.stdout.strip().splitlines()[-1])
+    result.update(reps=args.span_reps, kernel_us_median={k: round(v, 2) for k, v in us.items()},
+                  ratio_to_1best={k: round(v / us["1-best"], 3) for k, v in us.items() if k != "1-best"})
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cli", action="store_true", help="time the whole --do_predict command instead (synthetic world)")
@@ -98,9 +177,16 @@ def main():
     ap.add_argument("--max-seq-length", type=int, default=512)
     ap.add_argument("--peak-tflops", type=float, default=2500.0, help="dense fp16 peak of the device (MI355X: ~2.5 PFLOP/s)")
     ap.add_argument("--span-reps", type=int, default=50)
+    ap.add_argument("--n-best", type=str, default="",
+                    help="with --cli: --n-best of the command; without: the Ns of the n-best kernel to time, e.g. 1,5,20")
+    ap.add_argument("--nbest-child", action="store_true", help="(the traced child of --n-best)")
+    ap.add_argument("--out", default=None, help="--n-best: directory of the profiler's output (default: a temporary one)")
     args = ap.parse_args()
     if args.cli:
         return run_cli(args)
+    if args.n_best:
+        ns = [int(n) for n in args.n_best.split(",")]
+        return nbest_child(args, ns) if args.nbest_child else nbest_trace(args, ns)
     from proqa_amd.reader import BertReader, random_state_dict
     from proqa_amd.retriever import BERT_BASE
     dev = torch.device("cuda:0")
