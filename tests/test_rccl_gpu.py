@@ -1,7 +1,10 @@
 """The RCCL exchange of the sharded search on real hardware.  The test box has ONE GPU and RCCL refuses two ranks
 on one device, so the collective is exercised with a single rank: `ncclAllGather` / `all_gather_into_tensor` really
 run (communicator init, the flat byte buffer, the strided merge), only the wire is trivial.  Two ranks with the real
-kernels are covered over gloo in test_distributed_gpu.py, the rank arithmetic on CPU in test_sharded_gloo.py."""
+kernels are covered over gloo in test_distributed_gpu.py, the rank arithmetic on CPU in test_sharded_gloo.py.  With one
+rank the rank merge (merge_sorted_lists) is a copy and the exchange protocol never hears from another rank: the merge of 2
+to 64 parts and the multi-rank branches of the protocol (a peer asks for a second exchange, a peer is poisoned, the ranks
+never agree) are covered in test_rank_merge_gpu.py, in one process and without RCCL."""
 import os
 import socket
 

@@ -963,8 +963,9 @@ def test_non_finite_scores_follow_the_heap_rule(gpu_device, n, nq, k):
 @pytest.mark.gpu
 @pytest.mark.parametrize("bounds,k", [([(0, 60), (60, 5000), (5000, 9000)], 80), ([(0, 3000), (3000, 9000)], 300)])
 def test_shards_with_non_finite_scores_merge_like_the_unsharded_search(gpu_device, bounds, k):
-    """The rank merge of per-shard lists with +inf scores, excluded NaN / -inf rows and a shard shorter than k (its list ends
-    in I = -1 slots) equals the heap rule applied to the whole corpus."""
+    """The sorting merge (merge_topk_device) of per-shard lists with +inf scores, excluded NaN / -inf rows and a shard shorter
+    than k (its list ends in I = -1 slots) equals the heap rule applied to the whole corpus.  (The rank merge of the same kind
+    of lists: test_rank_merge_gpu.py::test_non_finite_scores_survive_the_rank_merge.)"""
     import torch
     from proqa_amd.index import IndexFlatIP, merge_topk_device
     rng = np.random.default_rng(len(bounds) * 100 + k)
