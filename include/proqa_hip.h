@@ -895,6 +895,46 @@ int proqa_inbatch_eval_f16(const void* q, const void* c, const int32_t* target, 
                            void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Answer pre-filter of the matched-paragraph file (qa/prepro_dense.py:126-158, process_ground_paras): which of a question's
+ * retrieved passages can hold one of its answer aliases at all.  The reference tokenises every (question, passage) pair;
+ * here the FOLDED passage texts (NFD, lower-cased, final sigma -> sigma, UTF-8: the caller folds them, once) live in HBM and
+ * the device runs the substring test of proqa_amd.eval_retrieval._may_match on the rows a search left on the device.
+ *
+ * Text store.  blob_host: blob_bytes of folded text; spans_host int64 [rows, 2]: first byte and end of every row's text in
+ * the blob (rows may share a span: that text is stored once; spans may touch or overlap).  The texts are copied to the
+ * current device, each distinct span at a multiple of 16 bytes and zero-padded to the next, so the kernel's 16-byte loads
+ * stay inside the allocation; bytes outside a row's span never count as its text.  rows < 2^31, a text < 2 GiB, 64 GiB of
+ * padded text at most.  Arguments are validated before the device is touched.
+ * ---------------------------------------------------------------------------------- */
+typedef struct proqa_textstore proqa_textstore;
+int proqa_textstore_create(const void* blob_host, int64_t blob_bytes, const int64_t* spans_host, int64_t rows,
+                           proqa_textstore** out);
+int proqa_textstore_destroy(proqa_textstore* store);
+/* rows of the store and the bytes its (de-duplicated, padded) texts take in HBM; either pointer may be NULL */
+int proqa_textstore_info(const proqa_textstore* store, int64_t* rows, int64_t* device_text_bytes);
+/* Needle table of nq questions (host arrays; validated, packed and uploaded here: the one call that allocates and waits).
+ *   token_bytes, token_off int64 [n_tokens + 1]      the folded tokens of all questions, back to back, and their offsets
+ *   question_token_off int64 [nq + 1]                question q owns the DISTINCT tokens [off[q], off[q + 1])
+ *   alias_tokens int32, alias_off int64 [n_aliases + 1]   alias a needs the tokens alias_tokens[alias_off[a] .. alias_off[a + 1]),
+ *                                                    indexes into ITS QUESTION's tokens (order and repeats do not matter)
+ *   question_alias_off int64 [nq + 1]                question q owns the aliases [off[q], off[q + 1])
+ * Limits (PROQA_EINVAL, checked before the device is touched): a token has 1..255 bytes; a question has at most 128 distinct
+ * tokens, 64 aliases and 4096 token bytes; nq < 2^24. */
+typedef struct proqa_text_needles proqa_text_needles;
+int proqa_text_needles_create(const void* token_bytes, const int64_t* token_off, const int64_t* question_token_off,
+                              const int32_t* alias_tokens, const int64_t* alias_off, const int64_t* question_alias_off,
+                              int64_t nq, proqa_text_needles** out);
+int proqa_text_needles_destroy(proqa_text_needles* needles);
+/* ids_dev int64 [nq, k] (device; what proqa_index_search_device returns: -1 = empty slot), 1 <= k <= 16384, nq = the
+ * table's.  mask_out uint32 [nq, ceil(k / 32)] (device): bit (j & 31) of word j / 32 of row q is set iff ids[q, j] is a row of
+ * the store and some alias of question q has every one of its tokens as a byte substring of that row's text -- an alias
+ * without tokens matches every row, a question without aliases none; bits at or past k are 0.  count_out int32 [nq] (device,
+ * optional): the set bits of each row.  Enqueued on `stream`: no allocation, no host wait; plain stores only (a wave owns a
+ * whole mask word), so the result is the same bits on every run. */
+int proqa_text_prefilter(const proqa_textstore* store, const proqa_text_needles* needles, const int64_t* ids_dev, int64_t nq,
+                         int k, uint32_t* mask_out, int32_t* count_out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * .npy index files.  Replace np.save (retrieval/get_embed.py:139) and np.load
  * (retrieval/eval_retrieval.py:99-100) for 2-D C-order '<f2' / '<f4' arrays, format v1.0,
  * header padded so that data starts at a multiple of 64 bytes.

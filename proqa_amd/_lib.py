@@ -259,6 +259,13 @@ SIGNATURES = {
     "proqa_ivf_list_ids": (c_int, [c_void_p, c_void_p]),
     "proqa_ivf_reset": (c_int, [c_void_p]),
     "proqa_ivf_search_stats": (c_int, [c_void_p, ctypes.POINTER(IvfStats)]),
+    "proqa_textstore_create": (c_int, [c_void_p, c_int64, c_void_p, c_int64, ctypes.POINTER(c_void_p)]),
+    "proqa_textstore_destroy": (c_int, [c_void_p]),
+    "proqa_textstore_info": (c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    "proqa_text_needles_create": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                          ctypes.POINTER(c_void_p)]),
+    "proqa_text_needles_destroy": (c_int, [c_void_p]),
+    "proqa_text_prefilter": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "proqa_npy_stat": (c_int, [c_char_p, ctypes.POINTER(NpyInfo)]),
     "proqa_npy_read_rows": (c_int, [c_char_p, c_int64, c_int64, c_void_p, c_size_t]),
     "proqa_npy_write": (c_int, [c_char_p, c_void_p, c_int64, c_int64, c_int]),

@@ -36,6 +36,7 @@ SOURCES = [
     "kmeans_kernels.hip",
     "ivf_index.cpp",
     "ivf_kernels.hip",
+    "text_match_kernels.hip",
     "microbench.hip",
 ]
 
