@@ -791,7 +791,14 @@ typedef struct proqa_kmeans proqa_kmeans;
 int proqa_kmeans_create(int d, int64_t n_max, int k, proqa_kmeans** out);
 int proqa_kmeans_free(proqa_kmeans* h);
 /* nearest centroid of every point: assign int32 [n]; dist float32 [n] = squared L2 distance
- * (metric_l2 != 0) or inner product; exact ties go to the lowest centroid index */
+ * (metric_l2 != 0) or inner product; exact ties go to the lowest centroid index.
+ * Supported range: every centroid component a finite number of at most 65504 in size (what fp16 holds), and for the L2
+ * metric |c| <= 65504 for every centroid (its -|c|^2/2 rides on the matrix pipe as five fp16 terms, exact up to there).
+ * Centroids outside it are refused with PROQA_EINVAL and nothing is written to assign / dist: the centroid preparation
+ * raises a word on the device, the assignment kernels queued behind it leave at once when it is set, and the call
+ * returns once that word has reached the host: it waits for the work queued on `stream` BEFORE it and for the centroid
+ * preparation (microseconds), not for the assignment, which is still asynchronous.  Points are any fp16 values; a point
+ * with a non-finite component gets an unspecified label in [0, k) and does not affect the others. */
 int proqa_kmeans_assign_device(proqa_kmeans* h, const void* x_f16_dev, int64_t n, const float* centroids_dev,
                                int metric_l2, int32_t* assign_dev, float* dist_dev, void* stream);
 /* the same with a hint per point (int32 [n], may be NULL, may alias assign_dev): any centroid index -- a Lloyd loop passes

@@ -12,8 +12,8 @@
 //            of a threshold test.  Centroids are fp32 in faiss; to keep fp32-grade dot products on
 //            the fp16 matrix pipe every centroid row is split into hi + lo fp16 parts (x.c =
 //            x.c_hi + x.c_lo, 16 k-steps) and, for L2, one extra k-step carries -|c|^2/2 split
-//            into three fp16 terms against a constant 1 in the point operand:
-//            argmin |x-c|^2 = argmax (x.c - |c|^2/2).
+//            into five fp16 terms against constants in the point operand (three against 1, two against 2^15:
+//            exact up to |c| = 65504, see kNormScale): argmin |x-c|^2 = argmax (x.c - |c|^2/2).
 //            Two passes: the hi parts alone nominate (half the k-steps; the lo parts move a score by at most
 //            |x| max|c_lo|, so a lead larger than twice that decides), the full-precision kernel runs over the few
 //            per cent of the points the nomination leaves undecided -- see kmeans_assign's MODEs.
@@ -56,9 +56,20 @@ constexpr int kAssignWaves = 8;
 constexpr int kAssignThreads = kAssignWaves * 64;
 constexpr int kPointsPerBlock = kAssignWaves * 64;         // 2 blocks of 32 points per wave
 
-// fp32 centroids -> MFMA operand rows [k_pad][280] fp16: c_hi | c_lo | (-|c|^2/2 as 3 fp16) | 0
-// stats (optional): {max_c |c_lo|^2, max_c |c_hi + c_lo|^2} as float bits (non-negative: unsigned order = float order),
-// zeroed by the caller -- what the nominating pass of the assignment bounds its error with
+// The L2 norm term h = -|c|^2/2 of a centroid, as the norm k-step carries it: three fine fp16 terms against 1 and two
+// coarse ones against 2^15 in the point operand's constant vector (`ones` in kmeans_assign).  |h| < 2^15 -- every embedding
+// this project produces -- has no coarse part: a + b + cc, exact unless a term underflows.  Above that
+// p = fp16(h / 2^15) and p2 = fp16((h - p 2^15) / 2^15) take the leading 22 bits and the fine terms the rest, so h is
+// carried exactly up to |h| = 65504 * 2^15: |c| = 65504 (kMaxNorm2 = 65504^2) is the documented limit, and it also
+// keeps every component an fp16 number.  Beyond it prep_centroids raises the refusal word and the call fails.
+constexpr float kNormScale = 32768.0f;
+constexpr float kMaxNorm2 = 4290774016.0f;   // 65504^2
+constexpr unsigned kRefuseComponent = 1u, kRefuseNorm = 2u, kRefusePending = 0xffffffffu;   // (pending: host side only)
+
+// fp32 centroids -> MFMA operand rows [k_pad][280] fp16: c_hi | c_lo | (-|c|^2/2: a, b, cc, p, p2) | 0
+// stats: {max_c |c_lo|^2, max_c |c_hi + c_lo|^2} as float bits (non-negative: unsigned order = float order) -- what the
+// nominating pass of the assignment bounds its error with -- and stats[3], the refusal word: a component fp16 cannot
+// hold (not finite, or beyond 65504), or for L2 a norm beyond kMaxNorm2.  Zeroed by the caller.
 __global__ void prep_centroids(const float* __restrict__ c, int k, int k_pad, int l2, _Float16* __restrict__ op,
                                unsigned* __restrict__ stats, _Float16* __restrict__ op_hi) {
   const int row = blockIdx.x;
@@ -68,6 +79,7 @@ __global__ void prep_centroids(const float* __restrict__ c, int k, int k_pad, in
   float v = 0.f;
   if (row < k) v = c[(long long)row * kD + t];
   const _Float16 hi = (_Float16)v;
+  if (!(__builtin_fabsf((float)hi) <= 65504.0f)) atomicOr(stats + 3, kRefuseComponent);   // inf or NaN as fp16
   const _Float16 lo = (_Float16)(v - (float)hi);
   _Float16* dst = op + (long long)row * kOpCols;
   dst[t] = hi;
@@ -86,18 +98,26 @@ __global__ void prep_centroids(const float* __restrict__ c, int k, int k_pad, in
     }
     __syncthreads();
   }
-  if (stats && t == 0 && row < k) {
+  if (t == 0 && row < k) {
     atomicMax(stats, __float_as_uint(red_lo[0]));
     atomicMax(stats + 1, __float_as_uint(red[0]));
+    if (l2 && !(red[0] <= kMaxNorm2)) atomicOr(stats + 3, kRefuseNorm);
   }
   if (t < 24) {  // norm step (16) + row padding (8)
     float term = 0.f;
-    if (l2 && row < k) {
-      const float h = -0.5f * red[0];
+    if (l2 && row < k && red[0] <= kMaxNorm2) {
+      float h = -0.5f * red[0];
+      _Float16 p = (_Float16)0.f, p2 = (_Float16)0.f;
+      if (__builtin_fabsf(h) >= kNormScale) {   // (every subtraction below is exact: a float less its own leading bits)
+        p = (_Float16)(h / kNormScale);
+        h -= (float)p * kNormScale;
+        p2 = (_Float16)(h / kNormScale);
+        h -= (float)p2 * kNormScale;
+      }
       const _Float16 a = (_Float16)h;
       const _Float16 b = (_Float16)(h - (float)a);
       const _Float16 cc = (_Float16)(h - (float)a - (float)b);
-      term = t == 0 ? (float)a : t == 1 ? (float)b : t == 2 ? (float)cc : 0.f;
+      term = t == 0 ? (float)a : t == 1 ? (float)b : t == 2 ? (float)cc : t == 3 ? (float)p : t == 4 ? (float)p2 : 0.f;
     }
     dst[2 * kD + t] = (_Float16)term;
     if (dst_hi) dst_hi[kD + t] = (_Float16)term;
@@ -175,14 +195,18 @@ __global__ __launch_bounds__(kAssignThreads) void kmeans_assign(const _Float16* 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, half = lane >> 5;
+  if (stats[3] != 0) return;   // centroids out of the supported range (prep_centroids): the host refuses the call
   if (MODE == MODE_SELECTED) n = (long long)*sel_count;
-  // operand of the norm k-step: lanes of half 0 multiply the three norm terms by 1
+  // operand of the norm k-step: lanes of half 0 multiply the three fine norm terms by 1 and the two coarse ones by 2^15
   f16x8 ones = {0, 0, 0, 0, 0, 0, 0, 0};
   if (half == 0) {
     ones[0] = (_Float16)1.0f;
     ones[1] = (_Float16)1.0f;
     ones[2] = (_Float16)1.0f;
+    ones[3] = (_Float16)kNormScale;
+    ones[4] = (_Float16)kNormScale;
   }
+  if (stats[3] != 0) return;   // centroids out of the supported range (prep_centroids): the host refuses the call
   const int nstages = k_pad / kStageRowsKm;
   auto issue_stage = [&](int s) {
     char* buf = lds + (s & (kRing - 1)) * kStageB;
@@ -261,7 +285,9 @@ __global__ __launch_bounds__(kAssignThreads) void kmeans_assign(const _Float16* 
 #pragma unroll
             for (int e = 0; e < 8; ++e) dot += (float)qf[blk][j][e] * (float)ch[e];
           }
-          if (L2 && half == 0) dot += (float)crow[kD] + (float)crow[kD + 1] + (float)crow[kD + 2];   // -|c|^2 / 2
+          if (L2 && half == 0)   // -|c|^2 / 2: coarse terms (zero below 2^15) + fine terms
+            dot += kNormScale * ((float)crow[kD + 3] + (float)crow[kD + 4]) +
+                   ((float)crow[kD] + (float)crow[kD + 1] + (float)crow[kD + 2]);
         }
         dot += __shfl_xor(dot, 32, 64);
         // (the matrix pipe sums the same products in another order: the margin holds twice that allowance)
@@ -384,6 +410,11 @@ __global__ __launch_bounds__(kAssignThreads) void kmeans_assign(const _Float16* 
   }
 }
 
+// the refusal word of prep_centroids, stored to the handle's pinned (host-coherent) word where the host is polling for it
+__global__ void publish_refusal(const unsigned* __restrict__ stats, unsigned* host_word) {
+  __hip_atomic_store(host_word, stats[3], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 __global__ void histogram_assign(const int* __restrict__ assign, long long n, unsigned* __restrict__ counts) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) atomicAdd(&counts[assign[i]], 1u);
@@ -475,7 +506,9 @@ struct proqa_kmeans {
   unsigned* vals_out = nullptr;
   void* sort_tmp = nullptr;
   size_t sort_tmp_bytes = 0;
-  unsigned* words = nullptr;    // {max |c_lo|^2, max |c|^2 (float bits), undecided points} of the two-pass assignment
+  unsigned* words = nullptr;    // {max |c_lo|^2, max |c|^2 (float bits), undecided points, refusal word} of the assignment
+  unsigned* refused_host = nullptr;   // pinned, host-coherent: where the refusal word of the running call lands
+  unsigned* refused_dev = nullptr;    // the device's address of that word
   int64_t order_n = 0;          // vals_out holds the ids of this many points sorted by assignment (the last update's)
 };
 
@@ -488,6 +521,7 @@ int proqa_kmeans_free(proqa_kmeans* h) {
   void* ptrs[] = {h->op, h->counts, h->begin, h->keys_in, h->keys_out, h->vals_in, h->vals_out, h->sort_tmp, h->words, h->op_hi};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  if (h->refused_host) (void)hipHostFree(h->refused_host);
   delete h;
   return PROQA_OK;
 }
@@ -519,6 +553,8 @@ int proqa_kmeans_create(int d, int64_t n_max, int k, proqa_kmeans** out) {
   alloc((void**)&h->vals_in, (size_t)n_max * sizeof(unsigned));
   alloc((void**)&h->vals_out, (size_t)n_max * sizeof(unsigned));
   alloc((void**)&h->words, 4 * sizeof(unsigned));
+  if (e == hipSuccess) e = hipHostMalloc((void**)&h->refused_host, sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&h->refused_dev, h->refused_host, 0);
   if (e == hipSuccess)
     e = hipcub::DeviceRadixSort::SortPairs(nullptr, h->sort_tmp_bytes, h->keys_in, h->keys_out, h->vals_in, h->vals_out,
                                            (int)n_max, 0, 32, nullptr);
@@ -554,6 +590,13 @@ int proqa_kmeans_assign_hinted_device(proqa_kmeans* h, const void* x_f16_dev, in
   hipLaunchKernelGGL(prep_centroids, dim3(h->k_pad), dim3(128), 0, st, centroids_dev, h->k, h->k_pad, metric_l2 ? 1 : 0,
                      h->op, h->words, two_pass ? h->op_hi : nullptr);
   PROQA_LAUNCH_CHECK();
+  // What the operand format cannot carry is refused, not computed.  The refusal word travels to pinned host memory right
+  // behind the prep kernel and the assignment kernels are queued behind it at once (they leave, writing nothing, when it
+  // is set): the device never idles, and the host only waits for the word to land (below) -- not for the assignment.
+  *(volatile unsigned*)h->refused_host = kRefusePending;
+  // (a one-thread kernel, not a copy: a copy engine between the prep kernel and the assignment cost 0.3 ms per call)
+  hipLaunchKernelGGL(publish_refusal, dim3(1), dim3(1), 0, st, (const unsigned*)h->words, h->refused_dev);
+  PROQA_LAUNCH_CHECK();
   const unsigned grid = (unsigned)ceil_div<int64_t>(n, kPointsPerBlock);
   const _Float16* x = (const _Float16*)x_f16_dev;
 #define PROQA_KM_LAUNCH(MODE, GRID)                                                                                          \
@@ -587,6 +630,22 @@ int proqa_kmeans_assign_hinted_device(proqa_kmeans* h, const void* x_f16_dev, in
     PROQA_KM_LAUNCH(MODE_SELECTED, std::min<unsigned>(grid, 4u * (unsigned)device_cu_count()));
   }
 #undef PROQA_KM_LAUNCH
+  // the word lands as soon as the prep kernel is through (whatever ran on the stream before it included); should the stream
+  // drain first, publish_refusal has run and its store is visible
+  unsigned refused;
+  while ((refused = __atomic_load_n(h->refused_host, __ATOMIC_ACQUIRE)) == kRefusePending) {
+    const hipError_t q = hipStreamQuery(st);
+    if (q == hipErrorNotReady) continue;
+    PROQA_HIP(q);
+    refused = __atomic_load_n(h->refused_host, __ATOMIC_ACQUIRE);
+    break;
+  }
+  if (refused == kRefusePending) return fail(PROQA_EHIP, "kmeans_assign: the refusal word never arrived");
+  if (refused & kRefuseComponent)
+    return fail(PROQA_EINVAL, "kmeans_assign: a centroid component is not a finite fp16 number (|value| must be at most 65504)");
+  if (refused & kRefuseNorm)
+    return fail(PROQA_EINVAL, "kmeans_assign: L2 metric: a centroid's norm |c| exceeds the supported limit of 65504 (its -|c|^2/2 "
+                              "does not fit the operand's norm step)");
   return PROQA_OK;
 }
 

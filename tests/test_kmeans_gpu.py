@@ -29,9 +29,10 @@ def test_assign_matches_oracle(gpu_device, n, k, l2):
     D, I = km.assign(torch.from_numpy(x).to(gpu_device))
     Do, Io = kmeans_oracle.assign(x, cent, l2)
     I = I.cpu().numpy()
-    # fp32-grade dot products: assignments may differ only where two centroids tie to round-off
-    mism = np.nonzero(I != Io)[0]
-    assert len(mism) <= max(1, n // 2000)
+    # fp32-grade dot products: a label may differ from the oracle's only where its float64 score is within the tolerance of
+    # the best one (the rule of tests/test_kmeans_assign_gpu.py)
+    from test_kmeans_assign_gpu import Reference, check_against_float64
+    check_against_float64(Reference(x, cent, l2, False), I, D.cpu().numpy())
     np.testing.assert_allclose(D.cpu().numpy(), Do, rtol=2e-4, atol=2e-3)
 
 
@@ -119,8 +120,16 @@ def test_clusering_never_rounds_float32_silently(gpu_device):
     with pytest.raises(ValueError, match="not representable in fp16"):
         clusering(bad, niter=2, verbose=False, ncentroids=8, max_points_per_centroid=1000)
     D, I = clusering(bad, niter=2, verbose=False, ncentroids=8, max_points_per_centroid=1000, allow_fp16_rounding=True)
-    Dr, Ir = clusering(bad.astype(np.float16), niter=2, verbose=False, ncentroids=8, max_points_per_centroid=1000)
-    np.testing.assert_array_equal(I, Ir)
+    # against the oracle's clustering of the rounded points, not against a second run of the same kernel: the float64 score
+    # of every label under the oracle's final centroids is within the tolerance of the best one (the rule of
+    # tests/test_kmeans_assign_gpu.py; |c| is in the thousands here, where -|c|^2/2 needs the coarse norm terms)
+    from test_kmeans_assign_gpu import Reference, check_against_float64
+    rounded = bad.astype(np.float16)
+    Do, Io, cent_o = kmeans_oracle.clustering(rounded, 2, 8, 1000)
+    ref = Reference(rounded, cent_o, True, False)
+    assert ref.near_tie_share() <= 0.01
+    assert len(np.unique(Io)) == 8
+    check_against_float64(ref, I[:, 0], D[:, 0])
 
 
 def test_empty_cluster_split_like_faiss(gpu_device):
