@@ -440,7 +440,14 @@ int proqa_attention_cls_varlen_f16(const void* qkv_packed, const int32_t* cu_seq
  * (qkv_bias [3*hidden] fp16 or NULL): the query bias is added to the query fragments, the key bias is
  * dropped (it shifts all scores of a query by the same amount: softmax-invariant), the value bias is
  * added to the output (probabilities sum to 1).  Exactly one of seq_lens_dev (padded layout) and
- * cu_seqlens_dev (packed layout) is non-NULL; cls_only selects the [batch, hidden] row-0 output. */
+ * cu_seqlens_dev (packed layout) is non-NULL; cls_only selects the [batch, hidden] row-0 output.
+ * That is the full kernel (cls_only = 0).  The cls_only kernel adds all three biases to the rows it reads: it works on
+ * q + b_q, k + b_k and v + b_v, each rounded to fp16 as a half-precision dense layer would have stored them.  Same
+ * mathematics, other roundings: a large key bias costs its keys the bits below the bias' own fp16 spacing.
+ * Lengths are clamped to [1, seq_len].
+ * Padded layout: the K and V of the rows >= len are never read.  The outputs of the valid queries do not depend on what
+ * those rows hold, bit for bit, NaN and Inf included.  The output rows >= len are written (their queries are the padding
+ * rows' own Q) and hold values nothing should read. */
 int proqa_attention_ex_f16(const void* qkv, const void* qkv_bias, const int32_t* seq_lens_dev,
                            const int32_t* cu_seqlens_dev, int batch, int seq_len, int n_heads, int cls_only,
                            void* out, void* stream);
@@ -459,6 +466,14 @@ int proqa_bias_residual_layernorm_f16(const void* x, const void* bias, const voi
 int proqa_pool_project_f16(const void* h, int batch, int seq_len, int hidden, const void* w_pool,
                            const void* b_pool, const void* w_proj, const void* b_proj,
                            void* pooled_ws, void* out, int out_dtype, void* stream);
+
+/* The dense layer for a few token rows on its own (what proqa_encoder_dense and the encoder's FFN run for <= 256 rows):
+ *   y[rows, n_feat] = act(x[rows, k] . w[n_feat, k]^T + bias[n_feat]),  act 0: none, 1: erf-GELU (BertIntermediate)
+ * fp16 row-major device pointers, fp32 accumulate; bias [n_feat] fp16 or NULL.  Any rows >= 0 (the grid grows with it);
+ * n_feat a multiple of 32 and k a multiple of 128, anything else is PROQA_EINVAL before the device is touched.
+ * Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive). */
+int proqa_small_dense_f16(const void* x, int rows, const void* w, const void* bias, int n_feat, int k, int act, void* y,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Backward operators of the tower and of the in-batch objective: what `loss.backward()` of retriever pre-training

@@ -175,6 +175,7 @@ SIGNATURES = {
                                                   c_float, c_int64, c_int, c_void_p, c_void_p]),
     "proqa_pool_project_f16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "proqa_small_dense_f16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "proqa_backward_workspace_bytes": (c_size_t, [c_int]),
     "proqa_attention_backward_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "proqa_colsum_f16": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -123,7 +123,9 @@ __device__ __forceinline__ void attention_fwd_body(const _Float16* __restrict__ 
       const int row = kc * kLongChunk + (i >> 3), c = i & 7;
       kreg[it] = zero8;
       vreg[it] = zero8;
-      if (row < rows_avail) {
+      // valid keys only: a masked key of the last tile has p = 0 exactly, but its V row still enters the MFMA, and 0 x NaN
+      // (or 0 x Inf) from a padding row of the padded layout would reach every valid query of the tile
+      if (row < len) {
         const _Float16* src = base + row * row_stride + c * 8;
         kreg[it] = *(const f16x8*)(src + hidden);
         vreg[it] = *(const f16x8*)(src + 2 * hidden);
@@ -337,6 +339,7 @@ __global__ __launch_bounds__(256) void attention_cls_fwd(const _Float16* __restr
     const int key = key0 + g;
     float acc = 0.f;
     if (key < len) {
+      // (k + b_k rounded to fp16, as a half-precision dense layer would have stored it; attention_fwd drops b_k instead)
       const f16x8 k8 = add_bias8(*(const f16x8*)(base + key * row_stride + hidden + c * 8),
                                  qkv_bias ? qkv_bias + hidden + head * kHeadDim + c * 8 : nullptr);
 #pragma unroll

@@ -343,8 +343,8 @@ int launch_cu_seqlens(const int32_t* seq_lens_dev, int batch, int32_t* cu_out, v
 // y[rows, n_feat] = act(x[rows, k] . w[n_feat, k]^T + bias) for a few rows; n_feat % 32 == 0, k % 128 == 0
 int launch_small_dense(const void* x, int rows, const void* w, const void* bias, int n_feat, int k_dim, int act, void* y,
                        void* stream) {
-  if (rows == 0) return PROQA_OK;
   if (n_feat % 32 || k_dim % 128 || k_dim <= 0) return fail(PROQA_EINVAL, "small_dense: n_feat=%d k=%d", n_feat, k_dim);
+  if (rows == 0) return PROQA_OK;
   const dim3 g((unsigned)(n_feat / 32), (unsigned)((rows + 31) / 32));
   if (act == 1)
     hipLaunchKernelGGL(small_dense_mfma<1>, g, dim3(256), 0, as_stream(stream), (const _Float16*)x, rows, (const _Float16*)w,
@@ -523,6 +523,14 @@ int proqa_bias_gelu_f16(void* x, const void* bias, int64_t rows, int cols, void*
                      n_chunks, cols / 8);
   PROQA_LAUNCH_CHECK();
   return PROQA_OK;
+}
+
+int proqa_small_dense_f16(const void* x, int rows, const void* w, const void* bias, int n_feat, int k, int act, void* y,
+                          void* stream) {
+  if (!x || !w || !y) return fail(PROQA_EINVAL, "small_dense: NULL argument");
+  if (rows < 0 || n_feat <= 0 || (act != 0 && act != 1))
+    return fail(PROQA_EINVAL, "small_dense: rows=%d n_feat=%d act=%d", rows, n_feat, act);
+  return launch_small_dense(x, rows, w, bias, n_feat, k, act, y, stream);
 }
 
 int proqa_pool_project_f16(const void* h, int batch, int seq_len, int hidden, const void* w_pool,
