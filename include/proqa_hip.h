@@ -796,6 +796,59 @@ int proqa_cast_half_tensors(const proqa_adamw_tensor* table_dev, void* const* ha
                             const proqa_adamw_chunk* chunks_dev, int64_t n_chunks, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Trainer-state snapshot: all fp32 tensors of a training run (masters, exp_avg, exp_avg_sq, the optimizer's device
+ * scalars viewed as fp32) copied into one flat device buffer and digested, in TWO launches whatever n_tensors is.  Added
+ * WITHOUT a bump of PROQA_ABI_VERSION (purely additive).  Rules of the optimizer block: caller-owned buffers, no
+ * allocation, no host synchronisation, no atomics, everything on `stream`; two calls on the same memory execute the same
+ * instruction stream.
+ *
+ * Layout.  Tensor t is numel[t] contiguous fp32 words at src_dev_ptrs[t] (a DEVICE array of n_tensors device pointers,
+ * so that a table survives tensors that move); the words are copied AS BITS (NaN payloads, -0.0 and denormals keep their
+ * bits) to dst_flat_dev + dst_offsets[t].  dst_flat_dev and every dst_offsets[t] (bytes) are multiples of
+ * PROQA_STATE_DST_ALIGN; the bytes between one tensor's end and the next one's start are not written.
+ * dst_flat_dev == NULL: digest only (dst_offsets may be NULL).  numel and dst_offsets are HOST arrays.  0 <= numel[t] <=
+ * 2^31 (a larger tensor is refused with PROQA_EINVAL); numel[t] == 0 and n_tensors == 0 are valid.
+ *
+ * Digest.  digests_dev[t] (DEVICE, n_tensors x uint64) = sum over i in [0, numel[t]) of mix(bits_i, i) mod 2^64 with
+ *     mix(bits, i) = ((uint64)(bits ^ PROQA_STATE_MIX_XOR) * (2 i + 1)) mod 2^64,
+ * bits_i the 32-bit pattern of element i, i its 64-bit index inside the tensor; an empty tensor has digest 0.  For
+ * i < 2^31 the weight 2 i + 1 is an odd 32-bit number that no other index has, hence: changing one element changes the
+ * digest (a non-zero difference below 2^32 times a weight below 2^32 is non-zero mod 2^64), and so does swapping two
+ * unequal elements ((a - b) (w_i - w_j) != 0, below 2^64 in magnitude).  The xor makes a zero-filled tensor's digest
+ * depend on its length.  One workgroup owns one chunk of PROQA_STATE_CHUNK elements and writes one uint64 partial; one
+ * wave per tensor then adds the tensor's partials.
+ *
+ * Alignment.  A source is only guaranteed 4-byte aligned (a parameter may be a row slice of a flat buffer): per chunk the
+ * elements before the first 16-byte boundary and the up to three after the last are loaded as single words, everything
+ * between with 16-byte loads.  A 16-byte aligned source is stored with 16-byte stores, a shifted one with 4-byte stores.
+ *
+ * Workspace.  ws (DEVICE, 16-byte aligned, proqa_state_snapshot_workspace_bytes) = [plan | partials].  The plan
+ * (proqa_state_snapshot_plan_bytes: n_tensors x proqa_state_tensor, then one proqa_state_chunk per chunk in tensor order)
+ * depends on numel and dst_offsets only: proqa_state_snapshot_plan fills a HOST image that the caller uploads to the start
+ * of ws once; the calls read it and write the partials behind it.  The three size / plan functions are pure host functions
+ * (no GPU needed); the size functions return 0 for sizes that proqa_state_snapshot refuses (proqa_last_error says why).
+ * ---------------------------------------------------------------------------------- */
+#define PROQA_STATE_CHUNK 16384
+#define PROQA_STATE_DST_ALIGN 256
+#define PROQA_STATE_MIX_XOR 0x9E3779B9u
+typedef struct proqa_state_tensor {
+  int64_t numel;
+  int64_t dst_offset;    /* bytes into dst_flat_dev */
+  int64_t first_chunk;   /* index of the tensor's first chunk (and partial) */
+  int64_t n_chunks;      /* ceil(numel / PROQA_STATE_CHUNK) */
+} proqa_state_tensor;
+typedef struct proqa_state_chunk {
+  int32_t tensor;
+  int32_t index;         /* elements [index * PROQA_STATE_CHUNK, ...) of that tensor */
+} proqa_state_chunk;
+size_t proqa_state_snapshot_plan_bytes(const int64_t* numel, int n_tensors);
+size_t proqa_state_snapshot_workspace_bytes(const int64_t* numel, int n_tensors);
+int proqa_state_snapshot_plan(const int64_t* numel, const int64_t* dst_offsets, int n_tensors, void* plan_host,
+                              size_t plan_bytes);
+int proqa_state_snapshot(const void* const* src_dev_ptrs, const int64_t* numel, int n_tensors, void* dst_flat_dev,
+                         const int64_t* dst_offsets, uint64_t* digests_dev, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * k-means over passage embeddings.  Replaces faiss.Clustering.train + index.search(data, 1) of
  * retrieval/group_paras.py:20-53 (IndexFlatL2, IndexFlatIP when --spherical).  The Lloyd loop
  * (sampling, initialisation, empty-cluster splitting: faiss Clustering.cpp) runs on the host

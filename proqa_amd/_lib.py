@@ -87,6 +87,9 @@ class AdamwHyper(ctypes.Structure):
 ADAMW_CHUNK = 16384
 ADAMW_STATE_BYTES = 64
 ADAMW_SCALE_NONE, ADAMW_SCALE_FIXED, ADAMW_SCALE_DYNAMIC = 0, 1, 2
+STATE_CHUNK = 16384
+STATE_DST_ALIGN = 256
+STATE_MIX_XOR = 0x9E3779B9
 
 ENC_CLS_ONLY_LAST = 1
 ENC_PACKED = 2
@@ -239,6 +242,10 @@ SIGNATURES = {
     "proqa_adamw_step_half": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, ctypes.POINTER(AdamwHyper), c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
     "proqa_cast_half_tensors": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "proqa_state_snapshot_plan_bytes": (c_size_t, [c_void_p, c_int]),
+    "proqa_state_snapshot_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "proqa_state_snapshot_plan": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    "proqa_state_snapshot": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "proqa_kmeans_create": (c_int, [c_int, c_int64, c_int, ctypes.POINTER(c_void_p)]),
     "proqa_kmeans_free": (c_int, [c_void_p]),
     "proqa_kmeans_assign_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p,

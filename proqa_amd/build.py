@@ -33,6 +33,7 @@ SOURCES = [
     "train_kernels.hip",
     "linear_kernels.hip",
     "optim_kernels.hip",
+    "state_kernels.hip",
     "kmeans_kernels.hip",
     "ivf_index.cpp",
     "ivf_kernels.hip",

@@ -61,15 +61,44 @@ EXTRA_FLAGS = (
     ("--deterministic", "flag", False),
 )
 
+# the training commands' checkpoint / resume flags (pretrain_retriever.py and train_reader.py; proqa_amd/checkpoint.py)
+STATE_FLAGS = (
+    # write trainer_state_last.pt (masters, AdamW moments, counters, sampler and RNG state) every --save_checkpoints_steps
+    ("--save-state", "flag", False),
+    # stop after this many updates (counted from the run's first, across resumes), state written; implies --save-state
+    ("--stop-after-updates", int, 0),
+    # continue from a state file, or from a run directory that holds trainer_state_last.pt
+    ("--resume", str, ""),
+    # every N updates a 64-bit digest of the masters and both moments goes into the stats and the log (0 = never)
+    ("--digest-every", int, 0),
+)
 
-def build_parser():
-    parser = argparse.ArgumentParser()
-    for flag, kind, default in _REFERENCE_FLAGS + EXTRA_FLAGS:
+
+def add_flags(parser, flags):
+    for flag, kind, default in flags:
         if kind == "flag":
             parser.add_argument(flag, action="store_true", default=default)
         else:
             parser.add_argument(flag, type=kind, default=default)
     return parser
+
+
+def check_state_flags(args, command):
+    """the refusals of the checkpoint flags; --stop-after-updates implies --save-state"""
+    if args.resume and args.init_checkpoint:
+        raise SystemExit(f"{command}: --resume together with --init_checkpoint is refused: the state file carries the weights")
+    if args.stop_after_updates < 0:
+        raise SystemExit(f"{command}: --stop-after-updates must not be negative")
+    if args.digest_every < 0:
+        raise SystemExit(f"{command}: --digest-every must not be negative")
+    if args.stop_after_updates > 0:
+        args.save_state = True
+    return args
+
+
+def build_parser():
+    parser = argparse.ArgumentParser()
+    return add_flags(parser, _REFERENCE_FLAGS + EXTRA_FLAGS + STATE_FLAGS)
 
 
 def get_args(argv=None):

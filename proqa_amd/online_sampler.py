@@ -148,6 +148,8 @@ class OnlineSampler:
         self.index = index
         with open(raw_data) as f:
             self.qa_data = [json.loads(l) for l in f.readlines()]
+        self._file_data = list(self.qa_data)          # the file's order; qa_data is _file_data in the order of _order
+        self._order = list(range(len(self.qa_data)))
         if isinstance(index2paraid, str):
             with open(index2paraid) as f:
                 index2paraid = json.load(f)
@@ -187,7 +189,22 @@ class OnlineSampler:
         self.questions_seen = 0
 
     def shuffle(self):
-        random.shuffle(self.qa_data)
+        # the same draws from `random` and the same arrangement as random.shuffle(self.qa_data): shuffle() swaps by
+        # position, whatever the list holds
+        random.shuffle(self._order)
+        self.qa_data = [self._file_data[i] for i in self._order]
+
+    def permutation(self):
+        """the current order of the questions, as indices into the file's order (what a trainer state saves)"""
+        return list(self._order)
+
+    def set_permutation(self, order):
+        """put a saved permutation() back; later shuffle() calls continue from it"""
+        order = [int(i) for i in order]
+        if sorted(order) != list(range(len(self._file_data))):
+            raise ValueError("OnlineSampler.set_permutation: not a permutation of the file's questions")
+        self._order = order
+        self.qa_data = [self._file_data[i] for i in order]
 
     def __len__(self):
         return len(self.qa_data)
@@ -318,12 +335,15 @@ class OnlineSampler:
         n_live, n_gold = record[0], record[1]
         return q_ids, rows[:n_live], labels[:n_live], n_live, n_gold, [r for r in record[2:] if r >= 0]
 
-    def load(self, retriever, k=5):
+    def load(self, retriever, k=5, start=0):
         """Yields, per question, {} when neither its top 5000 nor its top k passages carry the answer, else the
-        reference's batch with the tensors of net_input on the device."""
+        reference's batch with the tensors of net_input on the device.  start: the first `start` questions of the current
+        order are left out (a resumed epoch)."""
         if not 0 < k <= MAX_HEAD:
             raise ValueError(f"OnlineSampler.load: k must be in [1, {MAX_HEAD}], got {k}")
-        for qa in self.qa_data:
+        if not 0 <= start <= len(self.qa_data):
+            raise ValueError(f"OnlineSampler.load: start must be in [0, {len(self.qa_data)}], got {start}")
+        for qa in self.qa_data[start:] if start else self.qa_data:
             self.questions_seen += 1
             q_ids, para_embed, labels, n_live, n_gold, top_rows = self.retrieve(retriever, qa["question"], k)
             t0 = time.perf_counter()

@@ -13,6 +13,12 @@ the host never reads a loss inside the loop: the per-micro-batch losses stay on 
 and checkpoint time and at the end; the initial BERT weights come from the local --bert_model_name directory only (nothing
 is fetched); --local_rank, --no_cuda and a ';' list in --init_checkpoint are refused.  `train_retriever.py --do_train` keeps
 its refusal; `--do_predict` alone belongs to that command.
+
+Beyond the reference (proqa_amd/checkpoint.py): --save-state writes trainer_state_last.pt (masters,
+AdamW moments, counters, sampler position, RNG and dropout state) behind the training stream, --stop-after-updates K stops
+after the K-th update with the state written, --resume PATH continues from it (with --deterministic to the bits of the
+uninterrupted run), --digest-every N records 64-bit digests of the masters and both moments.  Without these flags the
+command writes the files, log lines and stats keys it always wrote.
 """
 import json
 import logging
@@ -63,7 +69,8 @@ def check_args(args):
     if int(args.train_batch_size / args.accumulate_gradients) < 1:
         raise ValueError(f"--train_batch_size {args.train_batch_size} / --accumulate_gradients {args.accumulate_gradients} "
                          "leaves no example per batch")
-    return args
+    from .config import check_state_flags
+    return check_state_flags(args, "pretrain_retriever.py")
 
 
 def batch_slices(order, batch_size):
@@ -200,6 +207,7 @@ def main(argv=None):
     args = check_args(get_args(argv))
     import numpy as np
     import torch
+    from . import checkpoint
     from transformers import BertTokenizer
     from .datasets import ClusterDataset, ClusterSampler, ReDataset, ReSampler, ReTextView, ReTokenizeCollate
     from .get_embed import usable_cpus
@@ -221,10 +229,12 @@ def main(argv=None):
     logger.setLevel(logging.INFO)
     logger.propagate = False
     tb = None
+    ckpt = None
     try:
         logger.info(args)
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: retriever training has no CPU fallback")
+        flag_batch_size = args.train_batch_size
         args.train_batch_size = int(args.train_batch_size / args.accumulate_gradients)
         random.seed(args.seed)
         np.random.seed(args.seed)
@@ -235,6 +245,13 @@ def main(argv=None):
         if args.max_seq_length > cfg.max_position_embeddings:
             raise ValueError("Cannot use sequence length %d because the BERT model was only trained up to sequence length %d"
                              % (args.max_seq_length, cfg.max_position_embeddings))
+        resume = None
+        fp = checkpoint.fingerprint("pretrain_retriever.py", args, train_batch_size=flag_batch_size,
+                                    hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention)
+        if args.resume:
+            # the flags first: a run of other settings is refused before the data and the model are built
+            resume = checkpoint.read_state(checkpoint.resolve_state_path(args.resume))
+            checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp, fields=tuple(fp))
         tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
 
         # the data first: ClusterDataset reads its folder with a process pool, and nothing forks once the GPU is in use
@@ -274,11 +291,12 @@ def main(argv=None):
         if args.deterministic:
             logger.info("--deterministic: the word-embedding gradient is summed in a fixed order (no atomics); a run is a "
                         "function of the data, the seed and the checkpoint, bit for bit")
-        if args.init_checkpoint != "":
-            state = torch.load(args.init_checkpoint, map_location="cpu")
-        else:
-            state = initial_state_dict(cfg, load_bert_weights(args.bert_model_name), args.seed)
-        model.load_state_dict(state)
+        if resume is None:
+            if args.init_checkpoint != "":
+                state = torch.load(args.init_checkpoint, map_location="cpu")
+            else:
+                state = initial_state_dict(cfg, load_bert_weights(args.bert_model_name), args.seed)
+            model.load_state_dict(state)
         for n, p in model.named_parameters():
             if any(s in n for s in FROZEN_PARAMETERS):
                 p.requires_grad_(False)
@@ -299,10 +317,57 @@ def main(argv=None):
         evals = []
         G = args.gradient_accumulation_steps
         model.train()
+
+        # checkpoint / resume (proqa_amd/checkpoint.py): nothing of it exists without the four flags
+        ckpt, digests, state_path = None, None, os.path.join(args.output_dir, checkpoint.STATE_FILE)
+        start_epoch, start_position, stopped_early = 0, 0, False
+        if args.save_state or args.digest_every > 0 or resume is not None:
+            fp = checkpoint.fingerprint("pretrain_retriever.py", args, train_batch_size=flag_batch_size,
+                                        hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention,
+                                        n_train=len(train_dataset), order=[i for b in train_batches for i in b], model=model)
+            if resume is not None:
+                checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp)
+            ckpt = checkpoint.TrainerCheckpoint(model, optimizer)
+            digests = checkpoint.DigestLog(ckpt, args.digest_every)
+        if resume is not None:
+            tr = ckpt.load(resume)
+            checkpoint.set_rng_states(tr["rng"])
+            global_step, batch_step, best_acc = tr["global_step"], tr["batch_step"], tr["best"]
+            wait_step, stop_training, evals = tr["wait_step"], tr["stop_training"], list(tr["evals"])
+            meter.values, meter.steps = list(tr["losses"]), list(tr["loss_steps"])
+            digests.entries = [dict(e) for e in tr["state_digests"]]
+            start_epoch, start_position = tr["epoch"], tr["position"]
+            if stop_training and start_position == 0:
+                start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
+            if 0 < args.stop_after_updates <= global_step:
+                raise SystemExit(f"pretrain_retriever.py: --stop-after-updates {args.stop_after_updates}: the state file "
+                                 f"already holds {global_step} updates")
+            logger.info("Resumed from %s: update %d, micro-batch %d, epoch %d position %d.  %s", args.resume, global_step,
+                        batch_step, start_epoch, start_position,
+                        "With --deterministic the run continues bit for bit as the uninterrupted one." if args.deterministic
+                        else "Without --deterministic the word-embedding gradient's atomics make two runs differ, resumed "
+                             "or not.")
+        resume = None       # (the file's flat buffer is not kept)
+
+        def save_state(next_epoch, next_position):
+            """the trainer state as of now, written behind the training stream (the losses are read here: allowed)"""
+            meter.flush(tb)
+            digests.flush(logger)
+            if next_position == len(train_batches):
+                next_epoch, next_position = next_epoch + 1, 0
+            ckpt.snapshot(state_path, dict(checkpoint.trainer_state(
+                fingerprint=fp, global_step=global_step, batch_step=batch_step, epoch=next_epoch, position=next_position,
+                epoch_started=True, best=best_acc, wait_step=wait_step, stop_training=stop_training,
+                dropout=checkpoint.dropout_states(model), losses=meter.values, loss_steps=meter.steps, evals=evals,
+                param_groups=[{"lr": g["lr"], "weight_decay": g["weight_decay"]} for g in optimizer.param_groups],
+                state_digests=digests.entries), rng=checkpoint.rng_states()))
+
         logger.info("Start training....")
         t_start = time.perf_counter()
-        for epoch in range(int(args.num_train_epochs)):
-            for indices in train_batches:
+        for epoch in range(start_epoch, int(args.num_train_epochs)):
+            first = start_position if epoch == start_epoch else 0
+            for position in range(first, len(train_batches)):
+                indices = train_batches[position]
                 batch_step += 1
                 batch = move_to_cuda(tensors(train_texts, indices), device)
                 outputs = model(batch)
@@ -316,6 +381,9 @@ def main(argv=None):
                     optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
                     model.zero_grad()
                     global_step += 1
+                    if digests is not None:
+                        digests.after_update(global_step)
+                    wrote_last = False
 
                     if global_step % args.save_checkpoints_steps == 0:
                         meter.flush(tb)
@@ -340,9 +408,20 @@ def main(argv=None):
                             wait_step += 1
                             if wait_step == args.wait_step:
                                 stop_training = True
-            if stop_training:
+                        wrote_last = True
+
+                    if args.save_state:
+                        stopped_early = global_step == args.stop_after_updates
+                        if global_step % args.save_checkpoints_steps == 0 or wrote_last or stopped_early:
+                            save_state(epoch, position + 1)
+                        if stopped_early:
+                            break
+            if stop_training or stopped_early:
                 break
         meter.flush(tb)
+        if ckpt is not None:
+            digests.flush(logger)
+            ckpt.close()
         fused = optimizer.state_dict()["fused"]
         seconds = time.perf_counter() - t_start
         logger.info("Training finished!")
@@ -352,11 +431,20 @@ def main(argv=None):
         stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
                      skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"], seconds=seconds,
                      best_acc=best_acc, output_dir=args.output_dir, deterministic=bool(args.deterministic))
+        if args.stop_after_updates > 0:
+            stats["stopped_early"] = stopped_early
+        if args.digest_every > 0:
+            stats["state_digests"] = digests.entries
         if os.environ.get("PROQA_STATS_JSON"):
             with open(os.environ["PROQA_STATS_JSON"], "w") as f:
                 json.dump(stats, f)
         return stats
     finally:
+        if ckpt is not None:
+            try:
+                ckpt.close()
+            except Exception:
+                logger.exception("the last trainer state was not written")
         if tb is not None:
             tb.close()
         for h in handlers:

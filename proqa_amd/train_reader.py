@@ -16,6 +16,10 @@ the loop (they are read at an evaluation, at the end of an epoch and at the end)
 searches (the model is back in train() after it, as after the reference's predict()); the initial weights come from --init_checkpoint, or from the local
 --bert_model_name directory plus --retriever-path (nothing is fetched); --do_predict alone, --local_rank, --no_cuda,
 --use-spanbert, --separate and --add-select are refused.  `train_retrieve_qa.py` keeps its refusal of the training flags.
+
+Beyond the reference (proqa_amd/checkpoint.py): --save-state, --stop-after-updates, --resume and
+--digest-every as in pretrain_retriever.py; the state also holds the sampler's permutation, the failed and update steps
+and the RNG states, so a run resumed inside an epoch visits the questions the uninterrupted run visits.
 """
 import argparse
 import json
@@ -108,7 +112,8 @@ def build_parser():
     p.add_argument("--candidates", default="", type=str)
     p.add_argument("--deterministic", action="store_true", default=False,
                    help="sum the word-embedding gradients in a fixed order: a run reproduces bit for bit")
-    return p
+    from .config import STATE_FLAGS, add_flags
+    return add_flags(p, STATE_FLAGS)       # --save-state, --stop-after-updates, --resume, --digest-every
 
 
 def get_args(argv=None):
@@ -152,7 +157,8 @@ def check_args(args):
                          f"the passages per question must be in [1, {MAX_HEAD}]")
     if args.matched_para_path == "":
         raise ValueError("--matched-para-path is required: the sampler's labels come from it")
-    return args
+    from .config import check_state_flags
+    return check_state_flags(args, "train_reader.py")
 
 
 def update_schedule(n_batches, gradient_accumulation_steps, failed=()):
@@ -185,7 +191,7 @@ def main(argv=None):
     import numpy as np
     import torch
     from transformers import BertTokenizer
-    from . import predict_qa
+    from . import checkpoint, predict_qa
     from .index import IndexFlatIP
     from .online_sampler import OnlineSampler
     from .optim import FusedAdamW
@@ -206,12 +212,14 @@ def main(argv=None):
     logger.propagate = False
     tb = None
     para_db = None
+    ckpt = None
     try:
         logger.info(args)
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: reader training has no CPU fallback")
         device = torch.device("cuda", torch.cuda.current_device())
         logger.info("device %s n_gpu %d distributed training %r", device, 1, False)
+        flag_batch_size = args.train_batch_size
         args.train_batch_size = int(args.train_batch_size / args.accumulate_gradients)     # passages per question
         random.seed(args.seed)
         np.random.seed(args.seed)
@@ -219,6 +227,15 @@ def main(argv=None):
         torch.cuda.manual_seed_all(args.seed)
 
         cfg, p_hidden, p_attention = load_model_config(args.bert_model_name)
+        resume = None
+        fp_extra = {"qa_drop": float(args.qa_drop), "shared_norm": bool(args.shared_norm), "drop_early": bool(args.drop_early),
+                    "fix_para_encoder": bool(args.fix_para_encoder)}
+        fp = checkpoint.fingerprint("train_reader.py", args, train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden,
+                                    attention_probs_dropout_prob=p_attention, extra=fp_extra)
+        if args.resume:
+            # the flags first: a run of other settings is refused before the data and the model are built
+            resume = checkpoint.read_state(checkpoint.resolve_state_path(args.resume))
+            checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp, fields=tuple(fp))
         tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
         logger.info("Loading para db and pretrained index ...")
         para_db = DocDB(args.db_path)
@@ -232,7 +249,12 @@ def main(argv=None):
             index2paraid = json.load(f)
         eval_data = predict_qa.load_qa(args.raw_eval_data)
 
-        if args.init_checkpoint != "":
+        if resume is not None:
+            retriever_path, args.retriever_path = args.retriever_path, ""       # the state file carries every master
+            model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
+                                              attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
+            args.retriever_path = retriever_path
+        elif args.init_checkpoint != "":
             retriever_path, args.retriever_path = args.retriever_path, ""       # the checkpoint carries the retriever
             model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
                                               attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
@@ -290,12 +312,69 @@ def main(argv=None):
         train_dataloader = OnlineSampler(args.raw_train_data, tokenizer, args.max_query_length, args.max_seq_length, para_db,
                                          index, index2paraid=index2paraid, matched_para_path=args.matched_para_path,
                                          regex=args.regex, device=device)
+
+        # checkpoint / resume (proqa_amd/checkpoint.py): nothing of it exists without the four flags
+        digests, state_path = None, os.path.join(args.output_dir, checkpoint.STATE_FILE)
+        start_epoch, start_position, epoch_started, resumed_failed = 0, 0, False, 0
+        stopped_early, pending_grad = False, False
+        if args.save_state or args.digest_every > 0 or resume is not None:
+            import zlib
+            fp = checkpoint.fingerprint("train_reader.py", args, train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden,
+                                        attention_probs_dropout_prob=p_attention, extra=fp_extra, n_train=len(train_dataloader),
+                                        order=[zlib.crc32(qa["question"].encode("utf-8")) for qa in train_dataloader.qa_data],
+                                        model=model)
+            if resume is not None:
+                checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp)
+            ckpt = checkpoint.TrainerCheckpoint(model, optimizer)
+            digests = checkpoint.DigestLog(ckpt, args.digest_every)
+        if resume is not None:
+            tr = ckpt.load(resume)
+            saved = tr["reader"]
+            train_dataloader.set_permutation(saved["permutation"])
+            checkpoint.set_rng_states(tr["rng"])       # OnlineSampler.shuffle() draws from `random` every epoch
+            global_step, batch_step, best_em = tr["global_step"], tr["batch_step"], tr["best"]
+            wait_step, stop_training, evals = tr["wait_step"], tr["stop_training"], list(tr["evals"])
+            meter.values, meter.steps = list(tr["losses"]), list(tr["loss_steps"])
+            digests.entries = [dict(e) for e in tr["state_digests"]]
+            failed_steps, update_steps = list(saved["failed_steps"]), list(saved["update_steps"])
+            failed_per_epoch, resumed_failed = list(saved["failed_per_epoch"]), saved["failed_retrieval"]
+            start_epoch, start_position, epoch_started = tr["epoch"], tr["position"], tr["epoch_started"]
+            if stop_training and not epoch_started:
+                start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
+            if 0 < args.stop_after_updates <= global_step:
+                raise SystemExit(f"train_reader.py: --stop-after-updates {args.stop_after_updates}: the state file already "
+                                 f"holds {global_step} updates")
+            logger.info("Resumed from %s: update %d, question %d, epoch %d position %d.  %s", args.resume, global_step,
+                        batch_step, start_epoch, start_position,
+                        "With --deterministic the run continues bit for bit as the uninterrupted one." if args.deterministic
+                        else "Without --deterministic the word-embedding gradient's atomics make two runs differ, resumed "
+                             "or not.")
+        resume = None       # (the file's flat buffer is not kept)
+
+        def save_state(next_epoch, next_position, started, failed_so_far):
+            """the trainer state as of now, written behind the training stream (the losses are read here: allowed)"""
+            meter.flush(tb)
+            digests.flush(logger)
+            reader_state = {"failed_steps": list(failed_steps), "update_steps": list(update_steps),
+                            "failed_per_epoch": list(failed_per_epoch), "failed_retrieval": int(failed_so_far),
+                            "permutation": train_dataloader.permutation()}
+            ckpt.snapshot(state_path, dict(checkpoint.trainer_state(
+                fingerprint=fp, global_step=global_step, batch_step=batch_step, epoch=next_epoch, position=next_position,
+                epoch_started=started, best=best_em, wait_step=wait_step, stop_training=stop_training,
+                dropout=checkpoint.dropout_states(model), losses=meter.values, loss_steps=meter.steps, evals=evals,
+                param_groups=[{"lr": g["lr"], "weight_decay": g["weight_decay"]} for g in optimizer.param_groups],
+                state_digests=digests.entries, reader=reader_state), rng=checkpoint.rng_states()))
+
         t_start = time.perf_counter()
-        for epoch in range(int(args.num_train_epochs)):
-            train_dataloader.shuffle()
-            failed_retrieval = 0
-            for batch in train_dataloader.load(model.retriever, k=args.train_batch_size):
+        for epoch in range(start_epoch, int(args.num_train_epochs)):
+            resumed_here = epoch_started and epoch == start_epoch       # inside a saved epoch: its shuffle is in the state
+            if not resumed_here:
+                train_dataloader.shuffle()
+            failed_retrieval = resumed_failed if resumed_here else 0
+            position = start_position if resumed_here else 0
+            for batch in train_dataloader.load(model.retriever, k=args.train_batch_size, **({"start": position} if position else {})):
                 batch_step += 1
+                position += 1
                 if batch == {}:
                     failed_retrieval += 1
                     failed_steps.append(batch_step)
@@ -308,12 +387,16 @@ def main(argv=None):
                     loss = loss / G
                 optimizer.scale_loss(loss).backward()
                 meter.add(loss.detach(), global_step)
+                pending_grad = True
 
                 if is_update_step(batch_step, G):
                     optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
                     model.zero_grad()
                     global_step += 1
                     update_steps.append(batch_step)
+                    pending_grad = False
+                    if digests is not None:
+                        digests.after_update(global_step)
 
                     if args.eval_period != -1 and global_step % args.eval_period == 0:
                         em = evaluate()
@@ -333,6 +416,15 @@ def main(argv=None):
                             if wait_step == args.wait_step:
                                 stop_training = True
 
+                    if args.save_state:
+                        stopped_early = global_step == args.stop_after_updates
+                        if global_step % args.save_checkpoints_steps == 0 or stopped_early:
+                            save_state(epoch, position, True, failed_retrieval)
+                        if stopped_early:
+                            break
+            if stopped_early:
+                break
+
             logger.info(f"Failed retrieval: {failed_retrieval}/{len(train_dataloader)} ...")
             failed_per_epoch.append(failed_retrieval)
             em = evaluate()
@@ -348,9 +440,17 @@ def main(argv=None):
             if epoch > 15:
                 logger.info(f"Saving model after epoch {epoch + 1}")
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"model-{epoch+1}-{em}.pt"))
+            if args.save_state:
+                if pending_grad:
+                    logger.info("no trainer state at the end of epoch %d: a gradient is accumulated and waits for its update", epoch)
+                else:
+                    save_state(epoch + 1, 0, False, 0)
             if stop_training:
                 break
         meter.flush(tb)
+        if ckpt is not None:
+            digests.flush(logger)
+            ckpt.close()
         fused = optimizer.state_dict()["fused"]
         seconds = time.perf_counter() - t_start
         logger.info("Training finished!")
@@ -361,11 +461,20 @@ def main(argv=None):
                      failed_retrieval=failed_per_epoch, failed_steps=failed_steps, update_steps=update_steps, skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"],
                      seconds=seconds, best_em=best_em, output_dir=args.output_dir, deterministic=bool(args.deterministic),
                      sampler_seconds=dict(train_dataloader.seconds), sampler_transfers=dict(train_dataloader.transfers))
+        if args.stop_after_updates > 0:
+            stats["stopped_early"] = stopped_early
+        if args.digest_every > 0:
+            stats["state_digests"] = digests.entries
         if os.environ.get("PROQA_STATS_JSON"):
             with open(os.environ["PROQA_STATS_JSON"], "w") as f:
                 json.dump(stats, f)
         return stats
     finally:
+        if ckpt is not None:
+            try:
+                ckpt.close()
+            except Exception:
+                logger.exception("the last trainer state was not written")
         if tb is not None:
             tb.close()
         if para_db is not None:
