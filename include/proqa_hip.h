@@ -378,7 +378,19 @@ int proqa_reader_select_f16(const void* pooled, int batch, int hidden_size, cons
 /* The kernels the encoder is made of, individually (tests, other drivers). */
 /* y[m,n] = epilogue(x[m,k] . w[n,k]^T + bias[n]): the encoder's dense layer as a hand-written MFMA GEMM (fp16 in, fp32
  * accumulate, fp16 out; 256 x 256 x 64 tiles, LDS-DMA ring).  epilogue 0: none (bias ignored), 1: + bias,
- * 2: erf-GELU(. + bias) = BertIntermediate.  m and n multiples of 256, k a multiple of 64. */
+ * 2: erf-GELU(. + bias) = BertIntermediate.  m and n multiples of 256, k a multiple of 64; x, w, y and a non-NULL bias
+ * 16-byte aligned (rows are dense: x [m, k], w [n, k], y [m, n]); anything else is PROQA_EINVAL before any launch, m = 0
+ * is PROQA_OK and writes nothing.  The contract as tests/test_gemm_gpu.py holds it, element by element against float64:
+ *   - the sum is accumulated in fp32 (fp16 subnormal operands count in full) and rounded once to fp16 after the epilogue; a
+ *     result beyond fp16's range is the correctly rounded +-Inf (after the GELU a pre-activation below -65504 gives 0);
+ *   - the GELU is max(t, 0) - a Phi(-a), a = min(|t|, 6), with Phi(-a) = 2^q(a), q a degree-6 fit: off by at most
+ *     4.6e-5 a Phi(-a) from the erf form before rounding (relative to Phi(-a): the negative tail keeps its accuracy), and
+ *     its fp16 result is the correctly rounded one or its neighbour (one step off for ~2 % of all fp16 arguments).  It is
+ *     built on max(): a NaN pre-activation comes out of epilogue 2 as a finite number (-6 Phi(-6), i.e. -0), and -Inf as 0;
+ *     epilogues 0 and 1 hand NaN and Inf on.  An operand's Inf / NaN reaches its own output row / column only;
+ *   - results do not depend on the base alignment, are bit-identical from launch to launch, and nothing outside y is written;
+ *   - the launch is min(tiles, max(CU count, 8)) persistent workgroups: the tile walk assigns the 256-row slabs by
+ *     blockIdx.x & 7 and needs all 8 residues whenever there are more slabs than workgroups. */
 #define PROQA_GEMM_EPI_NONE 0
 #define PROQA_GEMM_EPI_BIAS 1
 #define PROQA_GEMM_EPI_BIAS_GELU 2

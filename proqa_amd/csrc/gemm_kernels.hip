@@ -421,9 +421,16 @@ int proqa_gemm_tn_f16(const void* x, const void* w, const void* bias, void* y, i
   if (m < 0 || n <= 0 || k <= 0 || m % kTile || n % kTile || k % kBK || m > (1ll << 30))
     return fail(PROQA_EINVAL, "gemm_tn: m=%lld n=%d k=%d must be multiples of %d / %d / %d", (long long)m, n, k, kTile, kTile,
                 kBK);
+  // the LDS-DMA pieces, the bias loads and the output stores are 16-byte accesses (row pitches are multiples of 128 bytes)
+  const struct { const char* name; const void* p; } ptrs[] = {{"x", x}, {"w", w}, {"bias", bias}, {"y", y}};
+  for (const auto& a : ptrs)
+    if ((uintptr_t)a.p & 15) return fail(PROQA_EINVAL, "gemm_tn: %s is not 16-byte aligned", a.name);
   if (m == 0) return PROQA_OK;
   const long long tiles = (m / kTile) * (long long)(n / kTile);
-  const unsigned grid = (unsigned)std::min<long long>(tiles, device_cu_count());
+  // At least 8 workgroups wherever there are 8 tiles: workgroup b walks the token slabs b % 8, b % 8 + 8, ... only, so when
+  // there are more slabs than workgroups all 8 residues of blockIdx.x & 7 must exist, or the slabs of a missing residue are
+  // never computed (a device with fewer than 8 CUs).  grid = tiles < 8 is safe: then tiles_m <= grid.
+  const unsigned grid = (unsigned)std::min<long long>(tiles, std::max(device_cu_count(), 8));
   hipStream_t st = as_stream(stream);
   const dim3 g(grid), b(kWaves * 64);
   switch (epilogue) {
