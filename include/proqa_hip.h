@@ -700,6 +700,58 @@ int proqa_reader_loss_backward_f16(const void* hidden, const int32_t* seq_lens_d
                                    int flags, double p, uint64_t seed, int site, uint32_t call, const void* logits,
                                    const float* stats, const float* grad_in, void* d_hidden, float* d_qa_w, float* d_qa_b,
                                    void* d_q, void* ws, size_t ws_bytes, void* stream);
+/* The same objective over n_questions questions in ONE call (three launches forward, four backward, whatever n_questions
+ * is): the same seven kernels with a question dimension; the single-question entry points above are their one-question
+ * case.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive); every rule of the block above holds.
+ * Packed layout only: hidden [T, hidden_size] with cu_seqlens_dev [batch + 1] over the sequences of ALL questions,
+ * para_offset_dev [batch], start_pos / end_pos [batch, n_answers]; para_embed [n_paras, 128] / labels [n_paras] hold the
+ * questions' rows one question after the other; q fp16 [n_questions, 128]; one qa_w / qa_b / flags / para_dtype / dropout
+ * tuple for the call.  Device CSR arrays, int32 [n_questions + 1]: question i owns the sequences question_seq_dev[i] ..
+ * question_seq_dev[i + 1] (B_i of them) and the rows question_para_dev[i] .. question_para_dev[i + 1] of para_embed / labels
+ * (P_i of them, the first B_i belong to its sequences, in order).  max_seqs / max_paras: the largest B_i / P_i; with
+ * n_questions, batch and seq_len they size the grids, nothing is read back.
+ * Outputs: loss_out fp32 [n_questions, 3] = (total, joint, early) per question; logits_out [T, 2]; stats fp32
+ * [8 * n_questions + 2 * batch]: the single-question layout question after question (question i's block starts at
+ * 8 * i + 2 * question_seq[i]).  Backward: grad_in fp32 [n_questions], one incoming gradient per question; d_hidden
+ * [T, hidden_size], d_q fp16 [n_questions, 128], ONE d_qa_w [2, hidden_size] / d_qa_b [2].
+ * CONTRACT: loss_out[i], the logits of question i's rows, its block of stats, its rows of d_hidden and d_q[i] carry the
+ * bits the single-question entry points return for the question's slice of the operands -- rows cu[first sequence] ..
+ * cu[last sequence + 1] of hidden, cu_seqlens rebased to 0, its rows of para_embed / labels, q[i], grad_in[i] -- with p == 0.
+ * d_qa_w / d_qa_b: question i's value is the compensated ascending slab sum the single call makes for the slice at the SAME
+ * seq_len (seq_len fixes the slabs per sequence, and the compensated sum is taken over all of them); the values are added
+ * in ascending question order by plain fp32 additions, starting from question 0's value: ((v_0 + v_1) + v_2) + ...
+ * With p > 0 the mask coordinate is the packed row of the WHOLE pack (site 255, one `call` for the pass), so the masks of
+ * different questions are independent; this is the one place where a slice call (whose rows count from 0) differs.
+ * Limits, PROQA_EINVAL before the device is touched: 1 <= n_questions <= 4096; n_questions <= batch <= 65536;
+ * batch <= n_paras <= 4194304 (2^22); max_seqs / max_paras possible maxima of n_questions counts >= 1 that sum to batch /
+ * n_paras, max_seqs <= max_paras <= 65536; hidden_size, n_answers, seq_len, dim and the alignments as the single call.
+ * question_seq_host / question_para_host: host copies of the two arrays, both or neither.  Given, every question is checked
+ * as well (the arrays run from 0 to batch / n_paras, 1 <= B_i <= P_i, B_i <= max_seqs, P_i <= max_paras).  The DEVICE
+ * arrays cannot be checked without a read-back: the kernels clamp every entry into [0, batch] / [0, n_paras] and make each
+ * pair ascending, and take at most max_paras rows per question, so arrays that are not ascending or do not cover batch /
+ * n_paras give wrong values (a question left with no sequence, or fewer rows than sequences, gets a zero loss and no
+ * gradient) and never an access out of range.
+ * ws: at least proqa_reader_loss_multi_workspace_bytes(...) bytes (a pure host function; 0 for sizes out of range). */
+size_t proqa_reader_loss_multi_workspace_bytes(int n_questions, int batch, int seq_len, int hidden_size, int n_answers,
+                                               int n_paras, int max_paras);
+int proqa_reader_loss_multi_f16(const void* hidden, const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden_size,
+                                const int32_t* para_offset_dev, const void* qa_w, const void* qa_b, const int32_t* start_pos,
+                                const int32_t* end_pos, int n_answers, const void* q, const void* para_embed, int para_dtype,
+                                const int32_t* labels, int n_paras, int dim, const int32_t* question_seq_dev,
+                                const int32_t* question_para_dev, int n_questions, int max_seqs, int max_paras,
+                                const int32_t* question_seq_host, const int32_t* question_para_host, int flags, double p,
+                                uint64_t seed, int site, uint32_t call, void* logits_out, float* stats, float* loss_out,
+                                void* ws, size_t ws_bytes, void* stream);
+int proqa_reader_loss_multi_backward_f16(const void* hidden, const int32_t* cu_seqlens_dev, int batch, int seq_len,
+                                         int hidden_size, const int32_t* para_offset_dev, const void* qa_w,
+                                         const int32_t* start_pos, const int32_t* end_pos, int n_answers, const void* q,
+                                         const void* para_embed, int para_dtype, const int32_t* labels, int n_paras, int dim,
+                                         const int32_t* question_seq_dev, const int32_t* question_para_dev, int n_questions,
+                                         int max_seqs, int max_paras, const int32_t* question_seq_host,
+                                         const int32_t* question_para_host, int flags, double p, uint64_t seed, int site,
+                                         uint32_t call, const void* logits, const float* stats, const float* grad_in,
+                                         void* d_hidden, float* d_qa_w, float* d_qa_b, void* d_q, void* ws, size_t ws_bytes,
+                                         void* stream);
 /* The weight gradient of a linear layer y = x w^T, on a kernel of our own (csrc/linear_kernels.hip) so that it never
  * passes through fp16: fp16 operands, ONE fp32 sum over the whole token axis on v_mfma_f32_32x32x16_f16, fp32 output
  * written or accumulated straight into the caller's buffer.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive).

@@ -231,6 +231,16 @@ SIGNATURES = {
                                                c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                                c_double, c_uint64, c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "proqa_reader_loss_multi_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "proqa_reader_loss_multi_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                            c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_double, c_uint64,
+                                            c_int, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "proqa_reader_loss_multi_backward_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                                     c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                                     c_double, c_uint64, c_int, c_uint32, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "proqa_linear_wgrad_f16": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
                                        c_void_p]),
     "proqa_linear_wgrad_plan": (c_int, [c_int64, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_size_t)]),

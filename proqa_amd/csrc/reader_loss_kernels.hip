@@ -18,6 +18,12 @@
 //             reader_loss_bwd_rank  the forward's row ownership: drank_j, and the workgroup's slab of d_q
 //             reader_loss_bwd_sum   the slabs in ascending order (compensated, as reduce_slabs of train_kernels.hip)
 //
+// Every kernel has a question dimension (struct Questions): proqa_reader_loss_multi_f16 / _backward_f16 run the same seven
+// launches over the sequences and para rows of Q questions, cut by two device CSR arrays; the single-question entry points
+// pass no arrays and are the Q = 1 case of the same bodies, index for index.  The row kernels and reader_loss_pairs keep
+// their grids over the sequences of all questions, the rank kernels run Q x (blocks of the largest question),
+// reader_loss_finish one workgroup per question; reader_loss_bwd_sum adds the questions' d_qa_w / d_qa_b in ascending order.
+//
 // Determinism: no atomics; a wave adds by the xor butterfly, a workgroup adds its waves in a fixed order, workgroups meet
 // only in the ascending sums of reader_loss_finish and reader_loss_bwd_sum.  The T x H passes read every hidden row of
 // the paragraph once (16-byte loads, a wave per row, two rows in flight); para_embed is read once per pass.
@@ -124,6 +130,52 @@ __device__ __forceinline__ uint32_t packed_row0(const Layout& g, int b, int lane
   for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off, 64);
   return (uint32_t)n;
 }
+
+// ---- the questions of a pass ----------------------------------------------------------------------------------------------
+// Question i owns the sequences seq[i] .. seq[i + 1] and the rows para[i] .. para[i + 1] of para_embed / labels (CSR, on the
+// device).  seq == nullptr is the single-question call: one question that owns everything, and every index below is the
+// index the single-question kernels have always formed.  The arrays are not trusted: every bound is clamped into
+// [0, batch] / [0, n_paras] and made ascending, so that arrays which are not a cover give wrong sums and no stray access.
+struct Questions {
+  const int* seq;
+  const int* para;
+  int n;             // the number of questions
+  int batch;         // sequences of all questions
+  int n_paras;       // rows of para_embed of all questions
+  int rank_blocks;   // blocks of 64 para rows the rank grids hold per question
+};
+struct QSpan {
+  int b0, nb;   // the question's first sequence and their number
+  int p0, np;   // its first para row and their number
+};
+__device__ __forceinline__ int clamp_to(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ QSpan question_span(const Questions& qs, int qi) {
+  if (!qs.seq) return QSpan{0, qs.batch, 0, qs.n_paras};
+  QSpan s;
+  s.b0 = clamp_to(qs.seq[qi], 0, qs.batch);
+  s.nb = clamp_to(qs.seq[qi + 1], s.b0, qs.batch) - s.b0;
+  s.p0 = clamp_to(qs.para[qi], 0, qs.n_paras);
+  s.np = clamp_to(qs.para[qi + 1], s.p0, qs.n_paras) - s.p0;
+  return s;
+}
+// the question's blocks of 64 para rows, never more than the rank grids hold
+__device__ __forceinline__ int rank_blocks_of(const Questions& qs, const QSpan& s) {
+  const int n = (s.np + 63) / 64;
+  return n < qs.rank_blocks ? n : qs.rank_blocks;
+}
+// the last question whose first sequence is <= b (bisection; the loads are uniform over the wave)
+__device__ __forceinline__ int question_of_seq(const Questions& qs, int b) {
+  if (!qs.seq) return 0;
+  int lo = 0, hi = qs.n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (qs.seq[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+// the question's stats: the single-question layout (8 scalars, then 2 per sequence), question after question
+__device__ __forceinline__ size_t stats_at(int qi, const QSpan& s) { return (size_t)kStatsHead * qi + 2 * (size_t)s.b0; }
 
 __device__ __forceinline__ void load_head_weights(const _Float16* qa_w, int hsize, int lane, int n_chunks,
                                                   f16x8 (&w0)[kHeadMaxChunks], f16x8 (&w1)[kHeadMaxChunks]) {
@@ -252,19 +304,29 @@ __device__ __forceinline__ void load_q(const _Float16* q, int col0, float (&qv)[
   for (int i = 0; i < 8; ++i) qv[i] = (float)h[i];
 }
 
-// grid ceil(P / 64).  x_out[j] = q . para_embed[j]; rank_part[block * 8] = (max, sum) over the block's rows, (max, sum)
-// over its gold rows, the number of its gold rows.
+// grid n_questions * rank_blocks (question-major): a workgroup owns 64 rows of ONE question's para_embed, counted from the
+// question's first row; a workgroup past the question's rows does nothing, and nothing reads its outputs.
+// x_out[j] = q . para_embed[j]; rank_part[block * 8] = (max, sum) over the block's rows, (max, sum) over its gold rows, the
+// number of its gold rows.
 template <bool kF32>
-__global__ __launch_bounds__(kRankThreads) void reader_loss_rank(const _Float16* __restrict__ q, const void* __restrict__ para,
-                                                                  const int* __restrict__ labels, int n_paras,
-                                                                  float* __restrict__ x_out, float* __restrict__ rank_part) {
+__global__ __launch_bounds__(kRankThreads) void reader_loss_rank(const _Float16* __restrict__ q, const void* __restrict__ para_all,
+                                                                  const int* __restrict__ labels_all, Questions qs,
+                                                                  float* __restrict__ x_all, float* __restrict__ rank_part) {
   __shared__ float xs[kRankRows];
   __shared__ int gold[kRankRows];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col0 = (lane & 15) * 8;
+  const int qi = blockIdx.x / qs.rank_blocks;
+  const QSpan span = question_span(qs, qi);
+  const int n_paras = span.np;
+  const int base = (blockIdx.x - qi * qs.rank_blocks) * kRankRows;
+  if (base >= n_paras) return;
+  const void* para = kF32 ? (const void*)((const float*)para_all + (size_t)span.p0 * PROQA_EMBED_DIM)
+                          : (const void*)((const _Float16*)para_all + (size_t)span.p0 * PROQA_EMBED_DIM);
+  const int* labels = labels_all + span.p0;
+  float* x_out = x_all + span.p0;
   float qv[8];
-  load_q(q, col0, qv);
-  const int base = blockIdx.x * kRankRows;
+  load_q(q + (size_t)qi * PROQA_EMBED_DIM, col0, qv);
   RankRow rows[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
@@ -310,19 +372,40 @@ __device__ __forceinline__ float pair_logprob(const Extent& e, int sp, int ep, c
   return s - zs + t - ze + log_r;
 }
 
-__global__ __launch_bounds__(kFinishThreads) void reader_loss_finish(Layout g, int batch, int n_blocks, int n_answers,
-                                                                      const int* __restrict__ start_pos,
-                                                                      const int* __restrict__ end_pos, int n_rank_blocks,
+// grid n_questions: one workgroup per question; b below counts the question's own sequences
+__global__ __launch_bounds__(kFinishThreads) void reader_loss_finish(Layout g_all, Questions qs, int n_blocks, int n_answers,
+                                                                      const int* __restrict__ start_all,
+                                                                      const int* __restrict__ end_all,
                                                                       int flags, const _Float16* __restrict__ logits,
-                                                                      float* span_part,
-                                                                      const float* __restrict__ rank_part,
-                                                                      const float* __restrict__ x, float* __restrict__ stats,
-                                                                      float* __restrict__ loss_out) {
+                                                                      float* span_all,
+                                                                      const float* __restrict__ rank_all,
+                                                                      const float* __restrict__ x_all, float* __restrict__ stats_all,
+                                                                      float* __restrict__ loss_all) {
   __shared__ Lse red[kFinishThreads / 64];
   __shared__ float redf[kFinishThreads / 64];
   __shared__ float bc[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   constexpr int kWaves = kFinishThreads / 64;
+  const int qi = blockIdx.x;
+  const QSpan span = question_span(qs, qi);
+  const int batch = span.nb;
+  const int n_rank_blocks = rank_blocks_of(qs, span);
+  if (batch < 1 || span.np < batch) {   // only CSR arrays that are not a cover come here: a zero loss and no gradient
+    if (tid < kStatsHead) stats_all[stats_at(qi, span) + tid] = 0.f;
+    if (tid < 3) loss_all[3 * (size_t)qi + tid] = 0.f;
+    return;
+  }
+  Layout g = g_all;  // the question's sequences: cu_seqlens keeps the rows of the whole pack
+  if (g.seq_lens) g.seq_lens += span.b0;
+  if (g.cu_seqlens) g.cu_seqlens += span.b0;
+  g.para_offset += span.b0;
+  const int* start_pos = start_all + (size_t)span.b0 * n_answers;
+  const int* end_pos = end_all + (size_t)span.b0 * n_answers;
+  float* span_part = span_all + (size_t)span.b0 * n_blocks * 4;
+  const float* rank_part = rank_all + (size_t)qi * qs.rank_blocks * 8;
+  const float* x = x_all + span.p0;
+  float* stats = stats_all + stats_at(qi, span);
+  float* loss_out = loss_all + 3 * (size_t)qi;
   float* z = stats + kStatsHead;
 
   // the normalisers of every sequence: a wave per sequence, its blocks' partials lane by lane
@@ -420,23 +503,34 @@ __global__ __launch_bounds__(kFinishThreads) void reader_loss_finish(Layout g, i
 
 // ---- backward: pair weights ------------------------------------------------------------------------------------------------
 // a wave per sequence: w[b * A + a] = exp(l_ba + joint) (0 for an invalid pair), omega[b] = their sum
-__global__ __launch_bounds__(256) void reader_loss_pairs(Layout g, int batch, int n_answers, const int* __restrict__ start_pos,
+// (b counts the sequences of all questions; the wave looks its question up)
+__global__ __launch_bounds__(256) void reader_loss_pairs(Layout g, Questions qs, int n_answers, const int* __restrict__ start_pos,
                                                          const int* __restrict__ end_pos,
                                                          const _Float16* __restrict__ q, const void* __restrict__ para,
                                                          int para_f32, const _Float16* __restrict__ logits,
-                                                         const float* __restrict__ stats, float* __restrict__ w,
+                                                         const float* __restrict__ stats_all, float* __restrict__ w,
                                                          float* __restrict__ omega) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= batch) return;
+  if (b >= qs.batch) return;
+  const int qi = question_of_seq(qs, b);
+  const QSpan span = question_span(qs, qi);
+  const int lb = b - span.b0;   // the sequence within its question, and its row of the question's para_embed
+  if (lb < 0 || lb >= span.nb || lb >= span.np) {   // only CSR arrays that are not a cover come here
+    for (int a = lane; a < n_answers; a += 64) w[(size_t)b * n_answers + a] = 0.f;
+    if (lane == 0) omega[b] = 0.f;
+    return;
+  }
+  const float* stats = stats_all + stats_at(qi, span);
   // x_b as the forward formed it: the row's 16 lanes (here lanes 0..15; the other lanes repeat them)
   const int col0 = (lane & 15) * 8;
   float qv[8];
-  load_q(q, col0, qv);
-  const RankRow row = para_f32 ? load_rank_row<true>(para, b, col0) : load_rank_row<false>(para, b, col0);
+  load_q(q + (size_t)qi * PROQA_EMBED_DIM, col0, qv);
+  const long long prow = (long long)span.p0 + lb;
+  const RankRow row = para_f32 ? load_rank_row<true>(para, prow, col0) : load_rank_row<false>(para, prow, col0);
   const float log_r = rank_score(row, qv) - stats[1];
   const Extent e = extent_of(g, b);
-  const float joint = stats[0], zs = stats[kStatsHead + 2 * b], ze = stats[kStatsHead + 2 * b + 1];
+  const float joint = stats[0], zs = stats[kStatsHead + 2 * lb], ze = stats[kStatsHead + 2 * lb + 1];
   float sum = 0.f;
   for (int a = lane; a < n_answers; a += 64) {
     const size_t i = (size_t)b * n_answers + a;
@@ -455,12 +549,12 @@ __global__ __launch_bounds__(256) void reader_loss_pairs(Layout g, int batch, in
 // d_qa_b [2].  slab_stride = 2 H + 8.
 template <bool kDrop>
 __global__ __launch_bounds__(kRowThreads) void reader_loss_bwd_rows(const _Float16* __restrict__ hidden, Layout g,
-                                                                     int n_blocks, int hsize,
+                                                                     Questions qs, int n_blocks, int hsize,
                                                                      const _Float16* __restrict__ qa_w, int n_answers,
                                                                      const int* __restrict__ start_pos,
                                                                      const int* __restrict__ end_pos, int flags,
                                                                      DropoutParams drop, const _Float16* __restrict__ logits,
-                                                                     const float* __restrict__ stats,
+                                                                     const float* __restrict__ stats_all,
                                                                      const float* __restrict__ grad_in,
                                                                      const float* __restrict__ w,
                                                                      const float* __restrict__ omega,
@@ -476,10 +570,16 @@ __global__ __launch_bounds__(kRowThreads) void reader_loss_bwd_rows(const _Float
   const int n_chunks = hsize >> 3;
   const int slab_stride = 2 * hsize + 8;
   const int n_rows = g.cu_seqlens ? ext.len : g.seq_len;   // rows of the sequence that d_hidden has
-  const float gin = grad_in[0];
-  const bool has_pair = stats[3] != 0.f;
+  // the sequence's question: its incoming gradient and its stats (b counts the sequences of all questions)
+  const int qi = question_of_seq(qs, b);
+  const QSpan span = question_span(qs, qi);
+  const int lb = b - span.b0;
+  const bool owned = lb >= 0 && lb < span.nb;   // false only under CSR arrays that are not a cover: the rows get zeros
+  const float* stats = stats_all + stats_at(qi, span);
+  const float gin = grad_in[qi];
+  const bool has_pair = owned && stats[3] != 0.f;
   const float cb = (flags & PROQA_READER_LOSS_SHARED_NORM) ? 1.f : omega[b];
-  const float zs = stats[kStatsHead + 2 * b], ze = stats[kStatsHead + 2 * b + 1];
+  const float zs = owned ? stats[kStatsHead + 2 * lb] : 0.f, ze = owned ? stats[kStatsHead + 2 * lb + 1] : 0.f;
 
   for (int a = tid; a < n_answers; a += kRowThreads) {
     const size_t i = (size_t)b * n_answers + a;
@@ -630,21 +730,31 @@ __global__ __launch_bounds__(kRowThreads) void reader_loss_bwd_rows(const _Float
 // grid ceil(P / 64): drank_j = [pair](r_j - omega_j [j < B]) + [early](r_j - g_j), times the incoming gradient; the
 // workgroup's sum of drank_j para_embed[j] goes to dq_slabs[block * 128].
 template <bool kF32>
-__global__ __launch_bounds__(kRankThreads) void reader_loss_bwd_rank(const _Float16* __restrict__ q, const void* __restrict__ para,
-                                                                      const int* __restrict__ labels, int n_paras, int batch,
-                                                                      const float* __restrict__ stats,
+__global__ __launch_bounds__(kRankThreads) void reader_loss_bwd_rank(const _Float16* __restrict__ q, const void* __restrict__ para_all,
+                                                                      const int* __restrict__ labels_all, Questions qs,
+                                                                      const float* __restrict__ stats_all,
                                                                       const float* __restrict__ grad_in,
-                                                                      const float* __restrict__ omega,
+                                                                      const float* __restrict__ omega_all,
                                                                       float* __restrict__ dq_slabs) {
   __shared__ float part[kRankWaves][PROQA_EMBED_DIM];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col0 = (lane & 15) * 8;
+  // the forward's ownership: the grid is question-major, the rows count from the question's first
+  const int qi = blockIdx.x / qs.rank_blocks;
+  const QSpan span = question_span(qs, qi);
+  const int n_paras = span.np, batch = span.nb;
+  const int base = (blockIdx.x - qi * qs.rank_blocks) * kRankRows;
+  if (base >= n_paras) return;
+  const void* para = kF32 ? (const void*)((const float*)para_all + (size_t)span.p0 * PROQA_EMBED_DIM)
+                          : (const void*)((const _Float16*)para_all + (size_t)span.p0 * PROQA_EMBED_DIM);
+  const int* labels = labels_all + span.p0;
+  const float* omega = omega_all + span.b0;
+  const float* stats = stats_all + stats_at(qi, span);
   float qv[8];
-  load_q(q, col0, qv);
+  load_q(q + (size_t)qi * PROQA_EMBED_DIM, col0, qv);
   const float zr = stats[1], zg = stats[2];
   const bool has_pair = stats[3] != 0.f, has_gold = stats[4] != 0.f;
-  const float gin = grad_in[0];
-  const int base = blockIdx.x * kRankRows;
+  const float gin = grad_in[qi];
   RankRow rows[4];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
@@ -709,33 +819,50 @@ __device__ __forceinline__ float sum_slabs(const float* __restrict__ p, long lon
   for (; k < n; ++k) kahan_add(p[(size_t)k * stride], s, comp);
   return s;
 }
-__global__ __launch_bounds__(256) void reader_loss_bwd_sum(const float* __restrict__ slabs, long long n_slabs, int hsize,
-                                                           const float* __restrict__ dq_slabs, int n_rank_blocks,
+// d_qa_w / d_qa_b: the compensated sum of EACH question's slabs (what the single-question call returns for it), then the
+// questions in ascending order by plain fp32 additions, starting from question 0's value.  d_q: 128 columns per question.
+__global__ __launch_bounds__(256) void reader_loss_bwd_sum(const float* __restrict__ slabs, Questions qs, int n_blocks, int hsize,
+                                                           const float* __restrict__ dq_slabs,
                                                            float* __restrict__ d_qa_w, float* __restrict__ d_qa_b,
                                                            _Float16* __restrict__ d_q) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int n_w = 2 * hsize;
+  const size_t stride = (size_t)n_w + 8;
   if (t < n_w + 2) {
-    const float s = sum_slabs(slabs + t, n_slabs, (size_t)n_w + 8);
+    QSpan span = question_span(qs, 0);
+    float s = sum_slabs(slabs + (size_t)span.b0 * n_blocks * stride + t, (long long)span.nb * n_blocks, stride);
+    for (int qi = 1; qi < qs.n; ++qi) {
+      span = question_span(qs, qi);
+      s += sum_slabs(slabs + (size_t)span.b0 * n_blocks * stride + t, (long long)span.nb * n_blocks, stride);
+    }
     if (t < n_w) d_qa_w[t] = s;
     else d_qa_b[t - n_w] = s;
-  } else if (t < n_w + 2 + PROQA_EMBED_DIM) {
-    const int c = t - n_w - 2;
-    d_q[c] = (_Float16)sum_slabs(dq_slabs + c, n_rank_blocks, PROQA_EMBED_DIM);
+  } else if (t < n_w + 2 + qs.n * PROQA_EMBED_DIM) {
+    const int qi = (t - n_w - 2) / PROQA_EMBED_DIM, c = (t - n_w - 2) % PROQA_EMBED_DIM;
+    const QSpan span = question_span(qs, qi);
+    d_q[(size_t)qi * PROQA_EMBED_DIM + c] = (_Float16)sum_slabs(
+        dq_slabs + (size_t)qi * qs.rank_blocks * PROQA_EMBED_DIM + c, rank_blocks_of(qs, span), PROQA_EMBED_DIM);
   }
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 inline size_t up16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-// the regions of the caller's scratch (bytes from its start); forward and backward overlay each other
+// the caps of a multi-question pass (proqa_hip.h)
+constexpr int kMaxQuestions = 4096;
+constexpr int kMaxPackSeqs = 65536;
+constexpr int kMaxPackParas = 1 << 22;
+const int kPackedOnly = 0;   // stands for cu_seqlens in check_sizes: the multi calls take the packed layout only
+
+// the regions of the caller's scratch (bytes from its start); forward and backward overlay each other.  n_rank: the rank
+// grids' blocks over all questions (n_questions * blocks of the largest question).
 struct Scratch {
   size_t span_part, rank_part, x;             // forward
   size_t w, omega, slabs, dq_slabs;           // backward
   size_t bytes;
 };
-Scratch scratch_of(int batch, int seq_len, int hsize, int n_answers, int n_paras) {
-  const size_t n_blocks = (size_t)ceil_div(seq_len, kRowsPerBlock), n_rank = (size_t)ceil_div(n_paras, kRankRows);
+Scratch scratch_of(int batch, int seq_len, int hsize, int n_answers, int n_paras, size_t n_rank) {
+  const size_t n_blocks = (size_t)ceil_div(seq_len, kRowsPerBlock);
   Scratch s;
   size_t at = 0;
   s.span_part = at, at += up16((size_t)batch * n_blocks * 4 * sizeof(float));
@@ -751,9 +878,9 @@ Scratch scratch_of(int batch, int seq_len, int hsize, int n_answers, int n_paras
   return s;
 }
 
-// what both entry points check before the device is touched
-int check_sizes(const char* who, int batch, int seq_len, int hsize, int n_answers, int n_paras, int dim, int para_dtype,
-                int flags, const void* seq_lens, const void* cu_seqlens) {
+// what every entry point checks before the device is touched; paras_cap: the most rows of para_embed the call takes
+int check_sizes(const char* who, int batch, int seq_len, int hsize, int n_answers, int n_paras, int paras_cap, int dim,
+                int para_dtype, int flags, const void* seq_lens, const void* cu_seqlens) {
   if (dim != PROQA_EMBED_DIM) return fail(PROQA_EINVAL, "%s: dim=%d, only %d is supported", who, dim, PROQA_EMBED_DIM);
   if (hsize <= 0 || hsize % 8 || hsize > 64 * kHeadMaxChunks * 8)
     return fail(PROQA_EINVAL, "%s: hidden=%d must be a multiple of 8 and <= %d", who, hsize, 64 * kHeadMaxChunks * 8);
@@ -761,13 +888,130 @@ int check_sizes(const char* who, int batch, int seq_len, int hsize, int n_answer
     return fail(PROQA_EINVAL, "%s: batch=%d must be >= 1 and seq_len=%d in [1, %d]", who, batch, seq_len, kMaxSeqLen);
   if (n_answers < 1 || n_answers > kMaxAnswers)
     return fail(PROQA_EINVAL, "%s: %d answer positions per sequence, must be in [1, %d]", who, n_answers, kMaxAnswers);
-  if (n_paras < batch || n_paras > kMaxParas)
+  if (n_paras < batch || n_paras > paras_cap)
     return fail(PROQA_EINVAL, "%s: para_embed has %d rows; the first %d belong to the sequences and at most %d are taken", who,
-                n_paras, batch, kMaxParas);
+                n_paras, batch, paras_cap);
   if (para_dtype != PROQA_F16 && para_dtype != PROQA_F32) return fail(PROQA_EINVAL, "%s: para_dtype=%d", who, para_dtype);
   if (flags & ~(PROQA_READER_LOSS_SHARED_NORM | PROQA_READER_LOSS_NO_EARLY)) return fail(PROQA_EINVAL, "%s: flags=%d", who, flags);
   if ((seq_lens == nullptr) == (cu_seqlens == nullptr))
     return fail(PROQA_EINVAL, "%s: exactly one of seq_lens (padded) and cu_seqlens (packed) must be given", who);
+  return PROQA_OK;
+}
+
+// the questions of a multi call: the integers, and the host copies of the CSR arrays when the caller has them
+int check_questions(const char* who, int n_questions, int batch, int n_paras, int max_seqs, int max_paras,
+                    const int32_t* seq_host, const int32_t* para_host) {
+  if (n_questions < 1 || n_questions > kMaxQuestions)
+    return fail(PROQA_EINVAL, "%s: %d questions, must be in [1, %d]", who, n_questions, kMaxQuestions);
+  if (batch < n_questions || batch > kMaxPackSeqs)
+    return fail(PROQA_EINVAL, "%s: %d sequences for %d questions; every question has one, and at most %d are taken", who, batch,
+                n_questions, kMaxPackSeqs);
+  if (max_seqs < 1 || max_seqs > batch - (n_questions - 1) || (long long)max_seqs * n_questions < batch)
+    return fail(PROQA_EINVAL, "%s: max_seqs=%d cannot be the largest of %d questions' counts that sum to %d", who, max_seqs,
+                n_questions, batch);
+  if (max_paras < max_seqs || max_paras > kMaxParas || max_paras > n_paras - (n_questions - 1) ||
+      (long long)max_paras * n_questions < n_paras)
+    return fail(PROQA_EINVAL, "%s: max_paras=%d cannot be the largest of %d questions' counts that sum to %d (each >= its "
+                "sequences, <= %d)", who, max_paras, n_questions, n_paras, kMaxParas);
+  if ((seq_host == nullptr) != (para_host == nullptr))
+    return fail(PROQA_EINVAL, "%s: the host copies of question_seq and question_para come together or not at all", who);
+  if (!seq_host) return PROQA_OK;
+  if (seq_host[0] != 0 || seq_host[n_questions] != batch || para_host[0] != 0 || para_host[n_questions] != n_paras)
+    return fail(PROQA_EINVAL, "%s: question_seq must run from 0 to %d and question_para from 0 to %d", who, batch, n_paras);
+  for (int i = 0; i < n_questions; ++i) {
+    const long long nb = (long long)seq_host[i + 1] - seq_host[i], np = (long long)para_host[i + 1] - para_host[i];
+    if (nb < 1 || nb > max_seqs || np < nb || np > max_paras)
+      return fail(PROQA_EINVAL, "%s: question %d has %lld sequences and %lld rows of para_embed; 1 <= sequences <= rows, at most "
+                  "max_seqs=%d and max_paras=%d", who, i, nb, np, max_seqs, max_paras);
+  }
+  return PROQA_OK;
+}
+
+// the operands both passes share
+struct Operands {
+  const void* hidden;
+  Layout g;
+  Questions qs;
+  int hsize;
+  const void* qa_w;
+  const int* start_pos;
+  const int* end_pos;
+  int n_answers;
+  const void* q;
+  const void* para;
+  int para_dtype;
+  const int* labels;
+  int flags;
+  DropoutParams drop;
+};
+
+int launch_forward(const Operands& o, const void* qa_b, void* logits_out, float* stats, float* loss_out, void* ws,
+                   const Scratch& sc, hipStream_t st) {
+  const int n_blocks = ceil_div(o.g.seq_len, kRowsPerBlock);
+  const unsigned n_rank = (unsigned)((size_t)o.qs.n * o.qs.rank_blocks);
+  float* span_part = (float*)((char*)ws + sc.span_part);
+  float* rank_part = (float*)((char*)ws + sc.rank_part);
+  float* x = (float*)((char*)ws + sc.x);
+  const dim3 row_grid((unsigned)((size_t)n_blocks * o.qs.batch));
+  if (o.drop.thr > 0) {
+    hipLaunchKernelGGL(reader_loss_rows<true>, row_grid, dim3(kRowThreads), 0, st, (const _Float16*)o.hidden, o.g, n_blocks, o.hsize,
+                       (const _Float16*)o.qa_w, (const _Float16*)qa_b, o.drop, (_Float16*)logits_out, span_part);
+  } else {
+    hipLaunchKernelGGL(reader_loss_rows<false>, row_grid, dim3(kRowThreads), 0, st, (const _Float16*)o.hidden, o.g, n_blocks, o.hsize,
+                       (const _Float16*)o.qa_w, (const _Float16*)qa_b, o.drop, (_Float16*)logits_out, span_part);
+  }
+  PROQA_LAUNCH_CHECK();
+  if (o.para_dtype == PROQA_F32) {
+    hipLaunchKernelGGL(reader_loss_rank<true>, dim3(n_rank), dim3(kRankThreads), 0, st, (const _Float16*)o.q, o.para, o.labels,
+                       o.qs, x, rank_part);
+  } else {
+    hipLaunchKernelGGL(reader_loss_rank<false>, dim3(n_rank), dim3(kRankThreads), 0, st, (const _Float16*)o.q, o.para, o.labels,
+                       o.qs, x, rank_part);
+  }
+  PROQA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(reader_loss_finish, dim3((unsigned)o.qs.n), dim3(kFinishThreads), 0, st, o.g, o.qs, n_blocks, o.n_answers,
+                     o.start_pos, o.end_pos, o.flags, (const _Float16*)logits_out, span_part, (const float*)rank_part,
+                     (const float*)x, stats, loss_out);
+  PROQA_LAUNCH_CHECK();
+  return PROQA_OK;
+}
+
+int launch_backward(const Operands& o, const void* logits, const float* stats, const float* grad_in, void* d_hidden,
+                    float* d_qa_w, float* d_qa_b, void* d_q, void* ws, const Scratch& sc, hipStream_t st) {
+  const int n_blocks = ceil_div(o.g.seq_len, kRowsPerBlock);
+  const unsigned n_rank = (unsigned)((size_t)o.qs.n * o.qs.rank_blocks);
+  float* w = (float*)((char*)ws + sc.w);
+  float* omega = (float*)((char*)ws + sc.omega);
+  float* slabs = (float*)((char*)ws + sc.slabs);
+  float* dq_slabs = (float*)((char*)ws + sc.dq_slabs);
+  hipLaunchKernelGGL(reader_loss_pairs, dim3((unsigned)ceil_div(o.qs.batch, 4)), dim3(256), 0, st, o.g, o.qs, o.n_answers,
+                     o.start_pos, o.end_pos, (const _Float16*)o.q, o.para, (int)(o.para_dtype == PROQA_F32),
+                     (const _Float16*)logits, stats, w, omega);
+  PROQA_LAUNCH_CHECK();
+  const dim3 row_grid((unsigned)((size_t)n_blocks * o.qs.batch));
+  const size_t lds = (size_t)(kRowWaves / 2) * (2 * (size_t)o.hsize + 8) * sizeof(float);
+  if (o.drop.thr > 0) {
+    hipLaunchKernelGGL(reader_loss_bwd_rows<true>, row_grid, dim3(kRowThreads), lds, st, (const _Float16*)o.hidden, o.g, o.qs, n_blocks,
+                       o.hsize, (const _Float16*)o.qa_w, o.n_answers, o.start_pos, o.end_pos, o.flags, o.drop,
+                       (const _Float16*)logits, stats, grad_in, (const float*)w, (const float*)omega, (_Float16*)d_hidden, slabs);
+  } else {
+    hipLaunchKernelGGL(reader_loss_bwd_rows<false>, row_grid, dim3(kRowThreads), lds, st, (const _Float16*)o.hidden, o.g, o.qs, n_blocks,
+                       o.hsize, (const _Float16*)o.qa_w, o.n_answers, o.start_pos, o.end_pos, o.flags, o.drop,
+                       (const _Float16*)logits, stats, grad_in, (const float*)w, (const float*)omega, (_Float16*)d_hidden, slabs);
+  }
+  PROQA_LAUNCH_CHECK();
+  if (o.para_dtype == PROQA_F32) {
+    hipLaunchKernelGGL(reader_loss_bwd_rank<true>, dim3(n_rank), dim3(kRankThreads), 0, st, (const _Float16*)o.q, o.para, o.labels,
+                       o.qs, stats, grad_in, (const float*)omega, dq_slabs);
+  } else {
+    hipLaunchKernelGGL(reader_loss_bwd_rank<false>, dim3(n_rank), dim3(kRankThreads), 0, st, (const _Float16*)o.q, o.para, o.labels,
+                       o.qs, stats, grad_in, (const float*)omega, dq_slabs);
+  }
+  PROQA_LAUNCH_CHECK();
+  const int n_out = 2 * o.hsize + 2 + o.qs.n * PROQA_EMBED_DIM;
+  hipLaunchKernelGGL(reader_loss_bwd_sum, dim3((unsigned)ceil_div(n_out, 256)), dim3(256), 0, st, (const float*)slabs, o.qs, n_blocks,
+                     o.hsize, (const float*)dq_slabs, d_qa_w, d_qa_b, (_Float16*)d_q);
+  PROQA_LAUNCH_CHECK();
   return PROQA_OK;
 }
 
@@ -780,7 +1024,7 @@ extern "C" {
 
 size_t proqa_reader_loss_workspace_bytes(int batch, int seq_len, int hidden_size, int n_answers, int n_paras) {
   if (batch < 1 || seq_len < 1 || hidden_size < 1 || n_answers < 1 || n_paras < 1) return 0;
-  return scratch_of(batch, seq_len, hidden_size, n_answers, n_paras).bytes;
+  return scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)ceil_div(n_paras, kRankRows)).bytes;
 }
 
 int proqa_reader_loss_f16(const void* hidden, const int32_t* seq_lens_dev, const int32_t* cu_seqlens_dev, int batch,
@@ -790,8 +1034,8 @@ int proqa_reader_loss_f16(const void* hidden, const int32_t* seq_lens_dev, const
                           double p, uint64_t seed, int site, uint32_t call, void* logits_out, float* stats, float* loss_out,
                           void* ws, size_t ws_bytes, void* stream) {
   const char* who = "reader_loss";
-  const int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, dim, para_dtype, flags, seq_lens_dev,
-                             cu_seqlens_dev);
+  const int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxParas, dim, para_dtype, flags,
+                             seq_lens_dev, cu_seqlens_dev);
   if (rc != PROQA_OK) return rc;
   DropoutParams drop;
   if (!make_dropout_params(p, seed, site, call, &drop))
@@ -802,37 +1046,14 @@ int proqa_reader_loss_f16(const void* hidden, const int32_t* seq_lens_dev, const
   if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
       ((uintptr_t)logits_out & 3))
     return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / ws must be 16-byte aligned, logits 4-byte aligned", who);
-  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras);
+  const int n_rank = ceil_div(n_paras, kRankRows);
+  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_rank);
   if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
 
-  const hipStream_t st = as_stream(stream);
-  const Layout g = {(const int*)seq_lens_dev, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len};
-  const int n_blocks = ceil_div(seq_len, kRowsPerBlock), n_rank = ceil_div(n_paras, kRankRows);
-  float* span_part = (float*)((char*)ws + sc.span_part);
-  float* rank_part = (float*)((char*)ws + sc.rank_part);
-  float* x = (float*)((char*)ws + sc.x);
-  const dim3 row_grid((unsigned)((size_t)n_blocks * batch));
-  if (drop.thr > 0) {
-    hipLaunchKernelGGL(reader_loss_rows<true>, row_grid, dim3(kRowThreads), 0, st, (const _Float16*)hidden, g, n_blocks, hidden_size,
-                       (const _Float16*)qa_w, (const _Float16*)qa_b, drop, (_Float16*)logits_out, span_part);
-  } else {
-    hipLaunchKernelGGL(reader_loss_rows<false>, row_grid, dim3(kRowThreads), 0, st, (const _Float16*)hidden, g, n_blocks, hidden_size,
-                       (const _Float16*)qa_w, (const _Float16*)qa_b, drop, (_Float16*)logits_out, span_part);
-  }
-  PROQA_LAUNCH_CHECK();
-  if (para_dtype == PROQA_F32) {
-    hipLaunchKernelGGL(reader_loss_rank<true>, dim3((unsigned)n_rank), dim3(kRankThreads), 0, st, (const _Float16*)q, para_embed,
-                       (const int*)labels, n_paras, x, rank_part);
-  } else {
-    hipLaunchKernelGGL(reader_loss_rank<false>, dim3((unsigned)n_rank), dim3(kRankThreads), 0, st, (const _Float16*)q, para_embed,
-                       (const int*)labels, n_paras, x, rank_part);
-  }
-  PROQA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(reader_loss_finish, dim3(1), dim3(kFinishThreads), 0, st, g, batch, n_blocks, n_answers,
-                     (const int*)start_pos, (const int*)end_pos, n_rank, flags, (const _Float16*)logits_out, span_part,
-                     rank_part, x, stats, loss_out);
-  PROQA_LAUNCH_CHECK();
-  return PROQA_OK;
+  const Operands o = {hidden, Layout{(const int*)seq_lens_dev, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
+                      Questions{nullptr, nullptr, 1, batch, n_paras, n_rank}, hidden_size, qa_w, (const int*)start_pos,
+                      (const int*)end_pos, n_answers, q, para_embed, para_dtype, (const int*)labels, flags, drop};
+  return launch_forward(o, qa_b, logits_out, stats, loss_out, ws, sc, as_stream(stream));
 }
 
 int proqa_reader_loss_backward_f16(const void* hidden, const int32_t* seq_lens_dev, const int32_t* cu_seqlens_dev, int batch,
@@ -843,8 +1064,8 @@ int proqa_reader_loss_backward_f16(const void* hidden, const int32_t* seq_lens_d
                                    const float* stats, const float* grad_in, void* d_hidden, float* d_qa_w, float* d_qa_b,
                                    void* d_q, void* ws, size_t ws_bytes, void* stream) {
   const char* who = "reader_loss_backward";
-  const int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, dim, para_dtype, flags, seq_lens_dev,
-                             cu_seqlens_dev);
+  const int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxParas, dim, para_dtype, flags,
+                             seq_lens_dev, cu_seqlens_dev);
   if (rc != PROQA_OK) return rc;
   DropoutParams drop;
   if (!make_dropout_params(p, seed, site, call, &drop))
@@ -856,45 +1077,91 @@ int proqa_reader_loss_backward_f16(const void* hidden, const int32_t* seq_lens_d
       !aligned16(d_hidden) || ((uintptr_t)logits & 3))
     return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / d_hidden / ws must be 16-byte aligned, logits 4-byte aligned",
                 who);
-  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras);
+  const int n_rank = ceil_div(n_paras, kRankRows);
+  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_rank);
   if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
 
-  const hipStream_t st = as_stream(stream);
-  const Layout g = {(const int*)seq_lens_dev, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len};
-  const int n_blocks = ceil_div(seq_len, kRowsPerBlock), n_rank = ceil_div(n_paras, kRankRows);
-  float* w = (float*)((char*)ws + sc.w);
-  float* omega = (float*)((char*)ws + sc.omega);
-  float* slabs = (float*)((char*)ws + sc.slabs);
-  float* dq_slabs = (float*)((char*)ws + sc.dq_slabs);
-  hipLaunchKernelGGL(reader_loss_pairs, dim3((unsigned)ceil_div(batch, 4)), dim3(256), 0, st, g, batch, n_answers,
-                     (const int*)start_pos, (const int*)end_pos, (const _Float16*)q, para_embed, (int)(para_dtype == PROQA_F32),
-                     (const _Float16*)logits, stats, w, omega);
-  PROQA_LAUNCH_CHECK();
-  const dim3 row_grid((unsigned)((size_t)n_blocks * batch));
-  const size_t lds = (size_t)(kRowWaves / 2) * (2 * (size_t)hidden_size + 8) * sizeof(float);
-  if (drop.thr > 0) {
-    hipLaunchKernelGGL(reader_loss_bwd_rows<true>, row_grid, dim3(kRowThreads), lds, st, (const _Float16*)hidden, g, n_blocks, hidden_size,
-                       (const _Float16*)qa_w, n_answers, (const int*)start_pos, (const int*)end_pos, flags, drop,
-                       (const _Float16*)logits, stats, grad_in, (const float*)w, (const float*)omega, (_Float16*)d_hidden, slabs);
-  } else {
-    hipLaunchKernelGGL(reader_loss_bwd_rows<false>, row_grid, dim3(kRowThreads), lds, st, (const _Float16*)hidden, g, n_blocks, hidden_size,
-                       (const _Float16*)qa_w, n_answers, (const int*)start_pos, (const int*)end_pos, flags, drop,
-                       (const _Float16*)logits, stats, grad_in, (const float*)w, (const float*)omega, (_Float16*)d_hidden, slabs);
-  }
-  PROQA_LAUNCH_CHECK();
-  if (para_dtype == PROQA_F32) {
-    hipLaunchKernelGGL(reader_loss_bwd_rank<true>, dim3((unsigned)n_rank), dim3(kRankThreads), 0, st, (const _Float16*)q,
-                       para_embed, (const int*)labels, n_paras, batch, stats, grad_in, (const float*)omega, dq_slabs);
-  } else {
-    hipLaunchKernelGGL(reader_loss_bwd_rank<false>, dim3((unsigned)n_rank), dim3(kRankThreads), 0, st, (const _Float16*)q,
-                       para_embed, (const int*)labels, n_paras, batch, stats, grad_in, (const float*)omega, dq_slabs);
-  }
-  PROQA_LAUNCH_CHECK();
-  const int n_out = 2 * hidden_size + 2 + PROQA_EMBED_DIM;
-  hipLaunchKernelGGL(reader_loss_bwd_sum, dim3((unsigned)ceil_div(n_out, 256)), dim3(256), 0, st, (const float*)slabs,
-                     (long long)batch * n_blocks, hidden_size, (const float*)dq_slabs, n_rank, d_qa_w, d_qa_b, (_Float16*)d_q);
-  PROQA_LAUNCH_CHECK();
-  return PROQA_OK;
+  const Operands o = {hidden, Layout{(const int*)seq_lens_dev, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
+                      Questions{nullptr, nullptr, 1, batch, n_paras, n_rank}, hidden_size, qa_w, (const int*)start_pos,
+                      (const int*)end_pos, n_answers, q, para_embed, para_dtype, (const int*)labels, flags, drop};
+  return launch_backward(o, logits, stats, grad_in, d_hidden, d_qa_w, d_qa_b, d_q, ws, sc, as_stream(stream));
+}
+
+size_t proqa_reader_loss_multi_workspace_bytes(int n_questions, int batch, int seq_len, int hidden_size, int n_answers,
+                                               int n_paras, int max_paras) {
+  if (n_questions < 1 || batch < 1 || seq_len < 1 || hidden_size < 1 || n_answers < 1 || n_paras < 1 || max_paras < 1) return 0;
+  return scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_questions * ceil_div(max_paras, kRankRows)).bytes;
+}
+
+int proqa_reader_loss_multi_f16(const void* hidden, const int32_t* cu_seqlens_dev, int batch, int seq_len, int hidden_size,
+                                const int32_t* para_offset_dev, const void* qa_w, const void* qa_b, const int32_t* start_pos,
+                                const int32_t* end_pos, int n_answers, const void* q, const void* para_embed, int para_dtype,
+                                const int32_t* labels, int n_paras, int dim, const int32_t* question_seq_dev,
+                                const int32_t* question_para_dev, int n_questions, int max_seqs, int max_paras,
+                                const int32_t* question_seq_host, const int32_t* question_para_host, int flags, double p,
+                                uint64_t seed, int site, uint32_t call, void* logits_out, float* stats, float* loss_out,
+                                void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "reader_loss_multi";
+  int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxPackParas, dim, para_dtype, flags, nullptr,
+                       &kPackedOnly);   // (a NULL cu_seqlens is reported with the other NULLs below)
+  if (rc != PROQA_OK) return rc;
+  rc = check_questions(who, n_questions, batch, n_paras, max_seqs, max_paras, question_seq_host, question_para_host);
+  if (rc != PROQA_OK) return rc;
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "%s: p=%g must be in [0, 1) and site=%d in [0, 255]", who, p, site);
+  if (!hidden || !cu_seqlens_dev || !para_offset_dev || !qa_w || !qa_b || !start_pos || !end_pos || !q || !para_embed || !labels ||
+      !question_seq_dev || !question_para_dev || !logits_out || !stats || !loss_out || !ws)
+    return fail(PROQA_EINVAL, "%s: NULL argument", who);
+  if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
+      ((uintptr_t)logits_out & 3))
+    return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / ws must be 16-byte aligned, logits 4-byte aligned", who);
+  const int rank_blocks = ceil_div(max_paras, kRankRows);
+  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_questions * rank_blocks);
+  if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
+
+  const Operands o = {hidden, Layout{nullptr, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
+                      Questions{(const int*)question_seq_dev, (const int*)question_para_dev, n_questions, batch, n_paras, rank_blocks},
+                      hidden_size, qa_w, (const int*)start_pos, (const int*)end_pos, n_answers, q, para_embed, para_dtype,
+                      (const int*)labels, flags, drop};
+  return launch_forward(o, qa_b, logits_out, stats, loss_out, ws, sc, as_stream(stream));
+}
+
+int proqa_reader_loss_multi_backward_f16(const void* hidden, const int32_t* cu_seqlens_dev, int batch, int seq_len,
+                                         int hidden_size, const int32_t* para_offset_dev, const void* qa_w,
+                                         const int32_t* start_pos, const int32_t* end_pos, int n_answers, const void* q,
+                                         const void* para_embed, int para_dtype, const int32_t* labels, int n_paras, int dim,
+                                         const int32_t* question_seq_dev, const int32_t* question_para_dev, int n_questions,
+                                         int max_seqs, int max_paras, const int32_t* question_seq_host,
+                                         const int32_t* question_para_host, int flags, double p, uint64_t seed, int site,
+                                         uint32_t call, const void* logits, const float* stats, const float* grad_in,
+                                         void* d_hidden, float* d_qa_w, float* d_qa_b, void* d_q, void* ws, size_t ws_bytes,
+                                         void* stream) {
+  const char* who = "reader_loss_multi_backward";
+  int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxPackParas, dim, para_dtype, flags, nullptr,
+                       &kPackedOnly);
+  if (rc != PROQA_OK) return rc;
+  rc = check_questions(who, n_questions, batch, n_paras, max_seqs, max_paras, question_seq_host, question_para_host);
+  if (rc != PROQA_OK) return rc;
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "%s: p=%g must be in [0, 1) and site=%d in [0, 255]", who, p, site);
+  if (!hidden || !cu_seqlens_dev || !para_offset_dev || !qa_w || !start_pos || !end_pos || !q || !para_embed || !labels ||
+      !question_seq_dev || !question_para_dev || !logits || !stats || !grad_in || !d_hidden || !d_qa_w || !d_qa_b || !d_q || !ws)
+    return fail(PROQA_EINVAL, "%s: NULL argument", who);
+  if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
+      !aligned16(d_hidden) || ((uintptr_t)logits & 3))
+    return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / d_hidden / ws must be 16-byte aligned, logits 4-byte aligned",
+                who);
+  const int rank_blocks = ceil_div(max_paras, kRankRows);
+  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_questions * rank_blocks);
+  if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
+
+  const Operands o = {hidden, Layout{nullptr, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
+                      Questions{(const int*)question_seq_dev, (const int*)question_para_dev, n_questions, batch, n_paras, rank_blocks},
+                      hidden_size, qa_w, (const int*)start_pos, (const int*)end_pos, n_answers, q, para_embed, para_dtype,
+                      (const int*)labels, flags, drop};
+  return launch_backward(o, logits, stats, grad_in, d_hidden, d_qa_w, d_qa_b, d_q, ws, sc, as_stream(stream));
 }
 
 }  // extern "C"

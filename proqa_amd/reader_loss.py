@@ -6,9 +6,13 @@ over para_embed and the marginal over the answer positions are proqa_reader_loss
 proqa_reader_loss_backward_f16 (four launches).  No Python loop, no nonzero(), no device-to-host copy, and the [T, 2]
 logit gradient is never stored: it lives in fp32 registers, so a loss scale of 2^16 does not overflow it.
 
+reader_loss_multi is the same objective over the passages of Q questions in ONE call (proqa_reader_loss_multi_f16: the
+same seven kernels with a question dimension); each question's values carry the bits reader_loss gives for it alone.
+
 torch computes nothing here: it owns the memory and the stream, casts the fp32 masters to fp16 (as trainable.py does) and
 the sampler's int64 positions / labels to the int32 the kernels take, and autograd carries the four gradients.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -180,3 +184,148 @@ def reader_loss(hidden, qa_weight, qa_bias, q, para_embed, top5000_labels, start
     q0 = (q[0] if q.dim() == 2 else q).contiguous()
     out = _ReaderLoss.apply(hidden.contiguous(), qa_weight, qa_bias, q0, geo)
     return {"loss": out[0], "joint": out[1].detach(), "early": out[2].detach()}
+
+
+# ---- several questions in one call -------------------------------------------------------------------------------------------
+
+class _MultiGeometry(_Geometry):
+    """_Geometry of a pack of questions: the packed layout, and the CSR arrays that cut it into questions."""
+
+    def __init__(self, hidden, n_questions, cu_seqlens, question_seq, question_para, max_seqs, max_paras, *rest):
+        super().__init__(hidden, cu_seqlens, None, *rest)
+        dev = hidden.device
+        self.n_questions = int(n_questions)
+        self.host = []
+        counts = []
+        for name, csr, given in (("question_seq", question_seq, max_seqs), ("question_para", question_para, max_paras)):
+            if torch.is_tensor(csr):
+                if given is None:
+                    raise ValueError(f"reader_loss_multi: {name} on the device needs max_seqs= and max_paras= (the largest "
+                                     "per-question counts); a host list carries them itself")
+                self.host.append(None)
+                counts.append(int(given))
+            else:
+                arr = np.ascontiguousarray(np.asarray(list(csr), dtype=np.int64).astype(np.int32))
+                if arr.ndim != 1 or arr.size < 2:
+                    raise ValueError(f"reader_loss_multi: {name} must hold n_questions + 1 offsets")
+                self.host.append(arr)
+                counts.append(int(np.diff(arr).max()) if given is None else int(given))
+                csr = torch.from_numpy(arr).pin_memory().to(dev, non_blocking=True)     # (an upload the host does not wait for)
+            csr = _i32(csr, dev, name).reshape(-1)
+            if csr.numel() != self.n_questions + 1:
+                raise ValueError(f"reader_loss_multi: {name} must be [{self.n_questions + 1}] for q [{self.n_questions}, "
+                                 f"{EMBED_DIM}], got {csr.numel()}")
+            setattr(self, name, csr)
+        if (self.host[0] is None) != (self.host[1] is None):
+            raise ValueError("reader_loss_multi: question_seq and question_para must both be host lists or both be tensors")
+        self.max_seqs, self.max_paras = counts
+
+    def layout(self):
+        return (self.cu.data_ptr(), self.batch, self.seq_len, self.hidden_size, self.para_offset.data_ptr())
+
+    def objective(self, q):
+        host = [a.ctypes.data if a is not None else None for a in self.host]
+        return (self.start.data_ptr(), self.end.data_ptr(), self.n_answers, q.data_ptr(), self.para.data_ptr(), self.para_dtype,
+                self.labels.data_ptr(), self.n_paras, self.dim, self.question_seq.data_ptr(), self.question_para.data_ptr(),
+                self.n_questions, self.max_seqs, self.max_paras, host[0], host[1], self.flags, self.p, self.seed,
+                READER_HEAD_SITE, self.call)
+
+    def workspace(self, lib, device):
+        need = lib.proqa_reader_loss_multi_workspace_bytes(self.n_questions, self.batch, self.seq_len, self.hidden_size,
+                                                           self.n_answers, self.n_paras, self.max_paras)
+        return _workspace(device, need)
+
+
+def reader_loss_multi_forward(hidden, w16, b16, q, geo):
+    """-> (loss_out fp32 [Q, 3]; logits fp16 [T, 2]; stats fp32 [8 Q + 2 B], the single-question layout question after
+    question); no autograd"""
+    lib = _lib.load()
+    dev = hidden.device
+    logits = torch.empty((hidden.shape[0], 2), dtype=torch.float16, device=dev)
+    stats = torch.empty(8 * geo.n_questions + 2 * max(geo.batch, 0), dtype=torch.float32, device=dev)
+    loss_out = torch.empty((geo.n_questions, 3), dtype=torch.float32, device=dev)
+    ws = geo.workspace(lib, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.proqa_reader_loss_multi_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), b16.data_ptr(),
+                                                   *geo.objective(q), logits.data_ptr(), stats.data_ptr(), loss_out.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+    return loss_out, logits, stats
+
+
+def reader_loss_multi_backward(hidden, w16, q, geo, logits, stats, grad_in):
+    """grad_in: fp32 [Q] on the device -> (d_hidden fp16 [T, H], d_qa_w fp32 [2, H], d_qa_b fp32 [2], d_q fp16 [Q, 128])"""
+    lib = _lib.load()
+    dev = hidden.device
+    d_hidden = torch.empty_like(hidden)
+    d_w = torch.empty((2, geo.hidden_size), dtype=torch.float32, device=dev)
+    d_b = torch.empty(2, dtype=torch.float32, device=dev)
+    d_q = torch.empty((geo.n_questions, EMBED_DIM), dtype=torch.float16, device=dev)
+    ws = geo.workspace(lib, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.proqa_reader_loss_multi_backward_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), *geo.objective(q),
+                                                            logits.data_ptr(), stats.data_ptr(), grad_in.data_ptr(),
+                                                            d_hidden.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), d_q.data_ptr(),
+                                                            ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+    return d_hidden, d_w, d_b, d_q
+
+
+class _ReaderLossMulti(torch.autograd.Function):
+    """(hidden fp16 [T, H], qa_weight, qa_bias fp32 masters, q fp16 [Q, 128]) -> fp32 [Q, 3] = (loss, joint, early) per
+    question; only column 0 is differentiated."""
+
+    @staticmethod
+    def forward(ctx, hidden, qa_weight, qa_bias, q, geo):
+        w16, b16 = qa_weight.half().contiguous(), qa_bias.half().contiguous()
+        loss_out, logits, stats = reader_loss_multi_forward(hidden, w16, b16, q, geo)
+        ctx.save_for_backward(hidden, w16, q, logits, stats)
+        ctx.geo = geo
+        return loss_out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        hidden, w16, q, logits, stats = ctx.saved_tensors
+        g = grad_out[:, 0].to(torch.float32).contiguous()     # the gradients of the questions' total losses
+        d_hidden, d_w, d_b, d_q = reader_loss_multi_backward(hidden, w16, q, ctx.geo, logits, stats, g)
+        return d_hidden, d_w, d_b, d_q, None
+
+
+def reader_loss_multi(hidden, qa_weight, qa_bias, q, para_embed, top5000_labels, start_positions, end_positions, para_offset, *,
+                      cu_seqlens, question_seq, question_para, shared_norm=True, early=True, qa_drop=0.0, dropout_state=None,
+                      max_seq_len=None, max_seqs=None, max_paras=None):
+    """reader_loss for the passages of Q questions in one call (proqa_reader_loss_multi_f16): one autograd node, three
+    launches forward and four backward whatever Q is, no host wait.
+
+    hidden            packed fp16 [T, H] with cu_seqlens (int [B + 1]) over the sequences of ALL questions, question after
+                      question; start_positions / end_positions [B, A] and para_offset [B] likewise
+    q                 fp16 [Q, 128], one question embedding per question
+    para_embed        [P, 128] float16 or float32 and top5000_labels [P]: every question's rows, question after question; the
+                      first B_i rows of question i belong to its sequences
+    question_seq      [Q + 1] offsets into the sequences, question_para [Q + 1] offsets into the rows of para_embed: host
+                      lists (they are checked, and uploaded with the other integer tensors) or int device tensors (then
+                      max_seqs / max_paras, the largest per-question counts, must be given and nothing can be checked: the
+                      kernels clamp)
+    qa_weight, qa_bias, shared_norm, early, qa_drop, dropout_state, max_seq_len: as reader_loss, one value for the call.  With
+    qa_drop > 0 the mask coordinate is the packed row of the whole pack.
+
+    -> {"losses": fp32 [Q] with gradients w.r.t. hidden, q, qa_weight and qa_bias, "joint", "early": fp32 [Q], detached}.
+    Each question's values carry the bits reader_loss gives for the question alone (qa_drop == 0); the gradients of qa_weight /
+    qa_bias are the questions' gradients added in ascending order."""
+    if not torch.is_tensor(hidden) or not hidden.is_cuda or hidden.dtype != torch.float16:
+        raise ValueError("reader_loss_multi: hidden must be a float16 CUDA tensor (there is no CPU path)")
+    if not q.is_cuda or q.dtype != torch.float16 or q.dim() != 2 or q.shape[-1] != EMBED_DIM or q.shape[0] < 1:
+        raise ValueError(f"reader_loss_multi: q must be a float16 CUDA tensor [Q, {EMBED_DIM}] with Q >= 1, got {q.dtype} "
+                         f"{tuple(q.shape)}")
+    if qa_weight.dtype != torch.float32 or qa_bias.dtype != torch.float32:
+        raise ValueError("reader_loss_multi: qa_weight / qa_bias are the fp32 masters; they are cast to fp16 inside")
+    if tuple(qa_weight.shape) != (2, hidden.shape[-1]) or tuple(qa_bias.shape) != (2,):
+        raise ValueError(f"reader_loss_multi: qa_weight must be [2, {hidden.shape[-1]}] and qa_bias [2]")
+    if not 0.0 <= float(qa_drop) <= 0.9:
+        raise ValueError(f"reader_loss_multi: qa_drop={qa_drop!r} must be in [0, 0.9]")
+    if cu_seqlens is None:
+        raise ValueError("reader_loss_multi: the packed layout only (cu_seqlens)")
+    geo = _MultiGeometry(hidden.contiguous(), q.shape[0], cu_seqlens, question_seq, question_para, max_seqs, max_paras,
+                         para_offset, start_positions, end_positions, para_embed, top5000_labels, shared_norm, early, qa_drop,
+                         dropout_state, max_seq_len)
+    out = _ReaderLossMulti.apply(hidden.contiguous(), qa_weight, qa_bias, q.contiguous(), geo)
+    return {"losses": out[:, 0], "joint": out[:, 1].detach(), "early": out[:, 2].detach()}

@@ -20,6 +20,10 @@ searches (the model is back in train() after it, as after the reference's predic
 Beyond the reference (proqa_amd/checkpoint.py): --save-state, --stop-after-updates, --resume and
 --digest-every as in pretrain_retriever.py; the state also holds the sampler's permutation, the failed and update steps
 and the RNG states, so a run resumed inside an epoch visits the questions the uninterrupted run visits.
+--questions-per-pass Q (default 1: the loop above): within an accumulation window no weight changes, so up to Q of its
+questions are drawn from the sampler one after another, as before, and then run through ONE forward (TrainableReader on
+the list: one pass per tower, one fused loss call) and one backward; pass_schedule() is the grouping rule.  The optimisation
+step is the one of the questions run one after another; with --gradient_accumulation_steps 1 every pass holds one question.
 """
 import argparse
 import json
@@ -112,6 +116,9 @@ def build_parser():
     p.add_argument("--candidates", default="", type=str)
     p.add_argument("--deterministic", action="store_true", default=False,
                    help="sum the word-embedding gradients in a fixed order: a run reproduces bit for bit")
+    p.add_argument("--questions-per-pass", default=1, type=int,
+                   help="questions of one accumulation window that share a tower pass and one fused loss call (1: one question "
+                        "per pass); the optimisation step is the same, so it only pays with --gradient_accumulation_steps > 1")
     from .config import STATE_FLAGS, add_flags
     return add_flags(p, STATE_FLAGS)       # --save-state, --stop-after-updates, --resume, --digest-every
 
@@ -151,6 +158,8 @@ def check_args(args):
                          "kernels (DESIGN.md section 3h)")
     if args.gradient_accumulation_steps < 1:
         raise ValueError(f"Invalid gradient_accumulation_steps parameter: {args.gradient_accumulation_steps}, should be >= 1")
+    if args.questions_per_pass < 1:
+        raise ValueError(f"Invalid questions_per_pass parameter: {args.questions_per_pass}, should be >= 1")
     per_question = int(args.train_batch_size / args.accumulate_gradients)
     if not 1 <= per_question <= MAX_HEAD:
         raise ValueError(f"--train_batch_size {args.train_batch_size} / --accumulate_gradients {args.accumulate_gradients}: "
@@ -168,6 +177,51 @@ def update_schedule(n_batches, gradient_accumulation_steps, failed=()):
     that slot does not happen: the gradients go on accumulating until the next slot."""
     failed = set(failed)
     return [b for b in range(1, n_batches + 1) if b not in failed and is_update_step(b, gradient_accumulation_steps)]
+
+
+def closes_pass(n_in_pass, batch_step, gradient_accumulation_steps, questions_per_pass):
+    """Whether the pass is run now, asked when the question of `batch_step` (retrieved, not failed) has just joined it as its
+    n_in_pass-th: it is full, or the question sits in an update slot -- the optimizer step needs every gradient of its
+    window, and the next question is retrieved with the new weights."""
+    return n_in_pass >= questions_per_pass or is_update_step(batch_step, gradient_accumulation_steps)
+
+
+def pass_schedule(n_batches, gradient_accumulation_steps, questions_per_pass, failed=(), first=1):
+    """[[batch_step of every question of the pass]] over ONE epoch of n_batches questions whose batch steps are first ..
+    first + n_batches - 1; `failed` as update_schedule.  A failed retrieval joins no pass and closes none: in an update slot it
+    leaves the window open, and the pass with it.  What is open when the epoch ends is run as the epoch's last pass (the
+    evaluation that follows reads the weights, not the gradients; the window stays open into the next epoch)."""
+    failed = set(failed)
+    passes, open_pass = [], []
+    for b in range(first, first + n_batches):
+        if b in failed:
+            continue
+        open_pass.append(b)
+        if closes_pass(len(open_pass), b, gradient_accumulation_steps, questions_per_pass):
+            passes.append(open_pass)
+            open_pass = []
+    if open_pass:
+        passes.append(open_pass)
+    return passes
+
+
+def reader_fingerprint_extra(args):
+    """The reader command's own fields of the resume fingerprint.  questions_per_pass is a field only when it is not 1, so
+    that the state files of one-question passes keep their fingerprint."""
+    extra = {"qa_drop": float(args.qa_drop), "shared_norm": bool(args.shared_norm), "drop_early": bool(args.drop_early),
+             "fix_para_encoder": bool(args.fix_para_encoder)}
+    if int(getattr(args, "questions_per_pass", 1)) != 1:
+        extra["questions_per_pass"] = int(args.questions_per_pass)
+    return extra
+
+
+def check_questions_per_pass(saved_fingerprint, questions_per_pass):
+    """SystemExit when the state file was written at another --questions-per-pass (a state file without the field was
+    written at 1, where check_fingerprint would pass over the field)."""
+    was = int(saved_fingerprint.get("questions_per_pass", 1))
+    if was != int(questions_per_pass):
+        raise SystemExit(f"--resume: the state file was written by a different run: field 'questions_per_pass' is "
+                         f"{int(questions_per_pass)!r} now, was {was!r} when the state was saved")
 
 
 def initial_state_dict(cfg, bert_weights):
@@ -228,13 +282,13 @@ def main(argv=None):
 
         cfg, p_hidden, p_attention = load_model_config(args.bert_model_name)
         resume = None
-        fp_extra = {"qa_drop": float(args.qa_drop), "shared_norm": bool(args.shared_norm), "drop_early": bool(args.drop_early),
-                    "fix_para_encoder": bool(args.fix_para_encoder)}
+        fp_extra = reader_fingerprint_extra(args)
         fp = checkpoint.fingerprint("train_reader.py", args, train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden,
                                     attention_probs_dropout_prob=p_attention, extra=fp_extra)
         if args.resume:
             # the flags first: a run of other settings is refused before the data and the model are built
             resume = checkpoint.read_state(checkpoint.resolve_state_path(args.resume))
+            check_questions_per_pass(resume["trainer"]["fingerprint"], args.questions_per_pass)
             checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp, fields=tuple(fp))
         tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
         logger.info("Loading para db and pretrained index ...")
@@ -307,6 +361,12 @@ def main(argv=None):
         meter = _Losses()
         evals, failed_per_epoch, failed_steps, update_steps = [], [], [], []
         G = args.gradient_accumulation_steps
+        Q = args.questions_per_pass
+        n_passes = 0
+        if Q > 1:
+            logger.info("--questions-per-pass %d: the questions of an accumulation window share tower passes and one fused "
+                        "loss call%s", Q, "" if G > 1 else "; with --gradient_accumulation_steps 1 every question closes its "
+                        "window, so every pass holds one question")
         logger.info("Start training....")
         model.train()
         train_dataloader = OnlineSampler(args.raw_train_data, tokenizer, args.max_query_length, args.max_seq_length, para_db,
@@ -338,6 +398,7 @@ def main(argv=None):
             digests.entries = [dict(e) for e in tr["state_digests"]]
             failed_steps, update_steps = list(saved["failed_steps"]), list(saved["update_steps"])
             failed_per_epoch, resumed_failed = list(saved["failed_per_epoch"]), saved["failed_retrieval"]
+            n_passes = int(saved.get("passes", 0))
             start_epoch, start_position, epoch_started = tr["epoch"], tr["position"], tr["epoch_started"]
             if stop_training and not epoch_started:
                 start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
@@ -358,12 +419,27 @@ def main(argv=None):
             reader_state = {"failed_steps": list(failed_steps), "update_steps": list(update_steps),
                             "failed_per_epoch": list(failed_per_epoch), "failed_retrieval": int(failed_so_far),
                             "permutation": train_dataloader.permutation()}
+            if Q != 1:
+                reader_state["passes"] = int(n_passes)
             ckpt.snapshot(state_path, dict(checkpoint.trainer_state(
                 fingerprint=fp, global_step=global_step, batch_step=batch_step, epoch=next_epoch, position=next_position,
                 epoch_started=started, best=best_em, wait_step=wait_step, stop_training=stop_training,
                 dropout=checkpoint.dropout_states(model), losses=meter.values, loss_steps=meter.steps, evals=evals,
                 param_groups=[{"lr": g["lr"], "weight_decay": g["weight_decay"]} for g in optimizer.param_groups],
                 state_digests=digests.entries, reader=reader_state), rng=checkpoint.rng_states()))
+
+        def run_pass(batches):
+            """forward + backward of the questions of one pass (Q > 1): one forward on the list; every question's loss is
+            divided by G and their sum goes through the loss scale"""
+            for b in batches:
+                if ON_BATCH is not None:
+                    ON_BATCH(b)
+            losses = model([b["net_input"] for b in batches])["losses"]
+            if G > 1:
+                losses = losses / G
+            optimizer.scale_loss(losses.sum()).backward()
+            for i in range(len(batches)):
+                meter.add(losses[i].detach(), global_step)
 
         t_start = time.perf_counter()
         for epoch in range(start_epoch, int(args.num_train_epochs)):
@@ -372,6 +448,7 @@ def main(argv=None):
                 train_dataloader.shuffle()
             failed_retrieval = resumed_failed if resumed_here else 0
             position = start_position if resumed_here else 0
+            open_pass = []
             for batch in train_dataloader.load(model.retriever, k=args.train_batch_size, **({"start": position} if position else {})):
                 batch_step += 1
                 position += 1
@@ -379,14 +456,22 @@ def main(argv=None):
                     failed_retrieval += 1
                     failed_steps.append(batch_step)
                     continue
-                if ON_BATCH is not None:
-                    ON_BATCH(batch)
-                outputs = model(batch["net_input"])
-                loss = outputs["loss"]
-                if G > 1:
-                    loss = loss / G
-                optimizer.scale_loss(loss).backward()
-                meter.add(loss.detach(), global_step)
+                if Q > 1:
+                    open_pass.append(batch)
+                    if not closes_pass(len(open_pass), batch_step, G, Q):
+                        continue
+                    run_pass(open_pass)
+                    open_pass = []
+                else:
+                    if ON_BATCH is not None:
+                        ON_BATCH(batch)
+                    outputs = model(batch["net_input"])
+                    loss = outputs["loss"]
+                    if G > 1:
+                        loss = loss / G
+                    optimizer.scale_loss(loss).backward()
+                    meter.add(loss.detach(), global_step)
+                n_passes += 1
                 pending_grad = True
 
                 if is_update_step(batch_step, G):
@@ -424,6 +509,11 @@ def main(argv=None):
                             break
             if stopped_early:
                 break
+            if open_pass:       # the epoch ended inside a window: its last questions are a pass of their own
+                run_pass(open_pass)
+                open_pass = []
+                n_passes += 1
+                pending_grad = True
 
             logger.info(f"Failed retrieval: {failed_retrieval}/{len(train_dataloader)} ...")
             failed_per_epoch.append(failed_retrieval)
@@ -460,7 +550,8 @@ def main(argv=None):
         stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
                      failed_retrieval=failed_per_epoch, failed_steps=failed_steps, update_steps=update_steps, skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"],
                      seconds=seconds, best_em=best_em, output_dir=args.output_dir, deterministic=bool(args.deterministic),
-                     sampler_seconds=dict(train_dataloader.seconds), sampler_transfers=dict(train_dataloader.transfers))
+                     sampler_seconds=dict(train_dataloader.seconds), sampler_transfers=dict(train_dataloader.transfers),
+                     questions_per_pass=Q, passes=n_passes)
         if args.stop_after_updates > 0:
             stats["stopped_early"] = stopped_early
         if args.digest_every > 0:

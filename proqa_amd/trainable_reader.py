@@ -11,6 +11,11 @@ proqa_embed_layernorm_typed_varlen_f16 and its backward), the question tower on 
 identical rows and uses q[0]), and proqa_amd.reader_loss on the packed hidden states.  One host round trip per tower pass
 (the sizes and the checks of the masks), none in the loss.
 
+forward([net_input, ...]) in train() mode is ONE pass over several questions: one reader-tower pass over all their sequences,
+one question-tower pass over row 0 of every question's input_ids_q, and one reader_loss_multi call.  Within an accumulation
+window no weight changes, so it is the optimisation step of the questions run one after another; -> {"loss": the sum,
+"losses", "joint", "early": per question}.
+
 forward(net_input) in eval() mode returns the reference's keys (start_logits, end_logits, rank_logits) for its dev loop.  It
 runs the INFERENCE class (proqa_amd.reader.BertReader: the fused encoder and proqa_reader_span_f16) over an fp16 copy of the
 parameters, taken at the first forward after eval() is entered, so a dev score during training is the score --do_predict
@@ -23,12 +28,13 @@ two rates inside the fused operators, qa_drop inside the loss kernels (site 255)
 import torch
 
 from .reader import BertReader
-from .reader_loss import reader_loss
+from .reader_loss import reader_loss, reader_loss_multi
 from .retriever import config_from_dict, tower_keys
 from .trainable import TrainableRetriever, _Node, _parameter_shapes, run_tower
 from .trainable import state_dict_keys as _retriever_keys
 
-CALLS_PER_FORWARD = 3      # dropout `call`s one train() forward takes: reader tower, question tower, head
+CALLS_PER_FORWARD = 3      # dropout `call`s one train() forward takes: reader tower, question tower, head -- per PASS: a
+                           # list of questions takes the same three as one question
 
 
 def state_dict_keys(config):
@@ -61,7 +67,7 @@ def _check_rate(name, rate):
 
 class TrainableReader(torch.nn.Module):
     """BertRetrieveQA with gradients.  forward(net_input) takes the sampler's net_input; train(): {"loss", "joint",
-    "early"}, eval(): {"start_logits", "end_logits", "rank_logits"}."""
+    "early"}, eval(): {"start_logits", "end_logits", "rank_logits"}; train() also takes a list of net_inputs (one pass)."""
 
     def __init__(self, config, device=None, *, shared_norm=True, drop_early=False, qa_drop=0.0, hidden_dropout_prob=0.0,
                  attention_probs_dropout_prob=0.0, dropout_seed=None, separate=False, add_select=False,
@@ -177,6 +183,8 @@ class TrainableReader(torch.nn.Module):
         return super().train(mode)
 
     def forward(self, net_input):
+        if isinstance(net_input, (list, tuple)):
+            return self._forward_questions(list(net_input))
         ids = net_input["input_ids"]
         if not ids.is_cuda:
             raise RuntimeError("TrainableReader expects CUDA tensors (the reference feeds move_to_cuda(batch))")
@@ -208,6 +216,63 @@ class TrainableReader(torch.nn.Module):
                            net_input["top5000_labels"], net_input["start_positions"], net_input["end_positions"],
                            geometry["para_offset"], cu_seqlens=cu, shared_norm=self.shared_norm, early=not self.drop_early,
                            qa_drop=p_qa, dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
+
+    def _forward_questions(self, batches):
+        """train() mode, a list of the sampler's net_input dicts: the questions of one pass.  One reader-tower pass over all
+        sequences (padded on the device to the widest batch, packed by run_tower), one question-tower pass over row 0 of
+        every question's input_ids_q, one reader_loss_multi call; two host round trips and one (seed, call) triple for the
+        pass.  -> {"loss": losses.sum(), "losses" fp32 [Q] (with gradients), "joint", "early" fp32 [Q]}.  A list of one dict
+        gives the bits of the dict route."""
+        if not self.training:
+            raise ValueError("TrainableReader: a list of questions is a training pass; eval() takes one net_input dict")
+        if not batches:
+            raise ValueError("TrainableReader: an empty list of questions")
+        for x in batches:
+            ids = x["input_ids"]
+            if not ids.is_cuda:
+                raise RuntimeError("TrainableReader expects CUDA tensors (the reference feeds move_to_cuda(batch))")
+            if ids.shape[0] == 0:
+                raise ValueError("TrainableReader: an empty batch")
+            if x["paragraph_mask"].shape != ids.shape:
+                raise ValueError(f"paragraph_mask {tuple(x['paragraph_mask'].shape)} must have the shape of input_ids "
+                                 f"{tuple(ids.shape)}")
+            if x["para_embed"].dtype != batches[0]["para_embed"].dtype:
+                raise ValueError("TrainableReader: the questions of a pass must share para_embed's dtype")
+
+        def stacked(key, rows=None, fill=0):      # the questions' [n, width] tensors under each other, padded on the right
+            parts = [x[key] if rows is None else x[key][:rows] for x in batches]
+            width = max(t.shape[1] for t in parts)
+            return torch.cat([torch.nn.functional.pad(t, (0, width - t.shape[1]), value=fill) for t in parts], 0)
+
+        ids, pmask = stacked("input_ids"), stacked("paragraph_mask").to(torch.bool)
+        p_hid, p_att, p_qa = self.hidden_dropout_prob, self.attention_probs_dropout_prob, self.qa_drop
+        seed, call = self._dropout_seed, self._dropout_call
+        if p_hid > 0 or p_att > 0 or p_qa > 0:
+            self._dropout_call = (call + CALLS_PER_FORWARD) & 0xFFFFFF
+        geometry = {}
+
+        def paragraph_probe(lens):
+            geometry["para_offset"], bad = _paragraph_geometry(pmask, lens)
+            return bad, _PARAGRAPH_MESSAGE
+
+        hidden, cu, lens, max_len = run_tower(self._flat, "bert", self.config, ids, stacked("input_mask"),
+                                              type_ids=stacked("segment_ids"), drop=(p_hid, p_att, seed, call),
+                                              probe_extra=paragraph_probe, deterministic=self.deterministic)
+        q = run_tower(self.retriever._flat, "bert_q", self.config, stacked("input_ids_q", rows=1),
+                      stacked("input_mask_q", rows=1), proj="proj_q", drop=(p_hid, p_att, seed, (call + 1) & 0xFFFFFF),
+                      deterministic=self.deterministic)
+        question_seq, question_para = [0], [0]
+        for x in batches:
+            question_seq.append(question_seq[-1] + x["input_ids"].shape[0])
+            question_para.append(question_para[-1] + x["para_embed"].shape[0])
+        out = reader_loss_multi(hidden, self._flat["qa_outputs.weight"], self._flat["qa_outputs.bias"], q,
+                                torch.cat([x["para_embed"] for x in batches], 0),
+                                torch.cat([x["top5000_labels"].reshape(-1) for x in batches]),
+                                stacked("start_positions", fill=-1), stacked("end_positions", fill=-1), geometry["para_offset"],
+                                cu_seqlens=cu, question_seq=question_seq, question_para=question_para,
+                                shared_norm=self.shared_norm, early=not self.drop_early, qa_drop=p_qa,
+                                dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
+        return {"loss": out["losses"].sum(), "losses": out["losses"], "joint": out["joint"], "early": out["early"]}
 
     def inference_reader(self):
         """The BertReader that eval() forwards run: the inference class over an fp16 copy of the parameters, taken at the
