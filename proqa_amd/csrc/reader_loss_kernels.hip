@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <initializer_list>
 
 #include "common.h"
 #include "dropout_rng.h"
@@ -1015,6 +1016,53 @@ int launch_backward(const Operands& o, const void* logits, const float* stats, c
   return PROQA_OK;
 }
 
+// the questions of a multi call, as its entry points receive them
+struct QuestionArgs {
+  const int32_t *seq_dev, *para_dev;
+  int n, max_seqs, max_paras;
+  const int32_t *seq_host, *para_host;
+};
+
+// What all four entry points do before they launch: the checks, in one order and one wording, then the operands and the
+// regions of the scratch.  questions == nullptr: one question that owns the whole batch, in either layout; otherwise the
+// packed layout (seq_lens_dev is NULL; a NULL cu_seqlens is reported with the other NULLs).  `own`: the entry's own pointers
+// that must not be NULL (qa_b and the outputs, or the saved tensors and the gradients).  logits is the forward's output or the
+// backward's input; d_hidden is NULL in a forward call.
+int prepare(const char* who, const void* hidden, const int32_t* seq_lens_dev, const int32_t* cu_seqlens_dev, int batch,
+            int seq_len, int hsize, const int32_t* para_offset_dev, const void* qa_w, const int32_t* start_pos,
+            const int32_t* end_pos, int n_answers, const void* q, const void* para_embed, int para_dtype, const int32_t* labels,
+            int n_paras, int dim, const QuestionArgs* questions, int flags, double p, uint64_t seed, int site, uint32_t call,
+            std::initializer_list<const void*> own, const void* logits, const void* d_hidden, const void* ws, size_t ws_bytes,
+            Operands* o, Scratch* sc) {
+  const QuestionArgs* qa = questions;
+  int rc = check_sizes(who, batch, seq_len, hsize, n_answers, n_paras, qa ? kMaxPackParas : kMaxParas, dim, para_dtype, flags,
+                       seq_lens_dev, qa ? (const void*)&kPackedOnly : cu_seqlens_dev);
+  if (rc == PROQA_OK && qa)
+    rc = check_questions(who, qa->n, batch, n_paras, qa->max_seqs, qa->max_paras, qa->seq_host, qa->para_host);
+  if (rc != PROQA_OK) return rc;
+  DropoutParams drop;
+  if (!make_dropout_params(p, seed, site, call, &drop))
+    return fail(PROQA_EINVAL, "%s: p=%g must be in [0, 1) and site=%d in [0, 255]", who, p, site);
+  bool null = !hidden || !para_offset_dev || !qa_w || !start_pos || !end_pos || !q || !para_embed || !labels || !logits || !ws ||
+              (qa && (!cu_seqlens_dev || !qa->seq_dev || !qa->para_dev));
+  for (const void* ptr : own) null = null || !ptr;
+  if (null) return fail(PROQA_EINVAL, "%s: NULL argument", who);
+  if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
+      (d_hidden && !aligned16(d_hidden)) || ((uintptr_t)logits & 3))
+    return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / %sws must be 16-byte aligned, logits 4-byte aligned", who,
+                d_hidden ? "d_hidden / " : "");
+  const int n_questions = qa ? qa->n : 1;
+  const int rank_blocks = ceil_div(qa ? qa->max_paras : n_paras, kRankRows);
+  *sc = scratch_of(batch, seq_len, hsize, n_answers, n_paras, (size_t)n_questions * rank_blocks);
+  if (ws_bytes < sc->bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc->bytes);
+  *o = Operands{hidden, Layout{(const int*)seq_lens_dev, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
+                Questions{qa ? (const int*)qa->seq_dev : nullptr, qa ? (const int*)qa->para_dev : nullptr, n_questions, batch,
+                          n_paras, rank_blocks},
+                hsize, qa_w, (const int*)start_pos, (const int*)end_pos, n_answers, q, para_embed, para_dtype,
+                (const int*)labels, flags, drop};
+  return PROQA_OK;
+}
+
 }  // namespace
 }  // namespace proqa
 
@@ -1033,26 +1081,12 @@ int proqa_reader_loss_f16(const void* hidden, const int32_t* seq_lens_dev, const
                           const void* para_embed, int para_dtype, const int32_t* labels, int n_paras, int dim, int flags,
                           double p, uint64_t seed, int site, uint32_t call, void* logits_out, float* stats, float* loss_out,
                           void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "reader_loss";
-  const int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxParas, dim, para_dtype, flags,
-                             seq_lens_dev, cu_seqlens_dev);
+  Operands o;
+  Scratch sc;
+  const int rc = prepare("reader_loss", hidden, seq_lens_dev, cu_seqlens_dev, batch, seq_len, hidden_size, para_offset_dev, qa_w,
+                         start_pos, end_pos, n_answers, q, para_embed, para_dtype, labels, n_paras, dim, nullptr, flags, p, seed,
+                         site, call, {qa_b, stats, loss_out}, logits_out, nullptr, ws, ws_bytes, &o, &sc);
   if (rc != PROQA_OK) return rc;
-  DropoutParams drop;
-  if (!make_dropout_params(p, seed, site, call, &drop))
-    return fail(PROQA_EINVAL, "%s: p=%g must be in [0, 1) and site=%d in [0, 255]", who, p, site);
-  if (!hidden || !para_offset_dev || !qa_w || !qa_b || !start_pos || !end_pos || !q || !para_embed || !labels || !logits_out ||
-      !stats || !loss_out || !ws)
-    return fail(PROQA_EINVAL, "%s: NULL argument", who);
-  if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
-      ((uintptr_t)logits_out & 3))
-    return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / ws must be 16-byte aligned, logits 4-byte aligned", who);
-  const int n_rank = ceil_div(n_paras, kRankRows);
-  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_rank);
-  if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
-
-  const Operands o = {hidden, Layout{(const int*)seq_lens_dev, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
-                      Questions{nullptr, nullptr, 1, batch, n_paras, n_rank}, hidden_size, qa_w, (const int*)start_pos,
-                      (const int*)end_pos, n_answers, q, para_embed, para_dtype, (const int*)labels, flags, drop};
   return launch_forward(o, qa_b, logits_out, stats, loss_out, ws, sc, as_stream(stream));
 }
 
@@ -1063,27 +1097,13 @@ int proqa_reader_loss_backward_f16(const void* hidden, const int32_t* seq_lens_d
                                    int flags, double p, uint64_t seed, int site, uint32_t call, const void* logits,
                                    const float* stats, const float* grad_in, void* d_hidden, float* d_qa_w, float* d_qa_b,
                                    void* d_q, void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "reader_loss_backward";
-  const int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxParas, dim, para_dtype, flags,
-                             seq_lens_dev, cu_seqlens_dev);
+  Operands o;
+  Scratch sc;
+  const int rc = prepare("reader_loss_backward", hidden, seq_lens_dev, cu_seqlens_dev, batch, seq_len, hidden_size,
+                         para_offset_dev, qa_w, start_pos, end_pos, n_answers, q, para_embed, para_dtype, labels, n_paras, dim,
+                         nullptr, flags, p, seed, site, call, {stats, grad_in, d_hidden, d_qa_w, d_qa_b, d_q}, logits, d_hidden,
+                         ws, ws_bytes, &o, &sc);
   if (rc != PROQA_OK) return rc;
-  DropoutParams drop;
-  if (!make_dropout_params(p, seed, site, call, &drop))
-    return fail(PROQA_EINVAL, "%s: p=%g must be in [0, 1) and site=%d in [0, 255]", who, p, site);
-  if (!hidden || !para_offset_dev || !qa_w || !start_pos || !end_pos || !q || !para_embed || !labels || !logits || !stats ||
-      !grad_in || !d_hidden || !d_qa_w || !d_qa_b || !d_q || !ws)
-    return fail(PROQA_EINVAL, "%s: NULL argument", who);
-  if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
-      !aligned16(d_hidden) || ((uintptr_t)logits & 3))
-    return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / d_hidden / ws must be 16-byte aligned, logits 4-byte aligned",
-                who);
-  const int n_rank = ceil_div(n_paras, kRankRows);
-  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_rank);
-  if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
-
-  const Operands o = {hidden, Layout{(const int*)seq_lens_dev, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
-                      Questions{nullptr, nullptr, 1, batch, n_paras, n_rank}, hidden_size, qa_w, (const int*)start_pos,
-                      (const int*)end_pos, n_answers, q, para_embed, para_dtype, (const int*)labels, flags, drop};
   return launch_backward(o, logits, stats, grad_in, d_hidden, d_qa_w, d_qa_b, d_q, ws, sc, as_stream(stream));
 }
 
@@ -1101,29 +1121,14 @@ int proqa_reader_loss_multi_f16(const void* hidden, const int32_t* cu_seqlens_de
                                 const int32_t* question_seq_host, const int32_t* question_para_host, int flags, double p,
                                 uint64_t seed, int site, uint32_t call, void* logits_out, float* stats, float* loss_out,
                                 void* ws, size_t ws_bytes, void* stream) {
-  const char* who = "reader_loss_multi";
-  int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxPackParas, dim, para_dtype, flags, nullptr,
-                       &kPackedOnly);   // (a NULL cu_seqlens is reported with the other NULLs below)
+  const QuestionArgs qa = {question_seq_dev, question_para_dev, n_questions, max_seqs, max_paras, question_seq_host,
+                           question_para_host};
+  Operands o;
+  Scratch sc;
+  const int rc = prepare("reader_loss_multi", hidden, nullptr, cu_seqlens_dev, batch, seq_len, hidden_size, para_offset_dev, qa_w,
+                         start_pos, end_pos, n_answers, q, para_embed, para_dtype, labels, n_paras, dim, &qa, flags, p, seed, site,
+                         call, {qa_b, stats, loss_out}, logits_out, nullptr, ws, ws_bytes, &o, &sc);
   if (rc != PROQA_OK) return rc;
-  rc = check_questions(who, n_questions, batch, n_paras, max_seqs, max_paras, question_seq_host, question_para_host);
-  if (rc != PROQA_OK) return rc;
-  DropoutParams drop;
-  if (!make_dropout_params(p, seed, site, call, &drop))
-    return fail(PROQA_EINVAL, "%s: p=%g must be in [0, 1) and site=%d in [0, 255]", who, p, site);
-  if (!hidden || !cu_seqlens_dev || !para_offset_dev || !qa_w || !qa_b || !start_pos || !end_pos || !q || !para_embed || !labels ||
-      !question_seq_dev || !question_para_dev || !logits_out || !stats || !loss_out || !ws)
-    return fail(PROQA_EINVAL, "%s: NULL argument", who);
-  if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
-      ((uintptr_t)logits_out & 3))
-    return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / ws must be 16-byte aligned, logits 4-byte aligned", who);
-  const int rank_blocks = ceil_div(max_paras, kRankRows);
-  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_questions * rank_blocks);
-  if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
-
-  const Operands o = {hidden, Layout{nullptr, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
-                      Questions{(const int*)question_seq_dev, (const int*)question_para_dev, n_questions, batch, n_paras, rank_blocks},
-                      hidden_size, qa_w, (const int*)start_pos, (const int*)end_pos, n_answers, q, para_embed, para_dtype,
-                      (const int*)labels, flags, drop};
   return launch_forward(o, qa_b, logits_out, stats, loss_out, ws, sc, as_stream(stream));
 }
 
@@ -1137,30 +1142,15 @@ int proqa_reader_loss_multi_backward_f16(const void* hidden, const int32_t* cu_s
                                          uint32_t call, const void* logits, const float* stats, const float* grad_in,
                                          void* d_hidden, float* d_qa_w, float* d_qa_b, void* d_q, void* ws, size_t ws_bytes,
                                          void* stream) {
-  const char* who = "reader_loss_multi_backward";
-  int rc = check_sizes(who, batch, seq_len, hidden_size, n_answers, n_paras, kMaxPackParas, dim, para_dtype, flags, nullptr,
-                       &kPackedOnly);
+  const QuestionArgs qa = {question_seq_dev, question_para_dev, n_questions, max_seqs, max_paras, question_seq_host,
+                           question_para_host};
+  Operands o;
+  Scratch sc;
+  const int rc = prepare("reader_loss_multi_backward", hidden, nullptr, cu_seqlens_dev, batch, seq_len, hidden_size,
+                         para_offset_dev, qa_w, start_pos, end_pos, n_answers, q, para_embed, para_dtype, labels, n_paras, dim,
+                         &qa, flags, p, seed, site, call, {stats, grad_in, d_hidden, d_qa_w, d_qa_b, d_q}, logits, d_hidden, ws,
+                         ws_bytes, &o, &sc);
   if (rc != PROQA_OK) return rc;
-  rc = check_questions(who, n_questions, batch, n_paras, max_seqs, max_paras, question_seq_host, question_para_host);
-  if (rc != PROQA_OK) return rc;
-  DropoutParams drop;
-  if (!make_dropout_params(p, seed, site, call, &drop))
-    return fail(PROQA_EINVAL, "%s: p=%g must be in [0, 1) and site=%d in [0, 255]", who, p, site);
-  if (!hidden || !cu_seqlens_dev || !para_offset_dev || !qa_w || !start_pos || !end_pos || !q || !para_embed || !labels ||
-      !question_seq_dev || !question_para_dev || !logits || !stats || !grad_in || !d_hidden || !d_qa_w || !d_qa_b || !d_q || !ws)
-    return fail(PROQA_EINVAL, "%s: NULL argument", who);
-  if (!aligned16(hidden) || !aligned16(qa_w) || !aligned16(q) || !aligned16(para_embed) || !aligned16(ws) ||
-      !aligned16(d_hidden) || ((uintptr_t)logits & 3))
-    return fail(PROQA_EINVAL, "%s: hidden / qa_w / q / para_embed / d_hidden / ws must be 16-byte aligned, logits 4-byte aligned",
-                who);
-  const int rank_blocks = ceil_div(max_paras, kRankRows);
-  const Scratch sc = scratch_of(batch, seq_len, hidden_size, n_answers, n_paras, (size_t)n_questions * rank_blocks);
-  if (ws_bytes < sc.bytes) return fail(PROQA_EINVAL, "%s: workspace too small (%zu < %zu bytes)", who, ws_bytes, sc.bytes);
-
-  const Operands o = {hidden, Layout{nullptr, (const int*)cu_seqlens_dev, (const int*)para_offset_dev, seq_len},
-                      Questions{(const int*)question_seq_dev, (const int*)question_para_dev, n_questions, batch, n_paras, rank_blocks},
-                      hidden_size, qa_w, (const int*)start_pos, (const int*)end_pos, n_answers, q, para_embed, para_dtype,
-                      (const int*)labels, flags, drop};
   return launch_backward(o, logits, stats, grad_in, d_hidden, d_qa_w, d_qa_b, d_q, ws, sc, as_stream(stream));
 }
 

@@ -34,10 +34,13 @@ def _i32(x, device, name):
 
 
 class _Geometry:
-    """What both kernels are told about the batch (plain numbers and the int32 device tensors)."""
+    """What both kernels are told about the batch (plain numbers and the int32 device tensors).  Without question_seq: one
+    question, in the packed or the padded layout.  With question_seq / question_para (the CSR offsets that cut the batch into
+    n_questions: host lists, or int device tensors together with max_seqs / max_paras): a pack, in the packed layout."""
 
     def __init__(self, hidden, cu_seqlens, seq_lens, para_offset, start_positions, end_positions, para_embed, labels,
-                 shared_norm, early, qa_drop, dropout_state, max_seq_len):
+                 shared_norm, early, qa_drop, dropout_state, max_seq_len, n_questions=1, question_seq=None, question_para=None,
+                 max_seqs=None, max_paras=None):
         dev = hidden.device
         if (cu_seqlens is None) == (seq_lens is None):
             raise ValueError("reader_loss: exactly one of cu_seqlens (packed hidden [T, H]) and seq_lens (padded hidden "
@@ -81,120 +84,11 @@ class _Geometry:
             self.seed, self.call = int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFF
         else:
             self.seed, self.call = 0, 0
-
-    def layout(self):
-        return (self.lens.data_ptr() if self.lens is not None else None, self.cu.data_ptr() if self.cu is not None else None,
-                self.batch, self.seq_len, self.hidden_size, self.para_offset.data_ptr())
-
-    def objective(self, q):
-        return (self.start.data_ptr(), self.end.data_ptr(), self.n_answers, q.data_ptr(), self.para.data_ptr(), self.para_dtype,
-                self.labels.data_ptr(), self.n_paras, self.dim, self.flags, self.p, self.seed, READER_HEAD_SITE, self.call)
-
-    def workspace(self, lib, device):
-        need = lib.proqa_reader_loss_workspace_bytes(self.batch, self.seq_len, self.hidden_size, self.n_answers, self.n_paras)
-        return _workspace(device, need)
-
-
-def reader_loss_forward(hidden, w16, b16, q, geo):
-    """-> (loss_out fp32 [3] = total, joint, early; logits fp16 [rows, 2]; stats fp32 [8 + 2 B]); no autograd"""
-    lib = _lib.load()
-    dev = hidden.device
-    rows = hidden.numel() // max(geo.hidden_size, 1)
-    logits = torch.empty((rows, 2), dtype=torch.float16, device=dev)
-    stats = torch.empty(8 + 2 * max(geo.batch, 0), dtype=torch.float32, device=dev)
-    loss_out = torch.empty(3, dtype=torch.float32, device=dev)
-    ws = geo.workspace(lib, dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.proqa_reader_loss_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), b16.data_ptr(), *geo.objective(q),
-                                             logits.data_ptr(), stats.data_ptr(), loss_out.data_ptr(), ws.data_ptr(),
-                                             ws.numel(), _lib.current_stream_ptr()))
-    return loss_out, logits, stats
-
-
-def reader_loss_backward(hidden, w16, q, geo, logits, stats, grad_in):
-    """grad_in: fp32 device scalar -> (d_hidden fp16 like hidden, d_qa_w fp32 [2, H], d_qa_b fp32 [2], d_q fp16 [128])"""
-    lib = _lib.load()
-    dev = hidden.device
-    d_hidden = torch.empty_like(hidden)
-    d_w = torch.empty((2, geo.hidden_size), dtype=torch.float32, device=dev)
-    d_b = torch.empty(2, dtype=torch.float32, device=dev)
-    d_q = torch.empty(EMBED_DIM, dtype=torch.float16, device=dev)
-    ws = geo.workspace(lib, dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.proqa_reader_loss_backward_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), *geo.objective(q),
-                                                      logits.data_ptr(), stats.data_ptr(), grad_in.data_ptr(),
-                                                      d_hidden.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), d_q.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
-    return d_hidden, d_w, d_b, d_q
-
-
-class _ReaderLoss(torch.autograd.Function):
-    """(hidden fp16, qa_weight fp32 master, qa_bias fp32 master, q fp16 [128]) -> fp32 [3] = (loss, joint, early); only
-    element 0 is differentiated."""
-
-    @staticmethod
-    def forward(ctx, hidden, qa_weight, qa_bias, q, geo):
-        w16, b16 = qa_weight.half().contiguous(), qa_bias.half().contiguous()
-        loss_out, logits, stats = reader_loss_forward(hidden, w16, b16, q, geo)
-        ctx.save_for_backward(hidden, w16, q, logits, stats)
-        ctx.geo = geo
-        return loss_out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        hidden, w16, q, logits, stats = ctx.saved_tensors
-        g = grad_out.to(torch.float32).contiguous()     # element 0: the gradient of the total loss
-        d_hidden, d_w, d_b, d_q = reader_loss_backward(hidden, w16, q, ctx.geo, logits, stats, g)
-        return d_hidden, d_w, d_b, d_q, None
-
-
-def reader_loss(hidden, qa_weight, qa_bias, q, para_embed, top5000_labels, start_positions, end_positions, para_offset, *,
-                cu_seqlens=None, seq_lens=None, shared_norm=True, early=True, qa_drop=0.0, dropout_state=None,
-                max_seq_len=None):
-    """The training loss of BertRetrieveQA.forward for the B passages of one question.
-
-    hidden            fp16 last hidden state of the reader's BERT: packed [T, H] with cu_seqlens (int [B + 1]), or padded
-                      [B, L, H] with seq_lens (int [B]); H % 8 == 0, H <= 1024
-    qa_weight/qa_bias the fp32 masters of qa_outputs, [2, H] and [2]; their gradients are fp32
-    q                 fp16 question embedding [128], or [n, 128] of which row 0 is taken (the reference's q[0]), e.g.
-                      TrainableRetriever.get_embed(batch, True)["embed"]
-    para_embed        [P, 128] float16 or float32, the sampler's rows; the first B belong to the sequences
-    top5000_labels    int [P]; start_positions / end_positions: int [B, A] in sequence coordinates, -1 = padding
-    para_offset       int [B]: the paragraph mask of sequence b is [para_offset[b], len(b) - 1)
-    shared_norm       --shared-norm; early=False is --drop-early (the loss without the early term)
-    qa_drop           rate of the dropout in front of qa_outputs; dropout_state = (seed, call), call advanced by the caller
-    max_seq_len       packed layout only: a bound on the longest sequence (default min(T, 4096))
-
-    -> {"loss": fp32 scalar with gradients w.r.t. hidden, q, qa_weight and qa_bias, "joint", "early": fp32 scalars, detached}.
-    Everything stays on the device and on torch's current stream."""
-    if not torch.is_tensor(hidden) or not hidden.is_cuda or hidden.dtype != torch.float16:
-        raise ValueError("reader_loss: hidden must be a float16 CUDA tensor (there is no CPU path)")
-    if not q.is_cuda or q.dtype != torch.float16 or q.shape[-1] != EMBED_DIM or q.dim() not in (1, 2):
-        raise ValueError(f"reader_loss: q must be a float16 CUDA tensor [{EMBED_DIM}] or [n, {EMBED_DIM}], got {q.dtype} "
-                         f"{tuple(q.shape)}")
-    if qa_weight.dtype != torch.float32 or qa_bias.dtype != torch.float32:
-        raise ValueError("reader_loss: qa_weight / qa_bias are the fp32 masters; they are cast to fp16 inside")
-    if tuple(qa_weight.shape) != (2, hidden.shape[-1]) or tuple(qa_bias.shape) != (2,):
-        raise ValueError(f"reader_loss: qa_weight must be [2, {hidden.shape[-1]}] and qa_bias [2]")
-    if not 0.0 <= float(qa_drop) <= 0.9:
-        raise ValueError(f"reader_loss: qa_drop={qa_drop!r} must be in [0, 0.9]")
-    geo = _Geometry(hidden.contiguous(), cu_seqlens, seq_lens, para_offset, start_positions, end_positions, para_embed,
-                    top5000_labels, shared_norm, early, qa_drop, dropout_state, max_seq_len)
-    q0 = (q[0] if q.dim() == 2 else q).contiguous()
-    out = _ReaderLoss.apply(hidden.contiguous(), qa_weight, qa_bias, q0, geo)
-    return {"loss": out[0], "joint": out[1].detach(), "early": out[2].detach()}
-
-
-# ---- several questions in one call -------------------------------------------------------------------------------------------
-
-class _MultiGeometry(_Geometry):
-    """_Geometry of a pack of questions: the packed layout, and the CSR arrays that cut it into questions."""
-
-    def __init__(self, hidden, n_questions, cu_seqlens, question_seq, question_para, max_seqs, max_paras, *rest):
-        super().__init__(hidden, cu_seqlens, None, *rest)
-        dev = hidden.device
-        self.n_questions = int(n_questions)
+        self.pack = question_seq is not None
+        self.n_questions = int(n_questions) if self.pack else 1
+        self.per_question = (self.n_questions,) if self.pack else ()     # the leading shape of loss_out and d_q
+        if not self.pack:
+            return
         self.host = []
         counts = []
         for name, csr, given in (("question_seq", question_seq, max_seqs), ("question_para", question_para, max_paras)):
@@ -221,62 +115,88 @@ class _MultiGeometry(_Geometry):
         self.max_seqs, self.max_paras = counts
 
     def layout(self):
-        return (self.cu.data_ptr(), self.batch, self.seq_len, self.hidden_size, self.para_offset.data_ptr())
+        """the arguments between hidden and qa_w (a pack has no seq_lens)"""
+        lens = () if self.pack else (self.lens.data_ptr() if self.lens is not None else None,)
+        return (*lens, self.cu.data_ptr() if self.cu is not None else None, self.batch, self.seq_len, self.hidden_size,
+                self.para_offset.data_ptr())
 
     def objective(self, q):
-        host = [a.ctypes.data if a is not None else None for a in self.host]
+        """the arguments from start_pos to call (a pack puts its questions between dim and flags)"""
+        questions = ()
+        if self.pack:
+            host = [a.ctypes.data if a is not None else None for a in self.host]
+            questions = (self.question_seq.data_ptr(), self.question_para.data_ptr(), self.n_questions, self.max_seqs,
+                         self.max_paras, host[0], host[1])
         return (self.start.data_ptr(), self.end.data_ptr(), self.n_answers, q.data_ptr(), self.para.data_ptr(), self.para_dtype,
-                self.labels.data_ptr(), self.n_paras, self.dim, self.question_seq.data_ptr(), self.question_para.data_ptr(),
-                self.n_questions, self.max_seqs, self.max_paras, host[0], host[1], self.flags, self.p, self.seed,
-                READER_HEAD_SITE, self.call)
+                self.labels.data_ptr(), self.n_paras, self.dim, *questions, self.flags, self.p, self.seed, READER_HEAD_SITE,
+                self.call)
+
+    def entries(self, lib):
+        """(forward, backward) of the C ABI: a pack takes the multi pair, at one question too"""
+        if self.pack:
+            return lib.proqa_reader_loss_multi_f16, lib.proqa_reader_loss_multi_backward_f16
+        return lib.proqa_reader_loss_f16, lib.proqa_reader_loss_backward_f16
 
     def workspace(self, lib, device):
-        need = lib.proqa_reader_loss_multi_workspace_bytes(self.n_questions, self.batch, self.seq_len, self.hidden_size,
-                                                           self.n_answers, self.n_paras, self.max_paras)
+        if self.pack:
+            need = lib.proqa_reader_loss_multi_workspace_bytes(self.n_questions, self.batch, self.seq_len, self.hidden_size,
+                                                               self.n_answers, self.n_paras, self.max_paras)
+        else:
+            need = lib.proqa_reader_loss_workspace_bytes(self.batch, self.seq_len, self.hidden_size, self.n_answers, self.n_paras)
         return _workspace(device, need)
 
 
-def reader_loss_multi_forward(hidden, w16, b16, q, geo):
-    """-> (loss_out fp32 [Q, 3]; logits fp16 [T, 2]; stats fp32 [8 Q + 2 B], the single-question layout question after
-    question); no autograd"""
+def reader_loss_forward(hidden, w16, b16, q, geo):
+    """-> (loss_out fp32 [3] = total, joint, early, for a pack [Q, 3]; logits fp16 [rows, 2]; stats fp32 [8 Q + 2 B], the
+    single-question layout question after question); no autograd"""
     lib = _lib.load()
     dev = hidden.device
-    logits = torch.empty((hidden.shape[0], 2), dtype=torch.float16, device=dev)
+    rows = hidden.numel() // max(geo.hidden_size, 1)
+    logits = torch.empty((rows, 2), dtype=torch.float16, device=dev)
     stats = torch.empty(8 * geo.n_questions + 2 * max(geo.batch, 0), dtype=torch.float32, device=dev)
-    loss_out = torch.empty((geo.n_questions, 3), dtype=torch.float32, device=dev)
+    loss_out = torch.empty(geo.per_question + (3,), dtype=torch.float32, device=dev)
     ws = geo.workspace(lib, dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.proqa_reader_loss_multi_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), b16.data_ptr(),
-                                                   *geo.objective(q), logits.data_ptr(), stats.data_ptr(), loss_out.data_ptr(),
-                                                   ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+        _lib.check(geo.entries(lib)[0](hidden.data_ptr(), *geo.layout(), w16.data_ptr(), b16.data_ptr(), *geo.objective(q),
+                                       logits.data_ptr(), stats.data_ptr(), loss_out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _lib.current_stream_ptr()))
     return loss_out, logits, stats
 
 
-def reader_loss_multi_backward(hidden, w16, q, geo, logits, stats, grad_in):
-    """grad_in: fp32 [Q] on the device -> (d_hidden fp16 [T, H], d_qa_w fp32 [2, H], d_qa_b fp32 [2], d_q fp16 [Q, 128])"""
+def reader_loss_backward(hidden, w16, q, geo, logits, stats, grad_in):
+    """grad_in: fp32 on the device, one value per question -> (d_hidden fp16 like hidden, d_qa_w fp32 [2, H], d_qa_b fp32 [2],
+    d_q fp16 [128], for a pack [Q, 128])"""
     lib = _lib.load()
     dev = hidden.device
     d_hidden = torch.empty_like(hidden)
     d_w = torch.empty((2, geo.hidden_size), dtype=torch.float32, device=dev)
     d_b = torch.empty(2, dtype=torch.float32, device=dev)
-    d_q = torch.empty((geo.n_questions, EMBED_DIM), dtype=torch.float16, device=dev)
+    d_q = torch.empty(geo.per_question + (EMBED_DIM,), dtype=torch.float16, device=dev)
     ws = geo.workspace(lib, dev)
     with torch.cuda.device(dev):
-        _lib.check(lib.proqa_reader_loss_multi_backward_f16(hidden.data_ptr(), *geo.layout(), w16.data_ptr(), *geo.objective(q),
-                                                            logits.data_ptr(), stats.data_ptr(), grad_in.data_ptr(),
-                                                            d_hidden.data_ptr(), d_w.data_ptr(), d_b.data_ptr(), d_q.data_ptr(),
-                                                            ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
+        _lib.check(geo.entries(lib)[1](hidden.data_ptr(), *geo.layout(), w16.data_ptr(), *geo.objective(q), logits.data_ptr(),
+                                       stats.data_ptr(), grad_in.data_ptr(), d_hidden.data_ptr(), d_w.data_ptr(), d_b.data_ptr(),
+                                       d_q.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()))
     return d_hidden, d_w, d_b, d_q
 
 
-class _ReaderLossMulti(torch.autograd.Function):
-    """(hidden fp16 [T, H], qa_weight, qa_bias fp32 masters, q fp16 [Q, 128]) -> fp32 [Q, 3] = (loss, joint, early) per
-    question; only column 0 is differentiated."""
+# the names and the argument order under which tests/test_reader_loss_multi_gpu.py drives a pack through the helpers
+reader_loss_multi_forward, reader_loss_multi_backward = reader_loss_forward, reader_loss_backward
+
+
+def _MultiGeometry(hidden, n_questions, cu_seqlens, question_seq, question_para, max_seqs, max_paras, *rest):
+    return _Geometry(hidden, cu_seqlens, None, *rest, n_questions=n_questions, question_seq=question_seq,
+                     question_para=question_para, max_seqs=max_seqs, max_paras=max_paras)
+
+
+class _ReaderLoss(torch.autograd.Function):
+    """(hidden fp16, qa_weight fp32 master, qa_bias fp32 master, q fp16 [128] or, for a pack, [Q, 128]) -> fp32 [3] or [Q, 3]
+    = (loss, joint, early) per question; only element 0 of a question is differentiated."""
 
     @staticmethod
     def forward(ctx, hidden, qa_weight, qa_bias, q, geo):
         w16, b16 = qa_weight.half().contiguous(), qa_bias.half().contiguous()
-        loss_out, logits, stats = reader_loss_multi_forward(hidden, w16, b16, q, geo)
+        loss_out, logits, stats = reader_loss_forward(hidden, w16, b16, q, geo)
         ctx.save_for_backward(hidden, w16, q, logits, stats)
         ctx.geo = geo
         return loss_out
@@ -285,9 +205,51 @@ class _ReaderLossMulti(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         hidden, w16, q, logits, stats = ctx.saved_tensors
-        g = grad_out[:, 0].to(torch.float32).contiguous()     # the gradients of the questions' total losses
-        d_hidden, d_w, d_b, d_q = reader_loss_multi_backward(hidden, w16, q, ctx.geo, logits, stats, g)
+        g = grad_out[..., 0].to(torch.float32).contiguous()     # the gradients of the questions' total losses
+        d_hidden, d_w, d_b, d_q = reader_loss_backward(hidden, w16, q, ctx.geo, logits, stats, g)
         return d_hidden, d_w, d_b, d_q, None
+
+
+def _check_arguments(who, hidden, qa_weight, qa_bias, q, q_dims_ok, q_shape, qa_drop):
+    """what both fronts refuse before anything is built; q_dims_ok / q_shape: the front's own rule for q's dimensions"""
+    if not torch.is_tensor(hidden) or not hidden.is_cuda or hidden.dtype != torch.float16:
+        raise ValueError(f"{who}: hidden must be a float16 CUDA tensor (there is no CPU path)")
+    if not q.is_cuda or q.dtype != torch.float16 or not q_dims_ok or q.shape[-1] != EMBED_DIM:
+        raise ValueError(f"{who}: q must be a float16 CUDA tensor {q_shape}, got {q.dtype} {tuple(q.shape)}")
+    if qa_weight.dtype != torch.float32 or qa_bias.dtype != torch.float32:
+        raise ValueError(f"{who}: qa_weight / qa_bias are the fp32 masters; they are cast to fp16 inside")
+    if tuple(qa_weight.shape) != (2, hidden.shape[-1]) or tuple(qa_bias.shape) != (2,):
+        raise ValueError(f"{who}: qa_weight must be [2, {hidden.shape[-1]}] and qa_bias [2]")
+    if not 0.0 <= float(qa_drop) <= 0.9:
+        raise ValueError(f"{who}: qa_drop={qa_drop!r} must be in [0, 0.9]")
+
+
+def reader_loss(hidden, qa_weight, qa_bias, q, para_embed, top5000_labels, start_positions, end_positions, para_offset, *,
+                cu_seqlens=None, seq_lens=None, shared_norm=True, early=True, qa_drop=0.0, dropout_state=None,
+                max_seq_len=None):
+    """The training loss of BertRetrieveQA.forward for the B passages of one question.
+
+    hidden            fp16 last hidden state of the reader's BERT: packed [T, H] with cu_seqlens (int [B + 1]), or padded
+                      [B, L, H] with seq_lens (int [B]); H % 8 == 0, H <= 1024
+    qa_weight/qa_bias the fp32 masters of qa_outputs, [2, H] and [2]; their gradients are fp32
+    q                 fp16 question embedding [128], or [n, 128] of which row 0 is taken (the reference's q[0]), e.g.
+                      TrainableRetriever.get_embed(batch, True)["embed"]
+    para_embed        [P, 128] float16 or float32, the sampler's rows; the first B belong to the sequences
+    top5000_labels    int [P]; start_positions / end_positions: int [B, A] in sequence coordinates, -1 = padding
+    para_offset       int [B]: the paragraph mask of sequence b is [para_offset[b], len(b) - 1)
+    shared_norm       --shared-norm; early=False is --drop-early (the loss without the early term)
+    qa_drop           rate of the dropout in front of qa_outputs; dropout_state = (seed, call), call advanced by the caller
+    max_seq_len       packed layout only: a bound on the longest sequence (default min(T, 4096))
+
+    -> {"loss": fp32 scalar with gradients w.r.t. hidden, q, qa_weight and qa_bias, "joint", "early": fp32 scalars, detached}.
+    Everything stays on the device and on torch's current stream."""
+    _check_arguments("reader_loss", hidden, qa_weight, qa_bias, q, q.dim() in (1, 2), f"[{EMBED_DIM}] or [n, {EMBED_DIM}]",
+                     qa_drop)
+    geo = _Geometry(hidden.contiguous(), cu_seqlens, seq_lens, para_offset, start_positions, end_positions, para_embed,
+                    top5000_labels, shared_norm, early, qa_drop, dropout_state, max_seq_len)
+    q0 = (q[0] if q.dim() == 2 else q).contiguous()
+    out = _ReaderLoss.apply(hidden.contiguous(), qa_weight, qa_bias, q0, geo)
+    return {"loss": out[0], "joint": out[1].detach(), "early": out[2].detach()}
 
 
 def reader_loss_multi(hidden, qa_weight, qa_bias, q, para_embed, top5000_labels, start_positions, end_positions, para_offset, *,
@@ -311,21 +273,12 @@ def reader_loss_multi(hidden, qa_weight, qa_bias, q, para_embed, top5000_labels,
     -> {"losses": fp32 [Q] with gradients w.r.t. hidden, q, qa_weight and qa_bias, "joint", "early": fp32 [Q], detached}.
     Each question's values carry the bits reader_loss gives for the question alone (qa_drop == 0); the gradients of qa_weight /
     qa_bias are the questions' gradients added in ascending order."""
-    if not torch.is_tensor(hidden) or not hidden.is_cuda or hidden.dtype != torch.float16:
-        raise ValueError("reader_loss_multi: hidden must be a float16 CUDA tensor (there is no CPU path)")
-    if not q.is_cuda or q.dtype != torch.float16 or q.dim() != 2 or q.shape[-1] != EMBED_DIM or q.shape[0] < 1:
-        raise ValueError(f"reader_loss_multi: q must be a float16 CUDA tensor [Q, {EMBED_DIM}] with Q >= 1, got {q.dtype} "
-                         f"{tuple(q.shape)}")
-    if qa_weight.dtype != torch.float32 or qa_bias.dtype != torch.float32:
-        raise ValueError("reader_loss_multi: qa_weight / qa_bias are the fp32 masters; they are cast to fp16 inside")
-    if tuple(qa_weight.shape) != (2, hidden.shape[-1]) or tuple(qa_bias.shape) != (2,):
-        raise ValueError(f"reader_loss_multi: qa_weight must be [2, {hidden.shape[-1]}] and qa_bias [2]")
-    if not 0.0 <= float(qa_drop) <= 0.9:
-        raise ValueError(f"reader_loss_multi: qa_drop={qa_drop!r} must be in [0, 0.9]")
+    _check_arguments("reader_loss_multi", hidden, qa_weight, qa_bias, q, q.dim() == 2 and q.shape[0] >= 1,
+                     f"[Q, {EMBED_DIM}] with Q >= 1", qa_drop)
     if cu_seqlens is None:
         raise ValueError("reader_loss_multi: the packed layout only (cu_seqlens)")
-    geo = _MultiGeometry(hidden.contiguous(), q.shape[0], cu_seqlens, question_seq, question_para, max_seqs, max_paras,
-                         para_offset, start_positions, end_positions, para_embed, top5000_labels, shared_norm, early, qa_drop,
-                         dropout_state, max_seq_len)
-    out = _ReaderLossMulti.apply(hidden.contiguous(), qa_weight, qa_bias, q.contiguous(), geo)
+    geo = _Geometry(hidden.contiguous(), cu_seqlens, None, para_offset, start_positions, end_positions, para_embed,
+                    top5000_labels, shared_norm, early, qa_drop, dropout_state, max_seq_len, n_questions=q.shape[0],
+                    question_seq=question_seq, question_para=question_para, max_seqs=max_seqs, max_paras=max_paras)
+    out = _ReaderLoss.apply(hidden.contiguous(), qa_weight, qa_bias, q.contiguous(), geo)
     return {"losses": out[:, 0], "joint": out[:, 1].detach(), "early": out[:, 2].detach()}

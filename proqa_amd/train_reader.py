@@ -20,10 +20,11 @@ searches (the model is back in train() after it, as after the reference's predic
 Beyond the reference (proqa_amd/checkpoint.py): --save-state, --stop-after-updates, --resume and
 --digest-every as in pretrain_retriever.py; the state also holds the sampler's permutation, the failed and update steps
 and the RNG states, so a run resumed inside an epoch visits the questions the uninterrupted run visits.
---questions-per-pass Q (default 1: the loop above): within an accumulation window no weight changes, so up to Q of its
-questions are drawn from the sampler one after another, as before, and then run through ONE forward (TrainableReader on
-the list: one pass per tower, one fused loss call) and one backward; pass_schedule() is the grouping rule.  The optimisation
-step is the one of the questions run one after another; with --gradient_accumulation_steps 1 every pass holds one question.
+--questions-per-pass Q (default 1): within an accumulation window no weight changes, so up to Q of its questions are drawn
+from the sampler one after another and then run through ONE forward (TrainableReader on the list: one pass per tower, one
+fused loss call) and one backward; pass_schedule() is the grouping rule, and Q = 1, the reference's loop, is its smallest
+case.  The optimisation step is the one of the questions run one after another; with --gradient_accumulation_steps 1 every
+pass holds one question.
 """
 import argparse
 import json
@@ -429,8 +430,9 @@ def main(argv=None):
                 state_digests=digests.entries, reader=reader_state), rng=checkpoint.rng_states()))
 
         def run_pass(batches):
-            """forward + backward of the questions of one pass (Q > 1): one forward on the list; every question's loss is
-            divided by G and their sum goes through the loss scale"""
+            """forward + backward of the questions of one pass: one forward on the list; every question's loss is divided
+            by G and their sum goes through the loss scale"""
+            nonlocal n_passes, pending_grad
             for b in batches:
                 if ON_BATCH is not None:
                     ON_BATCH(b)
@@ -440,6 +442,8 @@ def main(argv=None):
             optimizer.scale_loss(losses.sum()).backward()
             for i in range(len(batches)):
                 meter.add(losses[i].detach(), global_step)
+            n_passes += 1
+            pending_grad = True
 
         t_start = time.perf_counter()
         for epoch in range(start_epoch, int(args.num_train_epochs)):
@@ -456,23 +460,11 @@ def main(argv=None):
                     failed_retrieval += 1
                     failed_steps.append(batch_step)
                     continue
-                if Q > 1:
-                    open_pass.append(batch)
-                    if not closes_pass(len(open_pass), batch_step, G, Q):
-                        continue
-                    run_pass(open_pass)
-                    open_pass = []
-                else:
-                    if ON_BATCH is not None:
-                        ON_BATCH(batch)
-                    outputs = model(batch["net_input"])
-                    loss = outputs["loss"]
-                    if G > 1:
-                        loss = loss / G
-                    optimizer.scale_loss(loss).backward()
-                    meter.add(loss.detach(), global_step)
-                n_passes += 1
-                pending_grad = True
+                open_pass.append(batch)
+                if not closes_pass(len(open_pass), batch_step, G, Q):
+                    continue
+                run_pass(open_pass)
+                open_pass = []
 
                 if is_update_step(batch_step, G):
                     optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
@@ -511,9 +503,6 @@ def main(argv=None):
                 break
             if open_pass:       # the epoch ended inside a window: its last questions are a pass of their own
                 run_pass(open_pass)
-                open_pass = []
-                n_passes += 1
-                pending_grad = True
 
             logger.info(f"Failed retrieval: {failed_retrieval}/{len(train_dataloader)} ...")
             failed_per_epoch.append(failed_retrieval)

@@ -5,16 +5,14 @@
 reference's loop (qa/train_retrieve_qa.py) runs with the model class and the optimizer swapped, its sampler keeps calling
 `model.retriever.get_embed`, and the checkpoint it saves loads into BertReader.load / train_retrieve_qa.py --do_predict.
 
-forward(net_input) in train() mode is three steps, all on the device: the reader tower on [CLS] q [SEP] p [SEP] with token
-types (trainable.run_tower: the operators of TrainableRetriever, the embeddings through
-proqa_embed_layernorm_typed_varlen_f16 and its backward), the question tower on ROW 0 of input_ids_q (the reference runs B
-identical rows and uses q[0]), and proqa_amd.reader_loss on the packed hidden states.  One host round trip per tower pass
-(the sizes and the checks of the masks), none in the loss.
-
-forward([net_input, ...]) in train() mode is ONE pass over several questions: one reader-tower pass over all their sequences,
-one question-tower pass over row 0 of every question's input_ids_q, and one reader_loss_multi call.  Within an accumulation
-window no weight changes, so it is the optimisation step of the questions run one after another; -> {"loss": the sum,
-"losses", "joint", "early": per question}.
+forward([net_input, ...]) in train() mode is ONE pass over the questions of the list, three steps, all on the device: the
+reader tower on [CLS] q [SEP] p [SEP] with token types over all their sequences (trainable.run_tower: the operators of
+TrainableRetriever, the embeddings through proqa_embed_layernorm_typed_varlen_f16 and its backward), the question tower on
+ROW 0 of every question's input_ids_q (the reference runs B identical rows and uses q[0]), and one call of
+proqa_amd.reader_loss on the packed hidden states (reader_loss_multi; reader_loss for a pass of one).  One host round trip
+per tower pass (the sizes and the checks of the masks), none in the loss.  Within an accumulation window no weight changes,
+so a pass is the optimisation step of its questions run one after another; -> {"loss": the sum, "losses", "joint", "early":
+per question}.  forward(net_input) in train() mode is the pass of that one question; -> {"loss", "joint", "early"}, scalars.
 
 forward(net_input) in eval() mode returns the reference's keys (start_logits, end_logits, rank_logits) for its dev loop.  It
 runs the INFERENCE class (proqa_amd.reader.BertReader: the fused encoder and proqa_reader_span_f16) over an fp16 copy of the
@@ -185,64 +183,47 @@ class TrainableReader(torch.nn.Module):
     def forward(self, net_input):
         if isinstance(net_input, (list, tuple)):
             return self._forward_questions(list(net_input))
-        ids = net_input["input_ids"]
+        if not self.training:
+            self._check_inputs(net_input)
+            return self._predict(net_input, net_input["paragraph_mask"].to(torch.bool))
+        out = self._forward_questions([net_input])       # one question is the shortest pass
+        return {"loss": out["loss"], "joint": out["joint"][0], "early": out["early"][0]}
+
+    @staticmethod
+    def _check_inputs(x):
+        ids = x["input_ids"]
         if not ids.is_cuda:
             raise RuntimeError("TrainableReader expects CUDA tensors (the reference feeds move_to_cuda(batch))")
-        B, S = ids.shape
-        if B == 0:
+        if ids.shape[0] == 0:
             raise ValueError("TrainableReader: an empty batch")
-        pmask = net_input["paragraph_mask"].to(torch.bool)
-        if pmask.shape != ids.shape:
-            raise ValueError(f"paragraph_mask {tuple(pmask.shape)} must have the shape of input_ids {tuple(ids.shape)}")
-        if not self.training:
-            return self._predict(net_input, pmask)
-        p_hid, p_att, p_qa = self.hidden_dropout_prob, self.attention_probs_dropout_prob, self.qa_drop
-        seed, call = self._dropout_seed, self._dropout_call
-        if p_hid > 0 or p_att > 0 or p_qa > 0:
-            self._dropout_call = (call + CALLS_PER_FORWARD) & 0xFFFFFF
-        geometry = {}
-
-        def paragraph_probe(lens):
-            geometry["para_offset"], bad = _paragraph_geometry(pmask, lens)
-            return bad, _PARAGRAPH_MESSAGE
-
-        hidden, cu, lens, max_len = run_tower(self._flat, "bert", self.config, ids, net_input["input_mask"],
-                                              type_ids=net_input["segment_ids"], drop=(p_hid, p_att, seed, call),
-                                              probe_extra=paragraph_probe, deterministic=self.deterministic)
-        # the question tower on row 0 alone: the reference encodes B identical rows and uses q[0]
-        q = run_tower(self.retriever._flat, "bert_q", self.config, net_input["input_ids_q"][:1], net_input["input_mask_q"][:1],
-                      proj="proj_q", drop=(p_hid, p_att, seed, (call + 1) & 0xFFFFFF), deterministic=self.deterministic)
-        return reader_loss(hidden, self._flat["qa_outputs.weight"], self._flat["qa_outputs.bias"], q, net_input["para_embed"],
-                           net_input["top5000_labels"], net_input["start_positions"], net_input["end_positions"],
-                           geometry["para_offset"], cu_seqlens=cu, shared_norm=self.shared_norm, early=not self.drop_early,
-                           qa_drop=p_qa, dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
+        if x["paragraph_mask"].shape != ids.shape:
+            raise ValueError(f"paragraph_mask {tuple(x['paragraph_mask'].shape)} must have the shape of input_ids "
+                             f"{tuple(ids.shape)}")
 
     def _forward_questions(self, batches):
         """train() mode, a list of the sampler's net_input dicts: the questions of one pass.  One reader-tower pass over all
         sequences (padded on the device to the widest batch, packed by run_tower), one question-tower pass over row 0 of
-        every question's input_ids_q, one reader_loss_multi call; two host round trips and one (seed, call) triple for the
-        pass.  -> {"loss": losses.sum(), "losses" fp32 [Q] (with gradients), "joint", "early" fp32 [Q]}.  A list of one dict
-        gives the bits of the dict route."""
+        every question's input_ids_q (the reference encodes B identical rows and uses q[0]), one loss call; two host round
+        trips and one (seed, call) triple for the pass.  -> {"loss": losses.sum(), "losses" fp32 [Q] (with gradients), "joint",
+        "early" fp32 [Q]}.  A pass of one question takes its tensors as they are (no copy) and the single-question loss
+        entry, whose bits reader_loss_multi gives at Q = 1."""
         if not self.training:
             raise ValueError("TrainableReader: a list of questions is a training pass; eval() takes one net_input dict")
         if not batches:
             raise ValueError("TrainableReader: an empty list of questions")
         for x in batches:
-            ids = x["input_ids"]
-            if not ids.is_cuda:
-                raise RuntimeError("TrainableReader expects CUDA tensors (the reference feeds move_to_cuda(batch))")
-            if ids.shape[0] == 0:
-                raise ValueError("TrainableReader: an empty batch")
-            if x["paragraph_mask"].shape != ids.shape:
-                raise ValueError(f"paragraph_mask {tuple(x['paragraph_mask'].shape)} must have the shape of input_ids "
-                                 f"{tuple(ids.shape)}")
+            self._check_inputs(x)
             if x["para_embed"].dtype != batches[0]["para_embed"].dtype:
                 raise ValueError("TrainableReader: the questions of a pass must share para_embed's dtype")
 
-        def stacked(key, rows=None, fill=0):      # the questions' [n, width] tensors under each other, padded on the right
+        def under(parts):                         # the questions' tensors under each other
+            return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+        def stacked(key, rows=None, fill=0):      # ... [n, width] tensors, padded on the right to the widest
             parts = [x[key] if rows is None else x[key][:rows] for x in batches]
             width = max(t.shape[1] for t in parts)
-            return torch.cat([torch.nn.functional.pad(t, (0, width - t.shape[1]), value=fill) for t in parts], 0)
+            return under([t if t.shape[1] == width else torch.nn.functional.pad(t, (0, width - t.shape[1]), value=fill)
+                          for t in parts])
 
         ids, pmask = stacked("input_ids"), stacked("paragraph_mask").to(torch.bool)
         p_hid, p_att, p_qa = self.hidden_dropout_prob, self.attention_probs_dropout_prob, self.qa_drop
@@ -261,17 +242,19 @@ class TrainableReader(torch.nn.Module):
         q = run_tower(self.retriever._flat, "bert_q", self.config, stacked("input_ids_q", rows=1),
                       stacked("input_mask_q", rows=1), proj="proj_q", drop=(p_hid, p_att, seed, (call + 1) & 0xFFFFFF),
                       deterministic=self.deterministic)
+        operands = (under([x["para_embed"] for x in batches]), under([x["top5000_labels"].reshape(-1) for x in batches]),
+                    stacked("start_positions", fill=-1), stacked("end_positions", fill=-1), geometry["para_offset"])
+        options = dict(cu_seqlens=cu, shared_norm=self.shared_norm, early=not self.drop_early, qa_drop=p_qa,
+                       dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
+        w, b = self._flat["qa_outputs.weight"], self._flat["qa_outputs.bias"]
+        if len(batches) == 1:       # the one branch on the pass length: the single entry takes no CSR arrays
+            out = reader_loss(hidden, w, b, q[0], *operands, **options)
+            return {"loss": out["loss"], "losses": out["loss"][None], "joint": out["joint"][None], "early": out["early"][None]}
         question_seq, question_para = [0], [0]
         for x in batches:
             question_seq.append(question_seq[-1] + x["input_ids"].shape[0])
             question_para.append(question_para[-1] + x["para_embed"].shape[0])
-        out = reader_loss_multi(hidden, self._flat["qa_outputs.weight"], self._flat["qa_outputs.bias"], q,
-                                torch.cat([x["para_embed"] for x in batches], 0),
-                                torch.cat([x["top5000_labels"].reshape(-1) for x in batches]),
-                                stacked("start_positions", fill=-1), stacked("end_positions", fill=-1), geometry["para_offset"],
-                                cu_seqlens=cu, question_seq=question_seq, question_para=question_para,
-                                shared_norm=self.shared_norm, early=not self.drop_early, qa_drop=p_qa,
-                                dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
+        out = reader_loss_multi(hidden, w, b, q, *operands, question_seq=question_seq, question_para=question_para, **options)
         return {"loss": out["losses"].sum(), "losses": out["losses"], "joint": out["joint"], "early": out["early"]}
 
     def inference_reader(self):

@@ -335,7 +335,7 @@ def test_reader_loss_multi_is_one_node_without_a_host_wait(gpu_device):
     finally:
         torch.cuda.set_sync_debug_mode("default")
     assert out["losses"].shape == (3,) and out["joint"].shape == (3,) and not out["early"].requires_grad
-    assert out["losses"].grad_fn.next_functions[0][0].name().startswith("_ReaderLossMulti")
+    assert out["losses"].grad_fn.next_functions[0][0].name().startswith("_ReaderLoss")
     low = run_multi(pack, dev)
     assert torch.equal(hidden.grad.cpu(), low["d_hidden"]) and torch.equal(q.grad.cpu(), low["d_q"])
     assert torch.equal(w.grad.cpu(), low["d_qa_w"]) and torch.equal(b.grad.cpu(), low["d_qa_b"])

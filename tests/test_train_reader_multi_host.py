@@ -54,6 +54,17 @@ def test_the_examples_of_the_documents():
     assert closes_pass(3, 6, 4, 3) and closes_pass(1, 7, 4, 3) and not closes_pass(2, 6, 4, 3)
 
 
+def test_one_question_per_pass_is_the_smallest_case_of_the_one_loop():
+    """The trainer has one loop body for every Q: at Q = 1 it must run every retrieved question as a pass of its own, at once."""
+    n = 12
+    for G in (1, 4):
+        failed = [6]                    # inside a window at G = 4 (the update slots are 3, 7, 11)
+        assert not is_update_step(6, 4)
+        assert pass_schedule(n, G, 1, failed) == [[b] for b in range(1, n + 1) if b not in failed]
+        assert all(closes_pass(1, b, G, 1) for b in range(1, 3 * n))
+    assert "questions_per_pass" not in train_reader.reader_fingerprint_extra(_args("--questions-per-pass", "1"))
+
+
 def test_update_schedule_is_unchanged():
     assert update_schedule(8, 2) == [1, 3, 5, 7]
     assert update_schedule(8, 2, failed=[3]) == [1, 5, 7]

@@ -156,20 +156,65 @@ def same_gradient_bits(a, b):
             assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), k
 
 
+def composed_by_hand(model, x, scale=LOSS_SCALE):
+    """One question through the pieces a pass is made of, put together here and not by the module: run_tower for the reader
+    tower, run_tower on row 0 of the question inputs, reader_loss through the single-question C entry; the dropout triple is
+    read from model.dropout_state() and the state is left as it is.  -> (reader_loss's dict, the parameters' gradients)"""
+    from proqa_amd.reader_loss import reader_loss
+    from proqa_amd.trainable import run_tower
+    from proqa_amd.trainable_reader import _PARAGRAPH_MESSAGE, _paragraph_geometry
+    model.zero_grad(set_to_none=True)
+    seed, call = model.dropout_state()
+    p_hid, p_att = model.hidden_dropout_prob, model.attention_probs_dropout_prob
+    pmask = x["paragraph_mask"].to(torch.bool)
+    geometry = {}
+
+    def paragraph_probe(lens):
+        geometry["para_offset"], bad = _paragraph_geometry(pmask, lens)
+        return bad, _PARAGRAPH_MESSAGE
+
+    hidden, cu, _, max_len = run_tower(model._flat, "bert", model.config, x["input_ids"], x["input_mask"],
+                                       type_ids=x["segment_ids"], drop=(p_hid, p_att, seed, call), probe_extra=paragraph_probe,
+                                       deterministic=model.deterministic)
+    q = run_tower(model.retriever._flat, "bert_q", model.config, x["input_ids_q"][:1], x["input_mask_q"][:1], proj="proj_q",
+                  drop=(p_hid, p_att, seed, (call + 1) & 0xFFFFFF), deterministic=model.deterministic)
+    out = reader_loss(hidden, model._flat["qa_outputs.weight"], model._flat["qa_outputs.bias"], q, x["para_embed"],
+                      x["top5000_labels"], x["start_positions"], x["end_positions"], geometry["para_offset"], cu_seqlens=cu,
+                      shared_norm=model.shared_norm, early=not model.drop_early, qa_drop=model.qa_drop,
+                      dropout_state=(seed, (call + 2) & 0xFFFFFF), max_seq_len=max_len)
+    (out["loss"] * scale).backward()
+    return out, {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in model.named_parameters()}
+
+
 def test_a_list_of_one_question_is_the_dict_route(gpu_device):
+    """model(dict), model([dict]) and model((dict,)) against the single-question route composed by hand, bit for bit; once
+    without dropout, once with all three rates set (the head's mask coordinate on a pack of one is the question's own row)."""
+    from proqa_amd.trainable_reader import CALLS_PER_FORWARD
     sd, *_ = reference()
-    model = make_model(gpu_device, sd, deterministic=True)
-    for batch in questions():
-        dev_batch = on(gpu_device, batch)
-        one, grads_one = gradients(model, dev_batch)
-        lst, grads_lst = gradients(model, [dev_batch])
-        assert set(lst) == {"loss", "losses", "joint", "early"} and lst["losses"].shape == (1,)
-        assert lst["loss"].dim() == 0 and lst["loss"].requires_grad and not lst["joint"].requires_grad
-        for k in ("loss", "joint", "early"):
-            assert one[k].item() == lst[k].reshape(-1)[0].item(), k
-        same_gradient_bits(grads_one, grads_lst)
-        _, grads_tuple = gradients(model, (dev_batch,))
-        same_gradient_bits(grads_one, grads_tuple)
+    for rates in ({}, dict(hidden_dropout_prob=0.1, attention_probs_dropout_prob=0.1, qa_drop=0.1)):
+        model = make_model(gpu_device, sd, deterministic=True, dropout_seed=11, **rates)
+        for batch in questions():
+            dev_batch = on(gpu_device, batch)
+            state = model.dropout_state()
+            want, grads_want = composed_by_hand(model, dev_batch)
+            assert model.dropout_state() == state
+            for net_input in (dev_batch, [dev_batch], (dev_batch,)):
+                model.set_dropout_state(state)
+                got, grads = gradients(model, net_input)
+                assert model.dropout_state() == (state[0], state[1] + (CALLS_PER_FORWARD if rates else 0))
+                if isinstance(net_input, dict):
+                    assert set(got) == {"loss", "joint", "early"} and all(got[k].dim() == 0 for k in got)
+                else:
+                    assert set(got) == {"loss", "losses", "joint", "early"} and got["losses"].shape == (1,)
+                    assert torch.equal(got["losses"].detach().view(torch.int32), got["loss"].detach().reshape(1).view(torch.int32))
+                assert got["loss"].dim() == 0 and got["loss"].requires_grad and not got["joint"].requires_grad
+                for k in ("loss", "joint", "early"):
+                    assert torch.equal(want[k].detach().reshape(1).view(torch.int32),
+                                       got[k].detach().reshape(1).view(torch.int32)), (k, rates)
+                same_gradient_bits(grads_want, grads)
+        if rates:       # the masks were really drawn: another call gives another loss
+            other, _ = gradients(model, dev_batch)
+            assert other["loss"].item() != want["loss"].item()
 
 
 def test_three_questions_match_float64(gpu_device):
