@@ -164,6 +164,22 @@ int proqa_sampler_collect_device(proqa_index* idx, const int64_t* ids_dev, int64
                                  int64_t n_gold, int head, void* rows_out_dev, int out_dtype, int32_t* labels_out_dev,
                                  int64_t* record_dev, void* stream);
 
+/* proqa_sampler_collect_device for the n_questions result rows of one proqa_index_search_device call, in one launch per
+ * 64 questions: ids_dev is int64 [n_questions, k] and, for every question q,
+ *   rows_out [q], labels_out [q], record_dev [q]  ([n_questions, k, d], [n_questions, k] int32, [n_questions, 2 + head] int64)
+ * hold exactly what the single entry writes for ids_dev[q] and the gold list gold_dev[gold_begin[q] .. gold_begin[q] +
+ * gold_count[q]).  gold_dev is one buffer of n_gold int64 ids (the lists of all questions; strictly ascending within a
+ * list; NULL when n_gold == 0); gold_begin and gold_count are HOST arrays of n_questions entries.  They are checked here
+ * (a list that leaves the buffer is PROQA_EINVAL, before anything is launched) and reach the kernel by value in its
+ * arguments: the call copies nothing in either direction.  Lists may be empty, may overlap and may repeat.  head is in
+ * [0, 64]; k == 0 writes the records only; n_questions == 0 does nothing.  Integer sums only: the same bits from run to
+ * run.  Asynchronous on `stream`; the library zeroes the counts of every record on it, so record_dev is written on the
+ * stream from its first word on and needs no preparation.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive). */
+int proqa_sampler_collect_multi_device(proqa_index* idx, const int64_t* ids_dev, int64_t n_questions, int64_t k, int64_t idx_offset,
+                                       const int64_t* gold_dev, int64_t n_gold, const int64_t* gold_begin, const int64_t* gold_count,
+                                       int head, void* rows_out_dev, int out_dtype, int32_t* labels_out_dev, int64_t* record_dev,
+                                       void* stream);
+
 /* statistics of the last search on this handle (for tests and the benchmark) */
 typedef struct proqa_search_stats {
   int32_t rounds;            /* filter+merge rounds launched */

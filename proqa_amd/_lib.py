@@ -126,6 +126,9 @@ SIGNATURES = {
     "proqa_index_reconstruct_batch_device": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     "proqa_sampler_collect_device": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int,
                                              c_void_p, c_void_p, c_void_p]),
+    "proqa_sampler_collect_multi_device": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                                   ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_int, c_void_p, c_int,
+                                                   c_void_p, c_void_p, c_void_p]),
     "proqa_index_last_stats": (c_int, [c_void_p, ctypes.POINTER(SearchStats)]),
     "proqa_index_set_profiling": (c_int, [c_void_p, c_int]),
     "proqa_index_configure": (c_int, [c_void_p, c_int, c_int]),

@@ -2222,20 +2222,50 @@ int proqa_index_reconstruct_batch_device(proqa_index* idx, const int64_t* ids_de
 int proqa_sampler_collect_device(proqa_index* idx, const int64_t* ids_dev, int64_t k, int64_t idx_offset, const int64_t* gold_dev,
                                  int64_t n_gold, int head, void* rows_out_dev, int out_dtype, int32_t* labels_out_dev,
                                  int64_t* record_dev, void* stream) {
+  const int64_t begin = 0;      // one question that owns the whole list
+  return proqa_sampler_collect_multi_device(idx, ids_dev, 1, k, idx_offset, gold_dev, n_gold, &begin, &n_gold, head, rows_out_dev,
+                                            out_dtype, labels_out_dev, record_dev, stream);
+}
+
+int proqa_sampler_collect_multi_device(proqa_index* idx, const int64_t* ids_dev, int64_t n_questions, int64_t k, int64_t idx_offset,
+                                       const int64_t* gold_dev, int64_t n_gold, const int64_t* gold_begin, const int64_t* gold_count,
+                                       int head, void* rows_out_dev, int out_dtype, int32_t* labels_out_dev, int64_t* record_dev,
+                                       void* stream) {
   if (!idx) return fail(PROQA_EINVAL, "sampler_collect: idx is NULL");
-  if (k < 0 || (k > 0 && (!ids_dev || !rows_out_dev || !labels_out_dev)))
+  if (n_questions < 0 || n_questions > INT32_MAX || (n_questions > 0 && (!gold_begin || !gold_count)))
+    return fail(PROQA_EINVAL, "sampler_collect: n_questions=%lld or NULL bounds", (long long)n_questions);
+  if (k < 0 || (k > 0 && n_questions > 0 && (!ids_dev || !rows_out_dev || !labels_out_dev)))
     return fail(PROQA_EINVAL, "sampler_collect: k=%lld or NULL argument", (long long)k);
   if (head < 0 || head > 64) return fail(PROQA_EINVAL, "sampler_collect: head=%d is outside [0, 64]", head);
-  if (n_gold < 0 || n_gold > INT32_MAX || (n_gold > 0 && !gold_dev))
-    return fail(PROQA_EINVAL, "sampler_collect: n_gold=%lld or NULL gold list", (long long)n_gold);
-  if (!record_dev) return fail(PROQA_EINVAL, "sampler_collect: record is NULL");
+  if (n_gold < 0 || (n_gold > 0 && !gold_dev))
+    return fail(PROQA_EINVAL, "sampler_collect: n_gold=%lld or NULL gold buffer", (long long)n_gold);
+  if (n_questions > 0 && !record_dev) return fail(PROQA_EINVAL, "sampler_collect: record is NULL");
   if (out_dtype != PROQA_F16 && out_dtype != PROQA_F32) return fail(PROQA_EINVAL, "sampler_collect: bad dtype %d", out_dtype);
+  // the lists are checked here, on the host, so that the kernel reads nothing outside the gold buffer
+  for (int64_t q = 0; q < n_questions; ++q)
+    if (gold_begin[q] < 0 || gold_count[q] < 0 || gold_count[q] > INT32_MAX || gold_begin[q] > n_gold ||
+        gold_count[q] > n_gold - gold_begin[q])
+      return fail(PROQA_EINVAL, "sampler_collect: the gold list of question %lld, [%lld, +%lld), leaves the %lld ids of the buffer",
+                  (long long)q, (long long)gold_begin[q], (long long)gold_count[q], (long long)n_gold);
+  if (n_questions == 0) return PROQA_OK;
   PROQA_ON_DEVICE(idx->device);
   hipStream_t st = (hipStream_t)stream;
-  PROQA_HIP(hipMemsetAsync(record_dev, 0, 2 * sizeof(int64_t), st));   // the kernel's integer atomics add to these two
-  PROQA_HIP(launch_sampler_collect_rows(idx->xb, idx->exact ? idx->xb32 : nullptr, idx->n, (const long long*)ids_dev, k, idx_offset,
-                                        (const long long*)gold_dev, (int)n_gold, head, rows_out_dev, out_dtype == PROQA_F32,
-                                        labels_out_dev, (long long*)record_dev, st));
+  const size_t rec = 2 + (size_t)head;
+  const size_t row_bytes = (size_t)kDim * (out_dtype == PROQA_F32 ? 4 : 2);
+  // the kernel's integer atomics add to the first two words of every record; it writes the rest
+  PROQA_HIP(hipMemsetAsync(record_dev, 0, (size_t)n_questions * rec * sizeof(int64_t), st));
+  for (int64_t q0 = 0; q0 < n_questions; q0 += kCollectMaxQuestions) {     // the bounds go by value: 64 questions a launch
+    CollectQuestions qs = {};
+    qs.n = (int)std::min<int64_t>(kCollectMaxQuestions, n_questions - q0);
+    for (int i = 0; i < qs.n; ++i) {
+      qs.begin[i] = gold_begin[q0 + i];
+      qs.count[i] = (int)gold_count[q0 + i];
+    }
+    PROQA_HIP(launch_sampler_collect_rows(idx->xb, idx->exact ? idx->xb32 : nullptr, idx->n,
+                                          k ? (const long long*)ids_dev + q0 * k : nullptr, k, idx_offset, (const long long*)gold_dev, qs,
+                                          head, k ? (char*)rows_out_dev + (size_t)q0 * k * row_bytes : nullptr, out_dtype == PROQA_F32,
+                                          k ? labels_out_dev + q0 * k : nullptr, (long long*)record_dev + q0 * rec, st));
+  }
   return PROQA_OK;
 }
 

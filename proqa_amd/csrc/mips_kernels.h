@@ -185,10 +185,20 @@ hipError_t launch_gather_index_rows(const void* xb16, const float* xb32, long lo
                                     long long idx_offset, void* out, bool out_f32, hipStream_t st);
 // launch_gather_index_rows plus labels[r] = (ids[r] is a row of the index and occurs in gold[0..n_gold), ascending int64 ids)
 // and record[2 + head] = {rows of the index among ids, sum of labels, ids[0..head) with -1 past n}; the caller zeroes
-// record[0..2) on st before the launch (integer atomics add to it)
+// record[0..2) on st before the launch (integer atomics add to it).
+// With a question dimension: ids [qs.n, n], out [qs.n, n, d], labels [qs.n, n], record [qs.n, 2 + head], and question q
+// tests against gold[qs.begin[q] .. qs.begin[q] + qs.count[q]).  The bounds travel by value in the kernel arguments (no
+// copy in either direction), so one launch takes at most kCollectMaxQuestions questions; the caller has checked that
+// every list lies inside the gold buffer.
+constexpr int kCollectMaxQuestions = 64;
+struct CollectQuestions {
+  long long begin[kCollectMaxQuestions];   // first id of the question's gold list, in ids of `gold`
+  int count[kCollectMaxQuestions];         // ids the list holds (0: an empty list, nothing of gold is read)
+  int n;                                   // the number of questions, 1 .. kCollectMaxQuestions
+};
 hipError_t launch_sampler_collect_rows(const void* xb16, const float* xb32, long long n_index, const long long* ids, long long n,
-                                       long long idx_offset, const long long* gold, int n_gold, int head, void* out, bool out_f32,
-                                       int* labels, long long* record, hipStream_t st);
+                                       long long idx_offset, const long long* gold, const CollectQuestions& qs, int head, void* out,
+                                       bool out_f32, int* labels, long long* record, hipStream_t st);
 // *flag = 1 if any of the nq lists holds fewer than `want` keys
 hipError_t launch_flag_short_lists(const unsigned* run_n, long long nq, unsigned want, unsigned* flag, hipStream_t st);
 // exact top-k of rows [0, n_rows) (n_rows <= kBootstrapMaxRows, k <= kBootstrapMaxK) for every query: run_keys / run_n /

@@ -2326,11 +2326,23 @@ __global__ void gather_index_rows(const _Float16* __restrict__ xb16, const float
 // ids[r] in gold (int64, strictly ascending, id space), plus record = {#live, sum of labels, ids[0..head) padded with -1}.
 // One thread per 16 bytes of output row; the lane that holds a row's first piece searches gold.  The two counts are
 // reduced per wave (ballot + popcount) and added with integer atomics to the record the caller zeroed on the stream:
-// integer sums commute, so the record is the same bits every run.  Grid covers max(n * per_row, head) threads.
+// integer sums commute, so the record is the same bits every run.  Grid x covers max(n * per_row, head) threads.
+//
+// The question dimension (struct CollectQuestions, passed by value: no copy in either direction): blockIdx.y is the
+// question, which owns ids[q * n ..), out[q * n ..), labels[q * n ..), record[q * (2 + head) ..) and the ids
+// gold[begin[q] .. begin[q] + count[q]) of the one gold buffer.  A block, and so a wave, holds rows of one question only:
+// its ballots count that question's rows and its atomics land in that question's record.  The single-question call is
+// n_questions = 1 with begin 0: every pointer offset is zero and every index is the one this kernel has always formed.
 __global__ void sampler_collect_rows(const _Float16* __restrict__ xb16, const float* __restrict__ xb32, long long n_index,
                                      const long long* __restrict__ ids, long long n, long long idx_offset,
-                                     const long long* __restrict__ gold, int n_gold, int head, void* out, int out_f32,
+                                     const long long* __restrict__ gold, CollectQuestions qs, int head, void* out, int out_f32,
                                      int* __restrict__ labels, long long* __restrict__ record) {
+  const int qi = blockIdx.y;       // uniform over the block: the loads of the bounds are scalar
+  const int n_gold = qs.count[qi];
+  gold += qs.begin[qi];
+  ids += qi * n;
+  labels += qi * n;
+  record += (long long)qi * (2 + head);
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t < head) record[2 + t] = t < n ? ids[t] : -1ll;
   const int per_row = out_f32 ? kDim / 4 : kDim / 8;      // 16-byte pieces per output row
@@ -2347,7 +2359,7 @@ __global__ void sampler_collect_rows(const _Float16* __restrict__ xb16, const fl
     if (!out_f32) {
       f16x8 v = {0};
       if (live) v = *(const f16x8*)(xb16 + row * kDim + c * 8);
-      *(f16x8*)((_Float16*)out + r * kDim + c * 8) = v;
+      *(f16x8*)((_Float16*)out + (qi * n + r) * kDim + c * 8) = v;
     } else {
       f32x4 v = {0.f, 0.f, 0.f, 0.f};
       if (live) {
@@ -2358,7 +2370,7 @@ __global__ void sampler_collect_rows(const _Float16* __restrict__ xb16, const fl
           v = f32x4{(float)src[0], (float)src[1], (float)src[2], (float)src[3]};
         }
       }
-      *(f32x4*)((float*)out + r * kDim + c * 4) = v;
+      *(f32x4*)((float*)out + (qi * n + r) * kDim + c * 4) = v;
     }
   }
   const bool owner = in_range && c == 0;
@@ -2831,13 +2843,14 @@ hipError_t launch_gather_index_rows(const void* xb16, const float* xb32, long lo
 }
 
 hipError_t launch_sampler_collect_rows(const void* xb16, const float* xb32, long long n_index, const long long* ids, long long n,
-                                       long long idx_offset, const long long* gold, int n_gold, int head, void* out, bool out_f32,
-                                       int* labels, long long* record, hipStream_t st) {
+                                       long long idx_offset, const long long* gold, const CollectQuestions& qs, int head, void* out,
+                                       bool out_f32, int* labels, long long* record, hipStream_t st) {
+  if (qs.n < 1 || qs.n > kCollectMaxQuestions) return hipErrorInvalidValue;
   const long long pieces = n * (out_f32 ? kDim / 4 : kDim / 8);
   const long long threads = pieces > head ? pieces : head;
   if (threads == 0) return hipSuccess;
-  hipLaunchKernelGGL(sampler_collect_rows, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, (const _Float16*)xb16, xb32,
-                     n_index, ids, n, idx_offset, gold, n_gold, head, out, out_f32 ? 1 : 0, labels, record);
+  hipLaunchKernelGGL(sampler_collect_rows, dim3((unsigned)((threads + 255) / 256), (unsigned)qs.n), dim3(256), 0, st,
+                     (const _Float16*)xb16, xb32, n_index, ids, n, idx_offset, gold, qs, head, out, out_f32 ? 1 : 0, labels, record);
   return hipGetLastError();
 }
 

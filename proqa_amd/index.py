@@ -204,6 +204,41 @@ class IndexFlatIP:
                 record.data_ptr(), _lib.current_stream_ptr()))
         return rows, labels, record
 
+    def collect_labeled_multi_device(self, ids, gold_rows, gold_begin, gold_count, head, dtype=None, idx_offset=0):
+        """collect_labeled_device for the Q rows of one search_device result, in one launch: ids int64 CUDA tensor [Q, k],
+        gold_rows the int64 CUDA buffer that holds every question's list (or None), gold_begin / gold_count: Q host
+        integers each, question q's list being gold_rows[gold_begin[q] : gold_begin[q] + gold_count[q]] (strictly
+        ascending; empty lists, shared lists are legal) -> (rows [Q, k, d], labels int32 [Q, k], records int64
+        [Q, 2 + head]), row q of each being what collect_labeled_device returns for ids[q] and that list.  The bounds go
+        to the kernel by value: nothing is copied to or from the GPU."""
+        import torch
+        if not ids.is_cuda or ids.dtype != torch.int64:
+            raise ValueError("collect_labeled_multi_device expects an int64 CUDA tensor")
+        if gold_rows is not None and (not gold_rows.is_cuda or gold_rows.dtype != torch.int64 or gold_rows.dim() != 1):
+            raise ValueError("collect_labeled_multi_device expects gold_rows as a 1-D int64 CUDA tensor")
+        if ids.dim() != 2:
+            raise ValueError(f"ids must have shape [Q, k], got {tuple(ids.shape)}")
+        nq, k = ids.shape
+        begin, count = [int(b) for b in gold_begin], [int(c) for c in gold_count]
+        if len(begin) != nq or len(count) != nq:
+            raise ValueError(f"gold_begin and gold_count must hold one entry per question ({nq}), got {len(begin)} and {len(count)}")
+        head = int(head)            # outside [0, 64]: the library's PROQA_EINVAL
+        dtype = dtype or torch.float16
+        ids = ids.contiguous()
+        n_gold = 0 if gold_rows is None else gold_rows.numel()
+        gold_rows = gold_rows.contiguous() if n_gold else None
+        rows = torch.empty((nq, k, self.d), dtype=dtype, device=ids.device)
+        labels = torch.empty((nq, k), dtype=torch.int32, device=ids.device)
+        records = torch.empty((nq, 2 + min(max(head, 0), 64)), dtype=torch.int64, device=ids.device)
+        some = nq * k > 0
+        with torch.cuda.device(ids.device):
+            _lib.check(self._lib.proqa_sampler_collect_multi_device(
+                self._h, ids.data_ptr() if some else None, nq, k, int(idx_offset), gold_rows.data_ptr() if n_gold else None,
+                n_gold, (ctypes.c_int64 * nq)(*begin), (ctypes.c_int64 * nq)(*count), head,
+                rows.data_ptr() if some else None, _torch_dtype_code(rows), labels.data_ptr() if some else None,
+                records.data_ptr() if nq else None, _lib.current_stream_ptr()))
+        return rows, labels, records
+
     # -- introspection / tuning ---------------------------------------------------------
     def last_stats(self):
         st = _lib.SearchStats()

@@ -21,6 +21,11 @@ a retriever whose get_embed takes (check_mask, seq_lens_host) -- BertForRetrieve
 host round trip of its own; it is measured in tests/test_reader_sampler_gpu.py, not taken from `transfers`.  The record is
 not the only wait for the device: search_device at k = 5000 synchronises its stream inside the library.
 
+The three launches take several questions as they take one (retrieve_many: one tower pass over the right-padded ids, one
+search, IndexFlatIP.collect_labeled_multi_device, one copy of the records down), and retrieve is the one-question case.
+load(lookahead=...) retrieves in one such step the questions its caller will draw before the retriever's weights can next
+change -- the caller says how many -- and yields them one by one.
+
 Host side, for the top `k` passages: qa_utils (char_to_word_offset, orig_to_tok_index, match_answer_span,
 find_ans_span_with_char_offsets) over the native WordPiece tokenizer; matched strings are sorted (the reference iterates a
 `set`), and prepared passages are cached by row.  An index with fewer than 5000 rows yields the rows it has.  No CPU path.
@@ -175,6 +180,9 @@ class OnlineSampler:
         for slot, t in enumerate(self._q_ids):
             padded[slot, :len(t)] = t
         self._q_ids_dev = torch.from_numpy(padded).to(self.device)
+        # and their masks (a prefix of ones per row), for the sampling step of several questions of different lengths
+        lengths = np.asarray([len(t) for t in self._q_ids], dtype=np.int64).reshape(-1, 1)
+        self._q_mask_dev = torch.from_numpy(np.arange(width, dtype=np.int64)[None, :] < lengths).to(self.device)
         self._host_lens = {}       # id(retriever) -> its get_embed takes (check_mask, seq_lens_host)
         self.basic_tokenizer = SimpleTokenizer()
         self.wordpieces = WordPieces(tokenizer)
@@ -183,10 +191,12 @@ class OnlineSampler:
         self.cache_passages = max(int(cache_passages), MAX_HEAD)
         self._answer_pieces = {}   # matched string -> its WordPiece tokens
         self._pinned = None
+        self._pinned_copied = None     # event behind the last copy out of _pinned
         self.sync_stages = False   # True: a device synchronise after every stage, so that `seconds` splits device time too
         self.transfers = {"d2h": 0, "h2d": 0}      # the copies this module issues; the tests count the real ones in a profile
         self.seconds = {"encode": 0.0, "search_collect": 0.0, "host_text": 0.0, "h2d": 0.0}
         self.questions_seen = 0
+        self.groups = 0            # sampling steps (retrieve_many calls): each is one tower pass, search, collect and record
 
     def shuffle(self):
         # the same draws from `random` and the same arrangement as random.shuffle(self.qa_data): shuffle() swaps by
@@ -234,6 +244,10 @@ class OnlineSampler:
         return passage_spans(prep, answers, self.basic_tokenizer, self._tokenize_answer, self.regex)
 
     def _pinned_buffer(self, n):
+        # the buffer is written again only once its last copy up has run: within a group of load(lookahead=...) no
+        # record copy stands between two batches to wait for it
+        if self._pinned_copied is not None:
+            self._pinned_copied.synchronize()
         if self._pinned is None or self._pinned.numel() < n:
             self._pinned = torch.empty(max(n, 1 << 14), dtype=torch.int64).pin_memory()
         return self._pinned[:n]
@@ -275,6 +289,9 @@ class OnlineSampler:
         dev = torch.empty(flat.numel(), dtype=torch.int64, device=self.device)
         dev.copy_(flat, non_blocking=True)          # the one host-to-device copy of the batch
         self.transfers["h2d"] += 1
+        if self._pinned_copied is None:
+            self._pinned_copied = torch.cuda.Event()
+        self._pinned_copied.record(torch.cuda.current_stream(self.device))
         if self.sync_stages:
             torch.cuda.current_stream(self.device).synchronize()
         self.seconds["h2d"] += time.perf_counter() - t0
@@ -294,23 +311,38 @@ class OnlineSampler:
     # -- the sampler ---------------------------------------------------------------------------------------------------
     def retrieve(self, retriever, question, head):
         """encode + search + collect of one question -> (q_ids, para_embed [n_live, 128], labels int32 [n_live],
-        n_live, sum of labels, the first min(head, n_live) rows as a list).  The record is this method's one device-to-host copy."""
+        n_live, sum of labels, the first min(head, n_live) rows as a list).  The record is this method's one device-to-host
+        copy.  It is retrieve_many of that one question."""
+        return self.retrieve_many(retriever, [question], head)[0]
+
+    def retrieve_many(self, retriever, questions, head):
+        """encode + search + collect of several questions in ONE sampling step -- one pass of the question tower over their
+        right-padded token ids, one search_device, one collect_labeled_multi_device, one copy of the records to the host --
+        -> [retrieve's tuple for every question]; para_embed and labels are views into the step's buffers.  The questions
+        are retrieved with the weights the retriever holds now, so the caller groups only questions between which no weight
+        changes.  A question may occur twice (both read one gold slot)."""
         t0 = time.perf_counter()
-        slot = self._gold_slot.get(hash_question(question))
-        if slot is None:
-            raise ValueError(f"question {question!r} is not one of the sampler's training questions")
-        q_ids = self._q_ids[slot]
+        if not questions:
+            return []
+        slots = [self._gold_slot.get(hash_question(question)) for question in questions]
+        for slot, question in zip(slots, questions):
+            if slot is None:
+                raise ValueError(f"question {question!r} is not one of the sampler's training questions")
+        q_ids = [self._q_ids[slot] for slot in slots]
+        lens = [len(t) for t in q_ids]
+        width = max(lens)
         with torch.no_grad():
-            ids = self._q_ids_dev[slot:slot + 1, :len(q_ids)]        # uploaded at construction: nothing goes up here
-            if ids.shape[1] != self._q_ids_dev.shape[1]:
-                ids = ids.contiguous()
-            mask = torch.ones_like(ids, dtype=torch.bool)
+            # uploaded at construction: nothing goes up here.  A row is zero past its question, so rows cut to the longest
+            # question are right-padded
+            ids = torch.cat([self._q_ids_dev[slot:slot + 1, :width] for slot in slots])
+            mask = torch.cat([self._q_mask_dev[slot:slot + 1, :width] for slot in slots])
             takes_lens = self._host_lens.get(id(retriever))
             if takes_lens is None:
                 params = inspect.signature(retriever.get_embed).parameters
                 takes_lens = self._host_lens[id(retriever)] = "seq_lens_host" in params and "check_mask" in params
-            # the mask is all ones and the length is known here: a tower that takes host lengths makes no host round trip
-            extra = {"check_mask": False, "seq_lens_host": [len(q_ids)]} if takes_lens else {}
+            # the mask is a prefix of ones per row and the lengths are known here: a tower that takes host lengths makes
+            # no host round trip
+            extra = {"check_mask": False, "seq_lens_host": lens} if takes_lens else {}
             was_training = bool(getattr(retriever, "training", False))
             if was_training:
                 retriever.eval()
@@ -319,43 +351,70 @@ class OnlineSampler:
             finally:
                 if was_training:
                     retriever.train()
-        q = q.reshape(1, -1)
+        q = q.reshape(len(slots), -1)
         if self.sync_stages:
             torch.cuda.current_stream(self.device).synchronize()
         t1 = time.perf_counter()
         _, I = self.index.search_device(q, SEARCH_K)
-        gold = self._gold_rows[int(self._gold_offsets[slot]):int(self._gold_offsets[slot + 1])]
+        begin = [int(self._gold_offsets[slot]) for slot in slots]
+        count = [int(self._gold_offsets[slot + 1]) - b for slot, b in zip(slots, begin)]
         dtype = torch.float32 if self.index.exact_f32 else torch.float16
-        rows, labels, record = self.index.collect_labeled_device(I.reshape(-1), gold if gold.numel() else None, head, dtype)
-        record = record.cpu().tolist()              # the one device-to-host copy of the sampling step (it synchronises)
+        rows, labels, records = self.index.collect_labeled_multi_device(
+            I, self._gold_rows if self._gold_rows.numel() else None, begin, count, head, dtype)
+        records = records.cpu().tolist()            # the one device-to-host copy of the sampling step (it synchronises)
         self.transfers["d2h"] += 1
+        self.groups += 1
         t2 = time.perf_counter()
         self.seconds["encode"] += t1 - t0
         self.seconds["search_collect"] += t2 - t1
-        n_live, n_gold = record[0], record[1]
-        return q_ids, rows[:n_live], labels[:n_live], n_live, n_gold, [r for r in record[2:] if r >= 0]
+        out = []
+        for i, record in enumerate(records):
+            n_live, n_gold = record[0], record[1]
+            out.append((q_ids[i], rows[i, :n_live], labels[i, :n_live], n_live, n_gold, [r for r in record[2:] if r >= 0]))
+        return out
 
-    def load(self, retriever, k=5, start=0):
+    def _batch(self, qa, retrieved):
+        """the host text work of one retrieved question: {} when neither its top 5000 nor its top k passages carry the
+        answer, else the reference's batch with the tensors of net_input on the device"""
+        q_ids, para_embed, labels, n_live, n_gold, top_rows = retrieved
+        t0 = time.perf_counter()
+        preps = self._prepared(top_rows)
+        spans = [self._spans(p, qa["answer"]) for p in preps]
+        if not preps or (n_gold == 0 and not any(c for c, _, _ in spans)):
+            self.seconds["host_text"] += time.perf_counter() - t0
+            return {}
+        h2d_before = self.seconds["h2d"]
+        batch = self._collate(qa, q_ids, preps, spans)
+        self.seconds["host_text"] += time.perf_counter() - t0 - (self.seconds["h2d"] - h2d_before)
+        batch["net_input"]["para_embed"] = para_embed
+        batch["net_input"]["top5000_labels"] = labels
+        return batch
+
+    def load(self, retriever, k=5, start=0, lookahead=None):
         """Yields, per question, {} when neither its top 5000 nor its top k passages carry the answer, else the
         reference's batch with the tensors of net_input on the device.  start: the first `start` questions of the current
-        order are left out (a resumed epoch)."""
+        order are left out (a resumed epoch).  lookahead: None retrieves question by question; else a callable that returns
+        how many questions, counting the next one, will be drawn before the retriever's weights can next change.  It is asked
+        whenever every retrieved question has been yielded; that many questions (at most what the epoch still holds) are
+        then retrieved in one retrieve_many and yielded one by one, para_embed and top5000_labels being views into the
+        group's buffers."""
         if not 0 < k <= MAX_HEAD:
             raise ValueError(f"OnlineSampler.load: k must be in [1, {MAX_HEAD}], got {k}")
         if not 0 <= start <= len(self.qa_data):
             raise ValueError(f"OnlineSampler.load: start must be in [0, {len(self.qa_data)}], got {start}")
-        for qa in self.qa_data[start:] if start else self.qa_data:
-            self.questions_seen += 1
-            q_ids, para_embed, labels, n_live, n_gold, top_rows = self.retrieve(retriever, qa["question"], k)
-            t0 = time.perf_counter()
-            preps = self._prepared(top_rows)
-            spans = [self._spans(p, qa["answer"]) for p in preps]
-            if not preps or (n_gold == 0 and not any(c for c, _, _ in spans)):
-                self.seconds["host_text"] += time.perf_counter() - t0
-                yield {}
-                continue
-            h2d_before = self.seconds["h2d"]
-            batch = self._collate(qa, q_ids, preps, spans)
-            self.seconds["host_text"] += time.perf_counter() - t0 - (self.seconds["h2d"] - h2d_before)
-            batch["net_input"]["para_embed"] = para_embed
-            batch["net_input"]["top5000_labels"] = labels
-            yield batch
+        todo = self.qa_data[start:] if start else self.qa_data
+        if lookahead is None:
+            for qa in todo:
+                self.questions_seen += 1
+                yield self._batch(qa, self.retrieve(retriever, qa["question"], k))
+            return
+        at = 0
+        while at < len(todo):
+            n = int(lookahead())
+            if n < 1:
+                raise ValueError(f"OnlineSampler.load: lookahead() must return at least 1, got {n}")
+            group = todo[at:at + n]
+            at += len(group)
+            for qa, retrieved in zip(group, self.retrieve_many(retriever, [qa["question"] for qa in group], k)):
+                self.questions_seen += 1
+                yield self._batch(qa, retrieved)

@@ -25,6 +25,11 @@ from the sampler one after another and then run through ONE forward (TrainableRe
 fused loss call) and one backward; pass_schedule() is the grouping rule, and Q = 1, the reference's loop, is its smallest
 case.  The optimisation step is the one of the questions run one after another; with --gradient_accumulation_steps 1 every
 pass holds one question.
+--sampler-lookahead W (default 1): the sampler retrieves up to W questions in one sampling step -- one question-tower pass, one
+search, one collect launch, one record copy (OnlineSampler.retrieve_many) -- never past the next update slot, so every
+question is retrieved with the weights its own retrieval would have read; retrieval_groups() is the grouping rule, and W = 1
+is today's loop, untouched.  A tower pass over W questions need not give the fp16 bits of W passes over one, so a run with
+W > 1 is a function of (data, seed, checkpoint, W), not the W = 1 run's bits.
 """
 import argparse
 import json
@@ -120,6 +125,9 @@ def build_parser():
     p.add_argument("--questions-per-pass", default=1, type=int,
                    help="questions of one accumulation window that share a tower pass and one fused loss call (1: one question "
                         "per pass); the optimisation step is the same, so it only pays with --gradient_accumulation_steps > 1")
+    p.add_argument("--sampler-lookahead", default=1, type=int,
+                   help="questions the sampler retrieves in one sampling step (one tower pass, one search, one collect); a "
+                        "group never crosses an update slot, so it only pays with --gradient_accumulation_steps > 1")
     from .config import STATE_FLAGS, add_flags
     return add_flags(p, STATE_FLAGS)       # --save-state, --stop-after-updates, --resume, --digest-every
 
@@ -161,6 +169,8 @@ def check_args(args):
         raise ValueError(f"Invalid gradient_accumulation_steps parameter: {args.gradient_accumulation_steps}, should be >= 1")
     if args.questions_per_pass < 1:
         raise ValueError(f"Invalid questions_per_pass parameter: {args.questions_per_pass}, should be >= 1")
+    if args.sampler_lookahead < 1:
+        raise ValueError(f"Invalid sampler_lookahead parameter: {args.sampler_lookahead}, should be >= 1")
     per_question = int(args.train_batch_size / args.accumulate_gradients)
     if not 1 <= per_question <= MAX_HEAD:
         raise ValueError(f"--train_batch_size {args.train_batch_size} / --accumulate_gradients {args.accumulate_gradients}: "
@@ -206,13 +216,38 @@ def pass_schedule(n_batches, gradient_accumulation_steps, questions_per_pass, fa
     return passes
 
 
+def group_length(next_step, gradient_accumulation_steps, lookahead):
+    """How many questions, counting the one of batch step `next_step`, can be retrieved together: up to the first update
+    slot (the weights can change there), at most `lookahead`.  (The sampler cuts it to what the epoch still holds.)"""
+    n = 1
+    while n < lookahead and not is_update_step(next_step + n - 1, gradient_accumulation_steps):
+        n += 1
+    return n
+
+
+def retrieval_groups(n_batches, gradient_accumulation_steps, lookahead, first=1):
+    """[[batch_step of every question of the group]] over ONE epoch of n_batches questions whose batch steps are first ..
+    first + n_batches - 1: the questions the sampler retrieves in one sampling step.  A group is a run of consecutive batch
+    steps that ends at the first update slot, after `lookahead` steps or with the epoch.  Failed retrievals do not move the
+    groups: batch_step counts them, and a failed update slot only means that the weights did not change there, so the cut is
+    merely early."""
+    groups, b, end = [], first, first + n_batches
+    while b < end:
+        n = min(group_length(b, gradient_accumulation_steps, lookahead), end - b)
+        groups.append(list(range(b, b + n)))
+        b += n
+    return groups
+
+
 def reader_fingerprint_extra(args):
-    """The reader command's own fields of the resume fingerprint.  questions_per_pass is a field only when it is not 1, so
-    that the state files of one-question passes keep their fingerprint."""
+    """The reader command's own fields of the resume fingerprint.  questions_per_pass and sampler_lookahead are fields only
+    when they are not 1, so that the state files of one-question passes and one-question sampling keep their fingerprint."""
     extra = {"qa_drop": float(args.qa_drop), "shared_norm": bool(args.shared_norm), "drop_early": bool(args.drop_early),
              "fix_para_encoder": bool(args.fix_para_encoder)}
     if int(getattr(args, "questions_per_pass", 1)) != 1:
         extra["questions_per_pass"] = int(args.questions_per_pass)
+    if int(getattr(args, "sampler_lookahead", 1)) != 1:
+        extra["sampler_lookahead"] = int(args.sampler_lookahead)
     return extra
 
 
@@ -223,6 +258,15 @@ def check_questions_per_pass(saved_fingerprint, questions_per_pass):
     if was != int(questions_per_pass):
         raise SystemExit(f"--resume: the state file was written by a different run: field 'questions_per_pass' is "
                          f"{int(questions_per_pass)!r} now, was {was!r} when the state was saved")
+
+
+def check_sampler_lookahead(saved_fingerprint, sampler_lookahead):
+    """SystemExit when the state file was written at another --sampler-lookahead (a state file without the field was
+    written at 1)."""
+    was = int(saved_fingerprint.get("sampler_lookahead", 1))
+    if was != int(sampler_lookahead):
+        raise SystemExit(f"--resume: the state file was written by a different run: field 'sampler_lookahead' is "
+                         f"{int(sampler_lookahead)!r} now, was {was!r} when the state was saved")
 
 
 def initial_state_dict(cfg, bert_weights):
@@ -290,6 +334,7 @@ def main(argv=None):
             # the flags first: a run of other settings is refused before the data and the model are built
             resume = checkpoint.read_state(checkpoint.resolve_state_path(args.resume))
             check_questions_per_pass(resume["trainer"]["fingerprint"], args.questions_per_pass)
+            check_sampler_lookahead(resume["trainer"]["fingerprint"], args.sampler_lookahead)
             checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp, fields=tuple(fp))
         tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
         logger.info("Loading para db and pretrained index ...")
@@ -368,6 +413,12 @@ def main(argv=None):
             logger.info("--questions-per-pass %d: the questions of an accumulation window share tower passes and one fused "
                         "loss call%s", Q, "" if G > 1 else "; with --gradient_accumulation_steps 1 every question closes its "
                         "window, so every pass holds one question")
+        W = args.sampler_lookahead
+        groups_before = 0       # sampling steps of the run this one resumes
+        if W > 1:
+            logger.info("--sampler-lookahead %d: the sampler retrieves the questions up to the next update slot, at most %d, in "
+                        "one sampling step%s", W, W, "" if G > 1 else "; with --gradient_accumulation_steps 1 every question "
+                        "sits in an update slot, so every group holds one question")
         logger.info("Start training....")
         model.train()
         train_dataloader = OnlineSampler(args.raw_train_data, tokenizer, args.max_query_length, args.max_seq_length, para_db,
@@ -400,6 +451,7 @@ def main(argv=None):
             failed_steps, update_steps = list(saved["failed_steps"]), list(saved["update_steps"])
             failed_per_epoch, resumed_failed = list(saved["failed_per_epoch"]), saved["failed_retrieval"]
             n_passes = int(saved.get("passes", 0))
+            groups_before = int(saved.get("sampler_groups", 0))
             start_epoch, start_position, epoch_started = tr["epoch"], tr["position"], tr["epoch_started"]
             if stop_training and not epoch_started:
                 start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
@@ -422,6 +474,8 @@ def main(argv=None):
                             "permutation": train_dataloader.permutation()}
             if Q != 1:
                 reader_state["passes"] = int(n_passes)
+            if W != 1:
+                reader_state["sampler_groups"] = groups_before + train_dataloader.groups
             ckpt.snapshot(state_path, dict(checkpoint.trainer_state(
                 fingerprint=fp, global_step=global_step, batch_step=batch_step, epoch=next_epoch, position=next_position,
                 epoch_started=started, best=best_em, wait_step=wait_step, stop_training=stop_training,
@@ -453,7 +507,11 @@ def main(argv=None):
             failed_retrieval = resumed_failed if resumed_here else 0
             position = start_position if resumed_here else 0
             open_pass = []
-            for batch in train_dataloader.load(model.retriever, k=args.train_batch_size, **({"start": position} if position else {})):
+            load_args = {"start": position} if position else {}
+            if W != 1:
+                # asked when the sampler has handed out all it retrieved: batch_step + 1 is the step of its next question
+                load_args["lookahead"] = lambda: group_length(batch_step + 1, G, W)
+            for batch in train_dataloader.load(model.retriever, k=args.train_batch_size, **load_args):
                 batch_step += 1
                 position += 1
                 if batch == {}:
@@ -541,6 +599,8 @@ def main(argv=None):
                      seconds=seconds, best_em=best_em, output_dir=args.output_dir, deterministic=bool(args.deterministic),
                      sampler_seconds=dict(train_dataloader.seconds), sampler_transfers=dict(train_dataloader.transfers),
                      questions_per_pass=Q, passes=n_passes)
+        if W != 1:
+            stats.update(sampler_lookahead=W, sampler_groups=groups_before + train_dataloader.groups)
         if args.stop_after_updates > 0:
             stats["stopped_early"] = stopped_early
         if args.digest_every > 0:

@@ -15,6 +15,15 @@ Measures (one JSON line, and --out FILE):
                   kernel alone is the trace's: `rocprofv3 --kernel-trace --stats -- python
                   scripts/dev_reader_train_timing.py --only-collect 200`, a run of its own), against the bytes it moves,
                   k x 256 B in and out, over 8 TB/s
+  --lookahead 1,4,8   the sampling step with the questions retrieved in groups (OnlineSampler.retrieve_many: one tower pass,
+                  one search, one collect launch, one record copy per group) against groups of one, which is
+                  OnlineSampler.retrieve.  The contenders take turns, block of lcm(W) questions by block, in one process, the
+                  first of a block rotating (it pays for the passages the block brings into the cache); a host clock from a
+                  synchronise to a synchronise around the block's groups, their host text work and copies up, divided by
+                  the block's questions; medians over the blocks of --questions questions after --warmup.  Then the
+                  per-stage split of every contender with a synchronise after every stage (passages cached).  Only this is
+                  measured, and --out receives it.  `--only-collect N --lookahead W` retrieves N questions in groups of W
+                  for a trace of the collect kernel.
 Transfer sizes are counted from the shapes: new route (2 + k) x 8 bytes down; parent route k x 8 + k x 512 bytes down and
 k x 516 bytes up.
 """
@@ -89,6 +98,59 @@ def fill_index(index, rows, device):
         index.add_device(torch.randn((min(step, rows - r0), 128), generator=g, device=device, dtype=torch.float16))
 
 
+def time_lookahead(sampler, retriever, group_sizes, args, sync, note):
+    """the sampling step per question with groups of every size of group_sizes (1 is the yardstick: retrieve)"""
+    import math
+    block = math.lcm(*group_sizes)
+
+    def run_block(qas, w):
+        for at in range(0, len(qas), w):
+            group = qas[at:at + w]
+            for qa, retrieved in zip(group, sampler.retrieve_many(retriever, [qa["question"] for qa in group], args.k)):
+                sampler._batch(qa, retrieved)
+        sync()
+
+    times = {w: [] for w in group_sizes}
+    blocks = [sampler.qa_data[at:at + block] for at in range(0, len(sampler.qa_data) - block + 1, block)]
+    warm_blocks = -(-args.warmup // block)
+    for n, qas in enumerate(blocks):
+        turn = n % len(group_sizes)
+        for w in group_sizes[turn:] + group_sizes[:turn]:
+            sync()
+            t0 = time.perf_counter()
+            run_block(qas, w)
+            dt = time.perf_counter() - t0
+            if n >= warm_blocks:
+                times[w].append(dt / len(qas))
+    med = {w: statistics.median(v) * 1e3 for w, v in times.items()}
+    note(f"sampling step per question, medians by group size: {med}")
+
+    # the per-stage split, a synchronise after every stage (passages now cached: host_text is the cached figure)
+    sampler.sync_stages = True
+    split = {}
+    for w in group_sizes:
+        for key in sampler.seconds:
+            sampler.seconds[key] = 0.0
+        n_split = 0
+        for qas in blocks[warm_blocks:]:
+            run_block(qas, w)
+            n_split += len(qas)
+        split[w] = {k: round(v / n_split * 1e3, 3) for k, v in sampler.seconds.items()}
+    sampler.sync_stages = False
+    note("split done")
+    return {
+        "rows": args.rows, "k_search": K_SEARCH, "k": args.k, "gold_rows": args.gold, "block_questions": block,
+        "questions": (len(blocks) - warm_blocks) * block, "blocks": len(blocks) - warm_blocks,
+        "yardstick": "groups of one: OnlineSampler.retrieve, one question at a time",
+        "sampling_ms_per_question_median": {str(w): round(v, 3) for w, v in med.items()},
+        "sampling_ms_per_question_p10_p90": {str(w): [round(float(np.percentile(v, 10)) * 1e3, 3),
+                                                      round(float(np.percentile(v, 90)) * 1e3, 3)] for w, v in times.items()},
+        "questions_per_second_sampler_bound": {str(w): round(1e3 / v, 1) for w, v in med.items()},
+        "split_ms_per_question_synced": {str(w): v for w, v in split.items()},
+        "collect_kernel_us": "not measured here: rocprofv3 --kernel-trace --stats, a run of its own with --only-collect",
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=18_000_000)
@@ -99,8 +161,13 @@ def main():
     ap.add_argument("--k", type=int, default=5)
     ap.add_argument("--steps", type=int, default=40, help="whole training steps to time (0: skip)")
     ap.add_argument("--only-collect", type=int, default=0, help="run this many sampler retrievals and exit (for a trace)")
+    ap.add_argument("--lookahead", type=str, default="", help="comma-separated group sizes, e.g. 1,4,8: time the sampling "
+                    "step in groups against groups of one, and nothing else")
     ap.add_argument("--out", type=str, default="")
     args = ap.parse_args()
+    group_sizes = sorted({int(w) for w in args.lookahead.split(",") if w.strip()} | ({1} if args.lookahead else set()))
+    if any(w < 1 for w in group_sizes):
+        ap.error("--lookahead: group sizes must be >= 1")
     from transformers import BertTokenizer
     from proqa_amd.index import IndexFlatIP
     from proqa_amd.online_retriever import OnlineRetriever
@@ -137,9 +204,20 @@ def main():
         note("model and sampler built")
 
         if args.only_collect:
-            for qa in sampler.qa_data[:args.only_collect]:
-                sampler.retrieve(retriever, qa["question"], args.k)
+            w = max(group_sizes, default=1)
+            todo = sampler.qa_data[:args.only_collect]
+            for at in range(0, len(todo), w):
+                sampler.retrieve_many(retriever, [qa["question"] for qa in todo[at:at + w]], args.k)
             sync()
+            return
+
+        if group_sizes:
+            result = time_lookahead(sampler, retriever, group_sizes, args, sync, note)
+            print(json.dumps(result))
+            if args.out:
+                os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+                with open(args.out, "w") as f:
+                    json.dump(result, f, indent=1)
             return
 
         parent = OnlineRetriever(np.float16, index2paraid=ids_of, device=dev, index=index)
