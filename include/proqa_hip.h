@@ -1198,6 +1198,10 @@ int proqa_microbench_mfma_i8_shape(double ms_target, int zero_operands, int shap
  * v_mfma_i32_32x32x32_i8 + n_valu x v_xad_u32 per wave and trip, four waves per SIMD (the shape of mips_filter_i8's unit);
  * n_valu in {0, 8, 16, 24, 32, 48, 64} */
 int proqa_microbench_mfma_i8_valu(double ms_target, int n_valu, void* stream, double* tops);
+/* the same with the PLACEMENT of the VALU work as an argument, n_valu in {0, 16, 24, 32}: placement 0 = behind the eight
+ * interleaved MFMAs (the loop above); placement 1 = the two chains of four one after the other, behind every MFMA n_valu / 8
+ * instructions of the examination (v_max3_i32 tree, then v_xad_u32) of the OTHER chain's accumulators */
+int proqa_microbench_mfma_i8_valu_placed(double ms_target, int n_valu, int placement, void* stream, double* tops);
 /* microseconds of ONE cooperative launch of `grid` 256-thread workgroups that meet at n_syncs grid-wide barriers
  * (hipLaunchCooperativeKernel + cooperative_groups::grid_group::sync): what fusing dependent small kernels would pay */
 int proqa_microbench_grid_sync(int grid, int n_syncs, void* stream, double* us);

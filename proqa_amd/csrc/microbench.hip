@@ -153,6 +153,83 @@ __global__ __launch_bounds__(512, 2) void mfma_i8_valu_loop(int iters, int* __re
   if (m0 + m1 == 0x12345678) *sink = m0;
 }
 
+// WHERE the VALU work stands (placement 1 of proqa_microbench_mfma_i8_valu_placed; placement 0 is the loop above).  The same
+// 8 MFMAs and NV VALU instructions per wave and trip, but the two chains run ONE AFTER THE OTHER and every MFMA is followed
+// by NV / 8 VALU instructions of the examination of the OTHER accumulator set: the test of one query block in the shadow of
+// the other block's chain.  The examination is the scan's: the maximum tree of max16_i32 (v_max3_i32 / v_max_i32 over 15 or 16
+// accumulators: 7 or 8 instructions) and NV / 2 - 7 or - 8 dependent v_xad_u32 behind it, in plain C++ -- the MFMA -> VALU wait
+// states are the compiler's.  The order is pinned with sched_group_barrier groups (1 MFMA, then NV / 8 VALU).
+__device__ __forceinline__ int imax_mb(int a, int b) { return a > b ? a : b; }
+template <int N>
+__device__ __forceinline__ int max_tree_mb(const i32x16& c) {   // ceil((N - 1) / 2) instructions
+  int v[16];
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] = c[e];
+  int n = N;
+#pragma unroll
+  for (int level = 0; level < 3; ++level) {
+    if (n > 1) {
+      const int g = n / 3, rem = n - 3 * g;
+#pragma unroll
+      for (int e = 0; e < g; ++e) v[e] = imax_mb(imax_mb(v[3 * e], v[3 * e + 1]), v[3 * e + 2]);
+      if (g == 0) {
+        v[0] = imax_mb(v[0], v[1]);
+        n = 1;
+      } else {
+#pragma unroll
+        for (int e = 0; e < rem; ++e) v[g + e] = v[3 * g + e];
+        n = g + rem;
+      }
+    }
+  }
+  return v[0];
+}
+template <int NV>
+__device__ __forceinline__ int examine_mb(const i32x16& c, int m) {   // NV / 2 VALU instructions (one at NV = 0)
+  if constexpr (NV == 0) {
+    return m ^ c[0];
+  } else {
+    constexpr int kTree = NV == 16 ? 15 : 16;
+    const int t = max_tree_mb<kTree>(c);
+#pragma unroll
+    for (int v = 0; v < NV / 2 - kTree / 2; ++v) m = (m ^ (v == 0 ? t : c[v])) + c[15 - v];
+    return m;
+  }
+}
+template <int NV>
+__global__ __launch_bounds__(512, 2) void mfma_i8_valu_staggered_loop(int iters, int* __restrict__ sink) {
+  static_assert(NV == 0 || NV == 16 || NV == 24 || NV == 32, "a whole number of VALU instructions per MFMA gap, a tree per chain");
+  i32x4 a, b;
+  for (int e = 0; e < 4; ++e) {
+    const unsigned h = (threadIdx.x * 2654435761u + e * 40503u + blockIdx.x * 97u);
+    a[e] = (int)(h * 2246822519u);
+    b[e] = (int)(h * 3266489917u + 12345u);
+  }
+  int m0 = 0, m1 = 0;
+  i32x16 c0, c1 = {0};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(b, a, c1, 0, 0, 0);   // (prologue: a first B chain)
+  for (int i = 0; i < iters; ++i) {
+    c0 = i32x16{0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, c0, 0, 0, 0);
+    m1 = examine_mb<NV>(c1, m1);   // (of the previous trip's B chain: under this trip's A chain)
+    asm volatile("" : "+v"(m1));   // (the examination is complete before the chain that overwrites its accumulators)
+    c1 = i32x16{0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(b, a, c1, 0, 0, 0);
+    m0 = examine_mb<NV>(c0, m0);   // (under the B chain)
+    asm volatile("" : "+v"(m0));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+      if (NV > 0) __builtin_amdgcn_sched_group_barrier(0x2, NV / 8, 0);
+    }
+  }
+  m1 = examine_mb<NV>(c1, m1);
+  if (m0 + m1 == 0x12345678) *sink = m0;
+}
+
 // What a grid-wide barrier costs: a cooperative launch of `grid` 256-thread workgroups that meet at n_syncs barriers
 // (cooperative_groups::grid_group::sync, i.e. device-scope release / acquire across the XCDs), touching one cache line each in
 // between -- the price list of a fused small-batch encoder (ABLATIONS R6.12).
@@ -343,6 +420,53 @@ int proqa_microbench_mfma_i8_valu(double ms_target, int n_valu, void* stream, do
   (void)hipFree(sink);
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
+  const double ops = (double)grid * 8 /*waves*/ * (double)iters * 8 /*MFMAs*/ * 2.0 * 32 * 32 * 32;
+  *tops = ops / (best * 1e-3) / 1e12;
+  return PROQA_OK;
+}
+
+// the same rate with the PLACEMENT of the VALU work as an argument: 0 = behind the eight interleaved MFMAs (the loop of
+// proqa_microbench_mfma_i8_valu), 1 = the two chains one after the other, n_valu / 8 instructions of the other chain's
+// examination behind every MFMA (mfma_i8_valu_staggered_loop); n_valu in {0, 16, 24, 32}
+int proqa_microbench_mfma_i8_valu_placed(double ms_target, int n_valu, int placement, void* stream, double* tops) {
+  if (placement == 0) {
+    if (n_valu != 0 && n_valu != 16 && n_valu != 24 && n_valu != 32)
+      return fail(PROQA_EINVAL, "microbench_mfma_i8_valu_placed: n_valu=%d is not built (0, 16, 24, 32)", n_valu);
+    return proqa_microbench_mfma_i8_valu(ms_target, n_valu, stream, tops);
+  }
+  if (!tops || !(ms_target > 0) || placement != 1) return fail(PROQA_EINVAL, "microbench_mfma_i8_valu_placed: bad argument");
+  hipStream_t st = as_stream(stream);
+  hipEvent_t e0, e1;
+  PROQA_HIP(hipEventCreate(&e0));
+  PROQA_HIP(hipEventCreate(&e1));
+  int* sink = nullptr;
+  PROQA_HIP(hipMalloc((void**)&sink, 4));
+  const unsigned grid = (unsigned)device_cu_count() * 2;   // two 8-wave workgroups per CU: four waves per SIMD
+  int iters = (int)(ms_target * 1e-3 * 2.4e9 / (8 * 4 * 32));
+  if (iters < 64) iters = 64;
+  float best = 1e30f;
+  for (int r = 0; r < 4; ++r) {
+    PROQA_HIP(hipEventRecord(e0, st));
+    switch (n_valu) {
+#define PROQA_CASE(N) case N: hipLaunchKernelGGL(mfma_i8_valu_staggered_loop<N>, dim3(grid), dim3(512), 0, st, iters, sink); break;
+      PROQA_CASE(0) PROQA_CASE(16) PROQA_CASE(24) PROQA_CASE(32)
+#undef PROQA_CASE
+      default:
+        (void)hipFree(sink);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        return fail(PROQA_EINVAL, "microbench_mfma_i8_valu_placed: n_valu=%d is not built (0, 16, 24, 32)", n_valu);
+    }
+    PROQA_HIP(hipEventRecord(e1, st));
+    PROQA_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    PROQA_HIP(hipEventElapsedTime(&ms, e0, e1));
+    if (r > 0 && ms < best) best = ms;
+  }
+  (void)hipFree(sink);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  // (the prologue chain and the last examination are outside the count: 4 MFMAs in iters * 8)
   const double ops = (double)grid * 8 /*waves*/ * (double)iters * 8 /*MFMAs*/ * 2.0 * 32 * 32 * 32;
   *tops = ops / (best * 1e-3) / 1e12;
   return PROQA_OK;

@@ -558,8 +558,9 @@ constexpr int kSubBytesI8 = kSubRows * kRowBytesI8;      // 4 KiB: one 32-row MF
 // of this kernel with that tree on the fresh ones read registers the MFMA had not written yet and lost 40 % of its hits).
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int max16_i32(const i32x16& v) {
-  // a tree of depth three (five independent v_max3 first), not a chain of eight dependent ones: the two query blocks' trees
-  // interleave and the wave is back at its MFMAs sooner
+  // a tree of depth three (five independent v_max3 first), not a chain of eight dependent ones: with two query blocks per wave
+  // the tree of one block stands in the gaps of the OTHER block's MFMA chain, three instructions behind every MFMA (the
+  // staggered unit loop of mips_filter_i8<2>), and no instruction there waits for the one before it
   const int m0 = imax(imax(v[0], v[1]), v[2]), m1 = imax(imax(v[3], v[4]), v[5]), m2 = imax(imax(v[6], v[7]), v[8]),
             m3 = imax(imax(v[9], v[10]), v[11]), m4 = imax(imax(v[12], v[13]), v[14]);
   return imax(imax(imax(m0, m1), m2), imax(imax(m3, m4), v[15]));
@@ -625,9 +626,11 @@ __device__ __forceinline__ unsigned column_rows_mask(int rows_left) {
 // Same tiling as mips_filter_f16 -- 8 waves, wave w keeps its QW x 32 queries as MFMA B fragments for its lifetime, the
 // workgroup streams a contiguous chunk of rows through LDS filled by LDS-DMA, each lane owns one query column of the 32x32
 // accumulator so the test is lane-local -- with what the half-size operands change:
-//   * 128 rows are 16 KiB and the LDS image of a workgroup 64 KiB: TWO workgroups per CU, i.e. four waves per SIMD; no second
-//     accumulator set for a software pipeline across units (<= 128 VGPRs), the other waves of the SIMD fill the matrix pipe
-//     while one examines its accumulators or logs a column;
+//   * 128 rows are 16 KiB and the LDS image of a workgroup 64 KiB: TWO workgroups per CU, i.e. four waves per SIMD (<= 128
+//     VGPRs).  QW = 2 runs its two query blocks half a unit apart -- the two accumulator sets it holds anyway are a software
+//     pipeline across units: each block's test stands under the other block's chain of four MFMAs (see the loop; ABLATIONS
+//     R23.2).  QW = 1 has one set and no pipeline: the other waves of the SIMD fill the matrix pipe while one examines its
+//     accumulators or logs a column;
 //   * the image is two PAIRS of 128-row stages (2 x 32 KiB): the barrier at the top of pair p publishes it (every wave's DMA
 //     pieces of the pair have landed: issued one pair -- eight units -- earlier; the only younger vector-memory operations of
 //     the wave are its record stores, COUNTED: memory operations of a wave retire in issue order, so `vmcnt(stores since)`
@@ -658,7 +661,7 @@ __device__ __forceinline__ unsigned column_rows_mask(int rows_left) {
 // The same eight-wave shape for QW = 2: FOUR four-wave workgroups of 256 queries per CU (one 128-row stage per pair, a SIMD
 // holding one wave of each of four barrier domains instead of two of each of two) measured 3 % slower (ABLATIONS R17.1).
 template <int QW, bool SPLIT = false>
-__global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8 a) {
+__global__ __launch_bounds__(kFilterThreads, QW == 2 ? 4 : 2) void mips_filter_i8(FilterArgsI8 a) {
   static_assert(QW == 1 || QW == 2, "8 waves x 32 / 64 queries");
   static_assert(!SPLIT || QW == 1, "row-split launches keep one query block per wave");
   constexpr int NW = kFilterWaves;
@@ -740,8 +743,12 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
         (__attribute__((address_space(3))) char*)(lds + (p & 1) * kPairBytes + wave * (kDmaPerWave * 1024));
     if (__builtin_expect((p + 1) * (kPairUnits * kSubRows) <= n_rows, 1)) {
       const signed char* pair_base = chunk_base + (long long)p * kPairBytes;
+      // (QW = 2 has no registers to spare: kept a scalar, so that the four instructions address `scalar base + 32-bit lane
+      // offset` and not two 64-bit per-lane pointers that run along with the pairs)
+      unsigned lane_off[2] = {dma_off[0], dma_off[1]};
+      if constexpr (QW == 2) asm volatile("" : "+s"(pair_base), "+v"(lane_off[0]), "+v"(lane_off[1]));
 #define PROQA_DMA(e)                                                                                                              \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pair_base + (size_t)dma_off[(e) & 1]),         \
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(pair_base + (size_t)lane_off[(e) & 1]),        \
                                    (__attribute__((address_space(3))) void*)dst, 16, (e) * 1024, QW == 1 ? kDmaAux : 0)
       PROQA_DMA(0);
       PROQA_DMA(1);
@@ -755,7 +762,9 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
         if (row0 < nstages * kStageRows) {
           int rel = row0 + (lane >> 3);
           rel = rel < n_rows ? rel : n_rows - 1;
-          const signed char* src = chunk_base + (long long)rel * kRowBytesI8 + (dma_off[e & 1] & 127u);
+          unsigned in_row = dma_off[e & 1] & 127u;
+          if constexpr (QW == 2) asm volatile("" : "+v"(in_row));   // (born here: no per-lane pointer of it lives through the scan)
+          const signed char* src = chunk_base + (long long)rel * kRowBytesI8 + in_row;
           __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                            (__attribute__((address_space(3))) void*)(dst + e * 1024), 16, 0, QW == 1 ? kDmaAux : 0);
         }
@@ -811,7 +820,108 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
     const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(addr >> 32));
     blk_addr = ((unsigned long long)hi << 32) | lo;
   }
-  for (int p = 0; wave_live && p < npairs; ++p) {
+  if constexpr (QW == 2) {
+    // Two query blocks per wave: the blocks run HALF A UNIT APART, each block's test in the shadow of the other block's MFMA
+    // chain (ABLATIONS R23):
+    //   unit u:  A0 f f f  A1 f f f  A2 f f f  A3 f f f    A chain(u) -> acc0;  f = test of acc1 of unit u - 1
+    //            (branch: block 1's hit path for unit u - 1; acc1 is intact until B0)
+    //            B0 g g g  B1 g g g  B2 g g g  B3 g g g    B chain(u) -> acc1;  g = test of acc0 of unit u, and fragment quad j
+    //                                                      of unit u + 1 re-requested right behind B_j, its last reader
+    //            (branch: block 0's hit path for unit u; acc0 is intact until A0 of unit u + 1)
+    // The pending block-1 test crosses the pair barrier in registers (acc1 and its threshold tb1): the last unit of pair p - 1
+    // is examined under the first A chain of pair p, behind publish() and issue_pair() -- a record it stores is younger than
+    // the DMA pieces just issued and is counted for the NEXT publish(), like any other store -- and the chunk's last unit
+    // behind the loop.  The order inside a half unit is pinned with sched_group_barrier groups (1 MFMA, then 1 ds_read
+    // and 3 VALU); everything that reads an MFMA result stays plain C++ (max16_i32).
+    uint2* list_base[2];   // wave-uniform
+#pragma unroll
+    for (int blk = 0; blk < 2; ++blk)
+      list_base[blk] = (uint2*)a.store.lane_log + lane_list_index(a.store, chunk, q0 + blk * 32, 0) * lane_cap;
+    auto log_column = [&](auto blk_c, const i32x16& acc, float tb, bool hit, int unit) {
+      constexpr int blk = decltype(blk_c)::value;
+      // (the lane's place is worked out here, from an opaque lane number, and not kept in registers across the no-hit path:
+      // the list of query q0 + 32 blk + li and accumulator half `half` is list 2 li + half behind the block's first)
+      int ln = 0;
+      asm volatile("" : "+v"(ln));
+      ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)ln));
+      const int rel = unit * kSubRows + 4 * (ln >> 5);
+      st_cur += 1;   // (entered wave-uniformly: exactly the regions whose store is issued are counted)
+      if (hit) {
+        uint2* list = list_base[blk] + (size_t)(unsigned)(2 * (ln & 31) + (ln >> 5)) * lane_cap;
+        const unsigned pos = lane_n[blk];
+        const unsigned slot = pos < lane_cap ? pos : lane_cap - 1u;   // a full list keeps counting: overflow below
+        unsigned mask = nominee_mask(acc, tb);
+        // (scalar condition: only the chunk's last unit can reach past its rows; the empty asm keeps the region a BRANCH,
+        // see the one-block loop below)
+        if ((unit + 1) * kSubRows > n_rows) {
+          int rows_left = n_rows - rel;
+          asm volatile("" : "+v"(rows_left));
+          mask &= column_rows_mask(rows_left);
+        }
+        list[slot] = make_uint2(row_begin32 + (unsigned)rel, mask);
+        ++lane_n[blk];
+      }
+    };
+    i32x16 acc1 = i32x16{0};
+    float tb1 = __builtin_inff();   // nothing is pending before the chunk's first unit: never a hit
+    int last_unit = 0;
+    for (int p = 0; wave_live && p < npairs; ++p) {
+      const f32x16 bc = *(const __attribute__((address_space(4))) f32x16*)blk_addr;
+      blk_addr += kPairUnits * sizeof(float2);
+      publish();
+      if (p + 1 < npairs) issue_pair(p + 1);
+      const int nunits = (nstages - 2 * p >= 2 ? 2 : 1) * (kStageRows / kSubRows);
+      i32x4 af[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) af[j] = *(const i32x4*)(lds + rd_off[j]);
+#pragma unroll
+      for (int u = 0; u < kPairUnits; ++u) {
+        if (u == 4 && nunits <= 4) break;   // (the chunk's last pair may hold one stage)
+        const int unit = p * kPairUnits + u;
+        // ---- A chain; the test of block 1 of the unit before (of the pair before at u == 0: every pair but the last is whole)
+        i32x16 acc0 = i32x16{0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[j], qf[0][j], acc0, 0, 0, 0);
+        const float tb1_next = block_threshold(thr[1], bc[2 * u], bc[2 * u + 1]);
+        const bool hit1 = (float)max16_i32(acc1) > tb1;   // (|acc| <= 127 * 127 * 128 < 2^24: the conversion is exact)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);   // VALU
+        }
+        if (__builtin_expect(__any(hit1), 0)) log_column(std::integral_constant<int, 1>{}, acc1, tb1, hit1, unit - 1);
+        tb1 = tb1_next;
+        // ---- B chain; the test of block 0 of this unit; the next unit's fragments.  (The pair's last unit has none to read:
+        // the next pair is not published yet.  Unit 3 of a one-stage last pair reads the buffer's second stage, which nobody
+        // writes any more, and the loop ends before anything uses it: no address select, no branch for it.)
+        acc1 = i32x16{0};
+        const int nxt = (u + 1) * kSubBytesI8;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[j], qf[1][j], acc1, 0, 0, 0);
+          if (u + 1 < kPairUnits) af[j] = *(const i32x4*)(lds + rd_off[j] + nxt);
+        }
+        const float tb0 = block_threshold(thr[0], bc[2 * u], bc[2 * u + 1]);
+        const bool hit0 = (float)max16_i32(acc0) > tb0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);   // MFMA
+          if (u + 1 < kPairUnits) __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);   // ds_read
+          __builtin_amdgcn_sched_group_barrier(0x002, 3, 1);   // VALU
+        }
+        if (__builtin_expect(__any(hit0), 0)) log_column(std::integral_constant<int, 0>{}, acc0, tb0, hit0, unit);
+        last_unit = unit;
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) rd_off[j] ^= (unsigned)kPairBytes;   // the other pair buffer
+    }
+    {   // the chunk's last unit, block 1 (a wave without live queries carries tb1 = +inf: no hit)
+      const bool hit1 = (float)max16_i32(acc1) > tb1;
+      if (__builtin_expect(__any(hit1), 0)) log_column(std::integral_constant<int, 1>{}, acc1, tb1, hit1, last_unit);
+    }
+  }
+  // one query block per wave (QW = 1, row-split or not): test behind the unit's four MFMAs
+  for (int p = 0; QW == 1 && wave_live && p < npairs; ++p) {
     const f32x16 bc = *(const __attribute__((address_space(4))) f32x16*)blk_addr;
     blk_addr += kPairUnits * sizeof(float2);
     publish();
@@ -916,13 +1026,21 @@ __global__ __launch_bounds__(kFilterThreads, 2) void mips_filter_i8(FilterArgsI8
       return;
     }
   }
+  int li_end = li, half_end = half;
+  if constexpr (QW == 2) {   // (worked out again, as in log_column: not kept through the scan)
+    int ln = 0;
+    asm volatile("" : "+v"(ln));
+    ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)ln));
+    li_end = ln & 31;
+    half_end = ln >> 5;
+  }
 #pragma unroll
   for (int blk = 0; blk < QW; ++blk) {
     if (lane_n[blk] > lane_cap) {
       *a.overflow = 1u;
       lane_n[blk] = lane_cap;
     }
-    a.store.lane_cnt[lane_cnt_index(a.store, chunk, q0 + blk * 32 + li, half)] = lane_n[blk];
+    a.store.lane_cnt[lane_cnt_index(a.store, chunk, q0 + blk * 32 + li_end, half_end)] = lane_n[blk];
   }
 }
 
