@@ -991,7 +991,11 @@ int proqa_ivf_add_device(proqa_ivf* h, const void* xb_f16_dev, int64_t n, void* 
 /* D float32 [nq, k], I int64 [nq, k] and, if ip_dev != NULL, the inner product q.x of every returned row (float32
  * [nq, k], the bits proqa_index_search reports for that (query, row); -FLT_MAX in empty slots).  xq_dev [nq, 128]
  * PROQA_F16, or PROQA_F32 that fp16 holds (see proqa_ivf_allow_rounding).  The result does not depend on the batch:
- * a query gets the same bits alone.
+ * a query gets the same bits alone.  D = max(fl(|q|^2) - 2 s, 0) with s = fl(q.x - fl(|x|^2 / 2)): the three terms are
+ * rounded separately, so D is within a few ulps of |q|^2 + |x|^2 of the exact distance (tests/ivf_oracle.py states the
+ * bound) and is clamped at 0, which a squared distance never falls below; rows rank by s, D is non-decreasing along a
+ * result.  A row holding +-inf or NaN is never returned (faiss' heap takes d < FLT_MAX only): it counts as scanned, and
+ * the result ends in I = -1, D = +FLT_MAX where fewer than k finite rows were probed.
  * Host round trips: ONE, the per-list query counts of the coarse step (nlist + 2 words), read before the scan is laid
  * out; the scan, merge and outputs stay on `stream`.
  * Workspace, grown on demand and kept for later calls: nq (256 + 12 nprobe' + 4) + 20 nlist + 32 W + 8 k S bytes,

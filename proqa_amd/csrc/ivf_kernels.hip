@@ -15,7 +15,7 @@
 //                the k-th best key so far; a full list is sorted in place (bitonic) and cut to k.  The item writes
 //                k sorted keys per query.
 //   ivf_merge    one workgroup per query: its partial lists (one per probed list and chunk) in batches through an LDS
-//                sort, the winners re-scored for q.x on the same MFMA sequence, D = |q|^2 - 2 s, I = original id.
+//                sort, the winners re-scored for q.x on the same MFMA sequence, D = max(|q|^2 - 2 s, 0), I = original id.
 // Keys are (ord(score) << 32) | (0xFFFFFFFF - id): descending key order = score descending, id ascending.  Every key is a
 // distinct row, so the result is the exact top k of the keys whatever the order in which workgroups ran.
 #include <hip/hip_runtime.h>
@@ -235,7 +235,8 @@ __global__ __launch_bounds__(kScanWaves * 64, 2) void ivf_scan(const char* __res
   const int nqt = min(kIvfTileQ, lt.qoff[w.list + 1] - qb);
   if (tid < kIvfTileQ) {
     s.kth[tid] = 0ull;
-    s.tau[tid] = -__builtin_inff();
+    s.tau[tid] = -3.402823466e38f;   // not -inf: a row holding +-inf or NaN scores -inf or NaN and must never enter (faiss' heap
+                                     // takes d < FLT_MAX only)
     s.cnt[tid] = 0u;
   }
   if (tid == 0) s.over[0] = s.over[1] = 0;
@@ -442,7 +443,9 @@ __global__ __launch_bounds__(kMergeThreads) void ivf_merge(const unsigned long l
     if (j < (int)run) {
       const unsigned long long key = keys[j];
       const float sv = float_from_ord((unsigned)(key >> 32));
-      D[o] = (float)((double)qn2[q] - 2.0 * (double)sv);
+      // clamped at 0: |q|^2, q.x and |x|^2 / 2 are rounded separately, so a row (nearly) equal to the query can come out a few
+      // ulps of |q|^2 below 0, which a squared distance never is; the ranking is by s, and the clamp keeps D monotone
+      D[o] = fmaxf((float)((double)qn2[q] - 2.0 * (double)sv), 0.f);
       I[o] = (long long)(0xFFFFFFFFu - (unsigned)key);
       if (ip) ip[o] = ipv;
     } else {
