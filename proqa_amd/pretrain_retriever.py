@@ -23,8 +23,9 @@ command writes the files, log lines and stats keys it always wrote.
 import json
 import logging
 import os
-import random
 import time
+
+from .trainer import TrainerRun, check_train_args, seed_everything, tensorboard
 
 LAST_RUN_STATS = {}
 
@@ -47,25 +48,10 @@ def model_name(args):
 
 def check_args(args):
     """The refusals, and --do_train implied.  Raises what the reference raises where it raises."""
-    if args.accumulate_gradients < 1:
-        raise ValueError("Invalid accumulate_gradients parameter: {}, should be >= 1".format(args.accumulate_gradients))
-    if args.do_predict and not args.do_train:
-        raise SystemExit("pretrain_retriever.py: --do_predict alone is the dev evaluation of a checkpoint: run "
-                         "train_retriever.py --do_predict --init_checkpoint ...")
-    args.do_train = True
-    if not args.train_file:
-        raise ValueError("If `do_train` is True, then `train_file` must be specified.")
-    if not args.predict_file:
-        raise ValueError("If `do_train` is True, then `predict_file` must be specified.")
-    if args.local_rank != -1:
-        raise SystemExit("pretrain_retriever.py: --local_rank (DistributedDataParallel) is not supported: one GPU per run")
-    if args.no_cuda:
-        raise SystemExit("pretrain_retriever.py: --no_cuda: proqa_amd has no CPU path")
+    check_train_args(args, "pretrain_retriever.py", "the dev evaluation of a checkpoint: run train_retriever.py")
     if ";" in args.init_checkpoint:
         raise SystemExit("pretrain_retriever.py: a ';' list in --init_checkpoint (the reference's ensemble path) is not "
                          "supported; training starts from one checkpoint")
-    if args.gradient_accumulation_steps < 1:
-        raise ValueError(f"Invalid gradient_accumulation_steps parameter: {args.gradient_accumulation_steps}, should be >= 1")
     if int(args.train_batch_size / args.accumulate_gradients) < 1:
         raise ValueError(f"--train_batch_size {args.train_batch_size} / --accumulate_gradients {args.accumulate_gradients} "
                          "leaves no example per batch")
@@ -165,49 +151,10 @@ def parameter_groups(model, weight_decay):
 
 # ---- the command -------------------------------------------------------------------------------------------------------------
 
-class _Losses:
-    """The reference's AverageMeter and its per-batch record without a host read per batch: device scalars queue up and
-    are read together at flush()."""
-
-    def __init__(self):
-        self.pending, self.pending_steps = [], []
-        self.values, self.steps = [], []
-
-    def add(self, loss, global_step):
-        self.pending.append(loss)
-        self.pending_steps.append(global_step)
-
-    def flush(self, tb=None):
-        if self.pending:
-            import torch
-            new = torch.stack(self.pending).cpu().tolist()
-            for value, step in zip(new, self.pending_steps):
-                self.values.append(value)
-                self.steps.append(step)
-                if tb is not None:
-                    tb.add_scalar("batch_train_loss", value, step)
-                    tb.add_scalar("smoothed_train_loss", sum(self.values) / len(self.values), step)
-            self.pending, self.pending_steps = [], []
-
-    @property
-    def avg(self):
-        return sum(self.values) / len(self.values) if self.values else 0.0
-
-
-def _tensorboard(log_dir):
-    try:
-        from torch.utils.tensorboard import SummaryWriter
-    except Exception:
-        return None
-    return SummaryWriter(log_dir)
-
-
 def main(argv=None):
     from .config import get_args
     args = check_args(get_args(argv))
-    import numpy as np
     import torch
-    from . import checkpoint
     from transformers import BertTokenizer
     from .datasets import ClusterDataset, ClusterSampler, ReDataset, ReSampler, ReTextView, ReTokenizeCollate
     from .get_embed import usable_cpus
@@ -219,39 +166,19 @@ def main(argv=None):
     name = model_name(args)
     tb_dir = os.path.join(args.output_dir, "tflogs", name)
     args.output_dir = os.path.join(args.output_dir, name)
-    if os.path.exists(args.output_dir) and os.listdir(args.output_dir):
-        print(f"output directory {args.output_dir} already exists and is not empty.")
-    os.makedirs(args.output_dir, exist_ok=True)
-    handlers = [logging.FileHandler(os.path.join(args.output_dir, "log.txt")), logging.StreamHandler()]
-    for h in handlers:
-        h.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S"))
-        logger.addHandler(h)
-    logger.setLevel(logging.INFO)
-    logger.propagate = False
-    tb = None
-    ckpt = None
-    try:
+    with TrainerRun("pretrain_retriever.py", args, logger) as run:
         logger.info(args)
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: retriever training has no CPU fallback")
         flag_batch_size = args.train_batch_size
         args.train_batch_size = int(args.train_batch_size / args.accumulate_gradients)
-        random.seed(args.seed)
-        np.random.seed(args.seed)
-        torch.manual_seed(args.seed)
-        torch.cuda.manual_seed_all(args.seed)
+        seed_everything(args.seed)
 
         cfg, p_hidden, p_attention = load_model_config(args.bert_model_name)
         if args.max_seq_length > cfg.max_position_embeddings:
             raise ValueError("Cannot use sequence length %d because the BERT model was only trained up to sequence length %d"
                              % (args.max_seq_length, cfg.max_position_embeddings))
-        resume = None
-        fp = checkpoint.fingerprint("pretrain_retriever.py", args, train_batch_size=flag_batch_size,
-                                    hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention)
-        if args.resume:
-            # the flags first: a run of other settings is refused before the data and the model are built
-            resume = checkpoint.read_state(checkpoint.resolve_state_path(args.resume))
-            checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp, fields=tuple(fp))
+        run.begin_resume(train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention)
         tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
 
         # the data first: ClusterDataset reads its folder with a process pool, and nothing forks once the GPU is in use
@@ -291,7 +218,7 @@ def main(argv=None):
         if args.deterministic:
             logger.info("--deterministic: the word-embedding gradient is summed in a fixed order (no atomics); a run is a "
                         "function of the data, the seed and the checkpoint, bit for bit")
-        if resume is None:
+        if not run.resuming:
             if args.init_checkpoint != "":
                 state = torch.load(args.init_checkpoint, map_location="cpu")
             else:
@@ -306,84 +233,34 @@ def main(argv=None):
                                max_grad_norm=args.max_grad_norm, loss_scale="dynamic", half_copies=model.half_weights())
         logger.info("activations and their gradients are fp16 with or without --fp16 (fp32 masters, dynamic loss scale); "
                     "--fp16_opt_level is ignored")
-        tb = _tensorboard(tb_dir)
-
-        global_step = 0      # gradient update step
-        batch_step = 0       # forward batch count
-        best_acc = 0
-        wait_step = 0
-        stop_training = False
-        meter = _Losses()
-        evals = []
-        G = args.gradient_accumulation_steps
+        run.tb = tb = tensorboard(tb_dir)
+        meter, G = run.meter, args.gradient_accumulation_steps
         model.train()
-
-        # checkpoint / resume (proqa_amd/checkpoint.py): nothing of it exists without the four flags
-        ckpt, digests, state_path = None, None, os.path.join(args.output_dir, checkpoint.STATE_FILE)
-        start_epoch, start_position, stopped_early = 0, 0, False
-        if args.save_state or args.digest_every > 0 or resume is not None:
-            fp = checkpoint.fingerprint("pretrain_retriever.py", args, train_batch_size=flag_batch_size,
-                                        hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention,
-                                        n_train=len(train_dataset), order=[i for b in train_batches for i in b], model=model)
-            if resume is not None:
-                checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp)
-            ckpt = checkpoint.TrainerCheckpoint(model, optimizer)
-            digests = checkpoint.DigestLog(ckpt, args.digest_every)
-        if resume is not None:
-            tr = ckpt.load(resume)
-            checkpoint.set_rng_states(tr["rng"])
-            global_step, batch_step, best_acc = tr["global_step"], tr["batch_step"], tr["best"]
-            wait_step, stop_training, evals = tr["wait_step"], tr["stop_training"], list(tr["evals"])
-            meter.values, meter.steps = list(tr["losses"]), list(tr["loss_steps"])
-            digests.entries = [dict(e) for e in tr["state_digests"]]
-            start_epoch, start_position = tr["epoch"], tr["position"]
-            if stop_training and start_position == 0:
-                start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
-            if 0 < args.stop_after_updates <= global_step:
-                raise SystemExit(f"pretrain_retriever.py: --stop-after-updates {args.stop_after_updates}: the state file "
-                                 f"already holds {global_step} updates")
-            logger.info("Resumed from %s: update %d, micro-batch %d, epoch %d position %d.  %s", args.resume, global_step,
-                        batch_step, start_epoch, start_position,
-                        "With --deterministic the run continues bit for bit as the uninterrupted one." if args.deterministic
-                        else "Without --deterministic the word-embedding gradient's atomics make two runs differ, resumed "
-                             "or not.")
-        resume = None       # (the file's flat buffer is not kept)
-
-        def save_state(next_epoch, next_position):
-            """the trainer state as of now, written behind the training stream (the losses are read here: allowed)"""
-            meter.flush(tb)
-            digests.flush(logger)
-            if next_position == len(train_batches):
-                next_epoch, next_position = next_epoch + 1, 0
-            ckpt.snapshot(state_path, dict(checkpoint.trainer_state(
-                fingerprint=fp, global_step=global_step, batch_step=batch_step, epoch=next_epoch, position=next_position,
-                epoch_started=True, best=best_acc, wait_step=wait_step, stop_training=stop_training,
-                dropout=checkpoint.dropout_states(model), losses=meter.values, loss_steps=meter.steps, evals=evals,
-                param_groups=[{"lr": g["lr"], "weight_decay": g["weight_decay"]} for g in optimizer.param_groups],
-                state_digests=digests.entries), rng=checkpoint.rng_states()))
+        if run.attach(model, optimizer, len(train_dataset), lambda: [i for b in train_batches for i in b]) is not None:
+            if run.stop_training and run.start_position == 0:
+                run.start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
+            run.log_resumed("micro-batch")
 
         logger.info("Start training....")
-        t_start = time.perf_counter()
-        for epoch in range(start_epoch, int(args.num_train_epochs)):
-            first = start_position if epoch == start_epoch else 0
+        run.t_start = time.perf_counter()
+        for epoch in range(run.start_epoch, int(args.num_train_epochs)):
+            first = run.start_position if epoch == run.start_epoch else 0
             for position in range(first, len(train_batches)):
                 indices = train_batches[position]
-                batch_step += 1
+                run.batch_step += 1
                 batch = move_to_cuda(tensors(train_texts, indices), device)
                 outputs = model(batch)
                 loss = inbatch_loss(outputs["q"], outputs["c"])
                 if G > 1:
                     loss = loss / G
                 optimizer.scale_loss(loss).backward()
-                meter.add(loss.detach(), global_step)
+                meter.add(loss.detach(), run.global_step)
 
-                if is_update_step(batch_step, G):
+                if is_update_step(run.batch_step, G):
                     optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
                     model.zero_grad()
-                    global_step += 1
-                    if digests is not None:
-                        digests.after_update(global_step)
-                    wrote_last = False
+                    run.after_update()
+                    global_step, wrote_last = run.global_step, False
 
                     if global_step % args.save_checkpoints_steps == 0:
                         meter.flush(tb)
@@ -393,63 +270,26 @@ def main(argv=None):
                         meter.flush(tb)
                         acc = predict(args, model, eval_dataloader(), device, fp16=args.efficient_eval)
                         logger.info("Step %d Train loss %.2f Acc %.2f on epoch=%d" % (global_step, meter.avg, acc * 100, epoch))
-                        evals.append({"step": global_step, "acc": acc, "train_loss_avg": meter.avg})
+                        run.evals.append({"step": global_step, "acc": acc, "train_loss_avg": meter.avg})
                         if tb is not None:
                             tb.add_scalar("dev_acc", acc * 100, global_step)
                         # save most recent model
                         torch.save(model.state_dict(), os.path.join(args.output_dir, "checkpoint_last.pt"))
-                        if best_acc < acc:
+                        best_acc = run.best
+                        if run.note_score(acc):
                             logger.info("Saving model with best  Acc %.2f -> Acc %.2f on epoch=%d" % (best_acc * 100, acc * 100, epoch))
                             torch.save(model.state_dict(), os.path.join(args.output_dir, "checkpoint_best.pt"))
-                            best_acc = acc
-                            wait_step = 0
-                            stop_training = False
-                        else:
-                            wait_step += 1
-                            if wait_step == args.wait_step:
-                                stop_training = True
                         wrote_last = True
 
-                    if args.save_state:
-                        stopped_early = global_step == args.stop_after_updates
-                        if global_step % args.save_checkpoints_steps == 0 or wrote_last or stopped_early:
-                            save_state(epoch, position + 1)
-                        if stopped_early:
-                            break
-            if stop_training or stopped_early:
+                    if run.save_due(also=wrote_last):
+                        # (after an epoch's last micro-batch the next one is the first of the next epoch)
+                        nxt = (epoch, position + 1) if position + 1 < len(train_batches) else (epoch + 1, 0)
+                        run.save_state(*nxt, True)
+                    if run.stopped_early:
+                        break
+            if run.stop_training or run.stopped_early:
                 break
-        meter.flush(tb)
-        if ckpt is not None:
-            digests.flush(logger)
-            ckpt.close()
-        fused = optimizer.state_dict()["fused"]
-        seconds = time.perf_counter() - t_start
-        logger.info("Training finished!")
-
-        stats = LAST_RUN_STATS
-        stats.clear()
-        stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
-                     skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"], seconds=seconds,
-                     best_acc=best_acc, output_dir=args.output_dir, deterministic=bool(args.deterministic))
-        if args.stop_after_updates > 0:
-            stats["stopped_early"] = stopped_early
-        if args.digest_every > 0:
-            stats["state_digests"] = digests.entries
-        if os.environ.get("PROQA_STATS_JSON"):
-            with open(os.environ["PROQA_STATS_JSON"], "w") as f:
-                json.dump(stats, f)
-        return stats
-    finally:
-        if ckpt is not None:
-            try:
-                ckpt.close()
-            except Exception:
-                logger.exception("the last trainer state was not written")
-        if tb is not None:
-            tb.close()
-        for h in handlers:
-            logger.removeHandler(h)
-            h.close()
+        return run.finish(LAST_RUN_STATS, best_acc=run.best)
 
 
 if __name__ == "__main__":

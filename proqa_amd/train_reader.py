@@ -32,13 +32,14 @@ is today's loop, untouched.  A tower pass over W questions need not give the fp1
 W > 1 is a function of (data, seed, checkpoint, W), not the W = 1 run's bits.
 """
 import argparse
+import dataclasses
 import json
 import logging
 import os
-import random
 import time
 
-from .pretrain_retriever import _Losses, _tensorboard, is_update_step, load_bert_weights, load_model_config, parameter_groups
+from .pretrain_retriever import is_update_step, load_bert_weights, load_model_config, parameter_groups
+from .trainer import TrainerRun, check_train_args, seed_everything, tensorboard
 
 LAST_RUN_STATS = {}
 
@@ -146,27 +147,12 @@ def model_name(args):
 def check_args(args):
     """The refusals, and --do_train implied.  Raises what the reference raises where it raises."""
     from .online_sampler import MAX_HEAD
-    if args.accumulate_gradients < 1:
-        raise ValueError("Invalid accumulate_gradients parameter: {}, should be >= 1".format(args.accumulate_gradients))
-    if args.do_predict and not args.do_train:
-        raise SystemExit("train_reader.py: --do_predict alone is the evaluation of a checkpoint: run "
-                         "train_retrieve_qa.py --do_predict --init_checkpoint ...")
-    args.do_train = True
-    if not args.train_file:
-        raise ValueError("If `do_train` is True, then `train_file` must be specified.")
-    if not args.predict_file:
-        raise ValueError("If `do_train` is True, then `predict_file` must be specified.")
-    if args.local_rank != -1:
-        raise SystemExit("train_reader.py: --local_rank (DistributedDataParallel) is not supported: one GPU per run")
-    if args.no_cuda:
-        raise SystemExit("train_reader.py: --no_cuda: proqa_amd has no CPU path")
+    check_train_args(args, "train_reader.py", "the evaluation of a checkpoint: run train_retrieve_qa.py")
     if args.use_spanbert:
         raise SystemExit("train_reader.py: --use-spanbert (a cased reader beside the uncased retriever) is not built")
     if args.separate or args.add_select:
         raise SystemExit("train_reader.py: --separate / --add-select are not built: they need a select term in the loss "
                          "kernels (DESIGN.md section 3h)")
-    if args.gradient_accumulation_steps < 1:
-        raise ValueError(f"Invalid gradient_accumulation_steps parameter: {args.gradient_accumulation_steps}, should be >= 1")
     if args.questions_per_pass < 1:
         raise ValueError(f"Invalid questions_per_pass parameter: {args.questions_per_pass}, should be >= 1")
     if args.sampler_lookahead < 1:
@@ -251,22 +237,13 @@ def reader_fingerprint_extra(args):
     return extra
 
 
-def check_questions_per_pass(saved_fingerprint, questions_per_pass):
-    """SystemExit when the state file was written at another --questions-per-pass (a state file without the field was
-    written at 1, where check_fingerprint would pass over the field)."""
-    was = int(saved_fingerprint.get("questions_per_pass", 1))
-    if was != int(questions_per_pass):
-        raise SystemExit(f"--resume: the state file was written by a different run: field 'questions_per_pass' is "
-                         f"{int(questions_per_pass)!r} now, was {was!r} when the state was saved")
-
-
-def check_sampler_lookahead(saved_fingerprint, sampler_lookahead):
-    """SystemExit when the state file was written at another --sampler-lookahead (a state file without the field was
-    written at 1)."""
-    was = int(saved_fingerprint.get("sampler_lookahead", 1))
-    if was != int(sampler_lookahead):
-        raise SystemExit(f"--resume: the state file was written by a different run: field 'sampler_lookahead' is "
-                         f"{int(sampler_lookahead)!r} now, was {was!r} when the state was saved")
+def check_field_default_1(saved_fingerprint, field, value):
+    """SystemExit when the state file was written at another --questions-per-pass or --sampler-lookahead (`field`: a state
+    file without the field was written at 1, where check_fingerprint would pass over the field)."""
+    was = int(saved_fingerprint.get(field, 1))
+    if was != int(value):
+        raise SystemExit(f"--resume: the state file was written by a different run: field {field!r} is "
+                         f"{int(value)!r} now, was {was!r} when the state was saved")
 
 
 def initial_state_dict(cfg, bert_weights):
@@ -285,12 +262,24 @@ def initial_state_dict(cfg, bert_weights):
 
 # ---- the command -------------------------------------------------------------------------------------------------------------
 
+@dataclasses.dataclass
+class _ReaderCounts:
+    """the command's counters beside TrainerRun's: what the "reader" section of a trainer state holds, and pending_grad"""
+    passes: int = 0
+    pending_grad: bool = False      # a backward has run since the last optimizer step
+    groups_before: int = 0          # sampling steps of the run this one resumes
+    resumed_failed: int = 0         # failed retrievals of the epoch this run resumes in
+    failed_per_epoch: list = dataclasses.field(default_factory=list)
+    failed_steps: list = dataclasses.field(default_factory=list)
+    update_steps: list = dataclasses.field(default_factory=list)
+
+
 def main(argv=None):
     args = check_args(get_args(argv))
-    import numpy as np
     import torch
+    import zlib
     from transformers import BertTokenizer
-    from . import checkpoint, predict_qa
+    from . import predict_qa
     from .index import IndexFlatIP
     from .online_sampler import OnlineSampler
     from .optim import FusedAdamW
@@ -300,19 +289,7 @@ def main(argv=None):
     name = model_name(args)
     tb_dir = os.path.join(args.output_dir, "tflogs", "dense", name)
     args.output_dir = os.path.join(args.output_dir, name)
-    if os.path.exists(args.output_dir) and os.listdir(args.output_dir):
-        print(f"output directory {args.output_dir} already exists and is not empty.")
-    os.makedirs(args.output_dir, exist_ok=True)
-    handlers = [logging.FileHandler(os.path.join(args.output_dir, "log.txt")), logging.StreamHandler()]
-    for h in handlers:
-        h.setFormatter(logging.Formatter("%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S"))
-        logger.addHandler(h)
-    logger.setLevel(logging.INFO)
-    logger.propagate = False
-    tb = None
-    para_db = None
-    ckpt = None
-    try:
+    with TrainerRun("train_reader.py", args, logger) as run:
         logger.info(args)
         if not torch.cuda.is_available():
             raise RuntimeError("no MI355X visible: reader training has no CPU fallback")
@@ -320,25 +297,17 @@ def main(argv=None):
         logger.info("device %s n_gpu %d distributed training %r", device, 1, False)
         flag_batch_size = args.train_batch_size
         args.train_batch_size = int(args.train_batch_size / args.accumulate_gradients)     # passages per question
-        random.seed(args.seed)
-        np.random.seed(args.seed)
-        torch.manual_seed(args.seed)
-        torch.cuda.manual_seed_all(args.seed)
+        seed_everything(args.seed)
 
         cfg, p_hidden, p_attention = load_model_config(args.bert_model_name)
-        resume = None
-        fp_extra = reader_fingerprint_extra(args)
-        fp = checkpoint.fingerprint("train_reader.py", args, train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden,
-                                    attention_probs_dropout_prob=p_attention, extra=fp_extra)
-        if args.resume:
-            # the flags first: a run of other settings is refused before the data and the model are built
-            resume = checkpoint.read_state(checkpoint.resolve_state_path(args.resume))
-            check_questions_per_pass(resume["trainer"]["fingerprint"], args.questions_per_pass)
-            check_sampler_lookahead(resume["trainer"]["fingerprint"], args.sampler_lookahead)
-            checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp, fields=tuple(fp))
+        run.begin_resume(checks=[lambda saved: check_field_default_1(saved, "questions_per_pass", args.questions_per_pass),
+                                 lambda saved: check_field_default_1(saved, "sampler_lookahead", args.sampler_lookahead)],
+                         train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden,
+                         attention_probs_dropout_prob=p_attention, extra=reader_fingerprint_extra(args))
         tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
         logger.info("Loading para db and pretrained index ...")
         para_db = DocDB(args.db_path)
+        run.closing.append(para_db)
         if args.max_seq_length > cfg.max_position_embeddings:
             raise ValueError("Cannot use sequence length %d because the BERT model was only trained up to sequence length %d"
                              % (args.max_seq_length, cfg.max_position_embeddings))
@@ -349,21 +318,18 @@ def main(argv=None):
             index2paraid = json.load(f)
         eval_data = predict_qa.load_qa(args.raw_eval_data)
 
-        if resume is not None:
-            retriever_path, args.retriever_path = args.retriever_path, ""       # the state file carries every master
-            model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
-                                              attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
-            args.retriever_path = retriever_path
-        elif args.init_checkpoint != "":
-            retriever_path, args.retriever_path = args.retriever_path, ""       # the checkpoint carries the retriever
-            model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
-                                              attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
-            args.retriever_path = retriever_path
-            model.load_state_dict(torch.load(args.init_checkpoint, map_location="cpu"))
+        state = None
+        retriever_path = args.retriever_path
+        if run.resuming or args.init_checkpoint != "":
+            args.retriever_path = ""       # the state file carries every master, the checkpoint the retriever
         else:
             state = initial_state_dict(cfg, load_bert_weights(args.bert_model_name))
-            model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
-                                              attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
+        model = TrainableReader.from_args(cfg, args, device, hidden_dropout_prob=p_hidden,
+                                          attention_probs_dropout_prob=p_attention, dropout_seed=args.seed)
+        args.retriever_path = retriever_path
+        if args.init_checkpoint != "":
+            model.load_state_dict(torch.load(args.init_checkpoint, map_location="cpu"))
+        elif state is not None:
             model.load_state_dict(state, strict=False)
         logger.info(f"number of trainable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
         if args.deterministic:
@@ -386,7 +352,8 @@ def main(argv=None):
                                loss_scale="dynamic", half_copies=half_copies)
         logger.info("activations and their gradients are fp16 with or without --fp16 (fp32 masters, dynamic loss scale); "
                     "--fp16_opt_level is ignored")
-        tb = _tensorboard(tb_dir)
+        run.tb = tb = tensorboard(tb_dir)
+        meter, counts = run.meter, _ReaderCounts()
 
         def evaluate():
             """the dev EM of the current weights: BertReader over an fp16 copy of them, on the sampler's index"""
@@ -399,22 +366,11 @@ def main(argv=None):
             return float(em)
 
         args.search, args.reader_batch = "exact", 256        # what predict_qa.evaluate reads beside the shared flags
-        global_step = 0      # gradient update step
-        batch_step = 0       # forward batch count
-        best_em = 0
-        wait_step = 0
-        stop_training = False
-        meter = _Losses()
-        evals, failed_per_epoch, failed_steps, update_steps = [], [], [], []
-        G = args.gradient_accumulation_steps
-        Q = args.questions_per_pass
-        n_passes = 0
+        G, Q, W = args.gradient_accumulation_steps, args.questions_per_pass, args.sampler_lookahead
         if Q > 1:
             logger.info("--questions-per-pass %d: the questions of an accumulation window share tower passes and one fused "
                         "loss call%s", Q, "" if G > 1 else "; with --gradient_accumulation_steps 1 every question closes its "
                         "window, so every pass holds one question")
-        W = args.sampler_lookahead
-        groups_before = 0       # sampling steps of the run this one resumes
         if W > 1:
             logger.info("--sampler-lookahead %d: the sampler retrieves the questions up to the next update slot, at most %d, in "
                         "one sampling step%s", W, W, "" if G > 1 else "; with --gradient_accumulation_steps 1 every question "
@@ -425,68 +381,31 @@ def main(argv=None):
                                          index, index2paraid=index2paraid, matched_para_path=args.matched_para_path,
                                          regex=args.regex, device=device)
 
-        # checkpoint / resume (proqa_amd/checkpoint.py): nothing of it exists without the four flags
-        digests, state_path = None, os.path.join(args.output_dir, checkpoint.STATE_FILE)
-        start_epoch, start_position, epoch_started, resumed_failed = 0, 0, False, 0
-        stopped_early, pending_grad = False, False
-        if args.save_state or args.digest_every > 0 or resume is not None:
-            import zlib
-            fp = checkpoint.fingerprint("train_reader.py", args, train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden,
-                                        attention_probs_dropout_prob=p_attention, extra=fp_extra, n_train=len(train_dataloader),
-                                        order=[zlib.crc32(qa["question"].encode("utf-8")) for qa in train_dataloader.qa_data],
-                                        model=model)
-            if resume is not None:
-                checkpoint.check_fingerprint(resume["trainer"]["fingerprint"], fp)
-            ckpt = checkpoint.TrainerCheckpoint(model, optimizer)
-            digests = checkpoint.DigestLog(ckpt, args.digest_every)
-        if resume is not None:
-            tr = ckpt.load(resume)
+        tr = run.attach(model, optimizer, len(train_dataloader),
+                        lambda: [zlib.crc32(qa["question"].encode("utf-8")) for qa in train_dataloader.qa_data])
+        if tr is not None:
             saved = tr["reader"]
-            train_dataloader.set_permutation(saved["permutation"])
-            checkpoint.set_rng_states(tr["rng"])       # OnlineSampler.shuffle() draws from `random` every epoch
-            global_step, batch_step, best_em = tr["global_step"], tr["batch_step"], tr["best"]
-            wait_step, stop_training, evals = tr["wait_step"], tr["stop_training"], list(tr["evals"])
-            meter.values, meter.steps = list(tr["losses"]), list(tr["loss_steps"])
-            digests.entries = [dict(e) for e in tr["state_digests"]]
-            failed_steps, update_steps = list(saved["failed_steps"]), list(saved["update_steps"])
-            failed_per_epoch, resumed_failed = list(saved["failed_per_epoch"]), saved["failed_retrieval"]
-            n_passes = int(saved.get("passes", 0))
-            groups_before = int(saved.get("sampler_groups", 0))
-            start_epoch, start_position, epoch_started = tr["epoch"], tr["position"], tr["epoch_started"]
-            if stop_training and not epoch_started:
-                start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
-            if 0 < args.stop_after_updates <= global_step:
-                raise SystemExit(f"train_reader.py: --stop-after-updates {args.stop_after_updates}: the state file already "
-                                 f"holds {global_step} updates")
-            logger.info("Resumed from %s: update %d, question %d, epoch %d position %d.  %s", args.resume, global_step,
-                        batch_step, start_epoch, start_position,
-                        "With --deterministic the run continues bit for bit as the uninterrupted one." if args.deterministic
-                        else "Without --deterministic the word-embedding gradient's atomics make two runs differ, resumed "
-                             "or not.")
-        resume = None       # (the file's flat buffer is not kept)
+            train_dataloader.set_permutation(saved["permutation"])      # (shuffle() draws from `random` every epoch)
+            counts = _ReaderCounts(passes=int(saved.get("passes", 0)), groups_before=int(saved.get("sampler_groups", 0)),
+                                   resumed_failed=saved["failed_retrieval"], failed_per_epoch=list(saved["failed_per_epoch"]),
+                                   failed_steps=list(saved["failed_steps"]), update_steps=list(saved["update_steps"]))
+            if run.stop_training and not run.epoch_started:
+                run.start_epoch = int(args.num_train_epochs)        # the straight run left its loop at the end of that epoch
+            run.log_resumed("question")
 
         def save_state(next_epoch, next_position, started, failed_so_far):
-            """the trainer state as of now, written behind the training stream (the losses are read here: allowed)"""
-            meter.flush(tb)
-            digests.flush(logger)
-            reader_state = {"failed_steps": list(failed_steps), "update_steps": list(update_steps),
-                            "failed_per_epoch": list(failed_per_epoch), "failed_retrieval": int(failed_so_far),
+            reader_state = {"failed_steps": list(counts.failed_steps), "update_steps": list(counts.update_steps),
+                            "failed_per_epoch": list(counts.failed_per_epoch), "failed_retrieval": int(failed_so_far),
                             "permutation": train_dataloader.permutation()}
             if Q != 1:
-                reader_state["passes"] = int(n_passes)
+                reader_state["passes"] = int(counts.passes)
             if W != 1:
-                reader_state["sampler_groups"] = groups_before + train_dataloader.groups
-            ckpt.snapshot(state_path, dict(checkpoint.trainer_state(
-                fingerprint=fp, global_step=global_step, batch_step=batch_step, epoch=next_epoch, position=next_position,
-                epoch_started=started, best=best_em, wait_step=wait_step, stop_training=stop_training,
-                dropout=checkpoint.dropout_states(model), losses=meter.values, loss_steps=meter.steps, evals=evals,
-                param_groups=[{"lr": g["lr"], "weight_decay": g["weight_decay"]} for g in optimizer.param_groups],
-                state_digests=digests.entries, reader=reader_state), rng=checkpoint.rng_states()))
+                reader_state["sampler_groups"] = counts.groups_before + train_dataloader.groups
+            run.save_state(next_epoch, next_position, started, reader=reader_state)
 
         def run_pass(batches):
             """forward + backward of the questions of one pass: one forward on the list; every question's loss is divided
             by G and their sum goes through the loss scale"""
-            nonlocal n_passes, pending_grad
             for b in batches:
                 if ON_BATCH is not None:
                     ON_BATCH(b)
@@ -495,133 +414,92 @@ def main(argv=None):
                 losses = losses / G
             optimizer.scale_loss(losses.sum()).backward()
             for i in range(len(batches)):
-                meter.add(losses[i].detach(), global_step)
-            n_passes += 1
-            pending_grad = True
+                meter.add(losses[i].detach(), run.global_step)
+            counts.passes += 1
+            counts.pending_grad = True
 
-        t_start = time.perf_counter()
-        for epoch in range(start_epoch, int(args.num_train_epochs)):
-            resumed_here = epoch_started and epoch == start_epoch       # inside a saved epoch: its shuffle is in the state
+        run.t_start = time.perf_counter()
+        for epoch in range(run.start_epoch, int(args.num_train_epochs)):
+            resumed_here = run.epoch_started and epoch == run.start_epoch       # inside a saved epoch: its shuffle is in the state
             if not resumed_here:
                 train_dataloader.shuffle()
-            failed_retrieval = resumed_failed if resumed_here else 0
-            position = start_position if resumed_here else 0
+            failed_retrieval = counts.resumed_failed if resumed_here else 0
+            position = run.start_position if resumed_here else 0
             open_pass = []
             load_args = {"start": position} if position else {}
             if W != 1:
                 # asked when the sampler has handed out all it retrieved: batch_step + 1 is the step of its next question
-                load_args["lookahead"] = lambda: group_length(batch_step + 1, G, W)
+                load_args["lookahead"] = lambda: group_length(run.batch_step + 1, G, W)
             for batch in train_dataloader.load(model.retriever, k=args.train_batch_size, **load_args):
-                batch_step += 1
+                run.batch_step += 1
                 position += 1
                 if batch == {}:
                     failed_retrieval += 1
-                    failed_steps.append(batch_step)
+                    counts.failed_steps.append(run.batch_step)
                     continue
                 open_pass.append(batch)
-                if not closes_pass(len(open_pass), batch_step, G, Q):
+                if not closes_pass(len(open_pass), run.batch_step, G, Q):
                     continue
                 run_pass(open_pass)
                 open_pass = []
 
-                if is_update_step(batch_step, G):
+                if is_update_step(run.batch_step, G):
                     optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
                     model.zero_grad()
-                    global_step += 1
-                    update_steps.append(batch_step)
-                    pending_grad = False
-                    if digests is not None:
-                        digests.after_update(global_step)
+                    run.after_update()
+                    global_step = run.global_step
+                    counts.update_steps.append(run.batch_step)
+                    counts.pending_grad = False
 
                     if args.eval_period != -1 and global_step % args.eval_period == 0:
                         em = evaluate()
                         logger.info("Step %d Train loss %.2f EM %.2f on epoch=%d" % (global_step, meter.avg, em * 100, epoch))
-                        evals.append({"step": global_step, "epoch": epoch, "em": em, "train_loss_avg": meter.avg})
+                        run.evals.append({"step": global_step, "epoch": epoch, "em": em, "train_loss_avg": meter.avg})
                         if tb is not None:
                             tb.add_scalar("dev_em", em * 100, global_step)
-                        if best_em < em:
+                        best_em = run.best
+                        if run.note_score(em):
                             logger.info("Saving model with best EM: %.2f -> EM %.2f on epoch=%d" % (best_em * 100, em * 100, epoch))
                             torch.save({k: v.cpu() for k, v in model.state_dict().items()},
                                        os.path.join(args.output_dir, "best-model.pt"))
-                            best_em = em
-                            wait_step = 0
-                            stop_training = False
-                        else:
-                            wait_step += 1
-                            if wait_step == args.wait_step:
-                                stop_training = True
 
-                    if args.save_state:
-                        stopped_early = global_step == args.stop_after_updates
-                        if global_step % args.save_checkpoints_steps == 0 or stopped_early:
-                            save_state(epoch, position, True, failed_retrieval)
-                        if stopped_early:
-                            break
-            if stopped_early:
+                    if run.save_due():
+                        save_state(epoch, position, True, failed_retrieval)
+                    if run.stopped_early:
+                        break
+            if run.stopped_early:
                 break
             if open_pass:       # the epoch ended inside a window: its last questions are a pass of their own
                 run_pass(open_pass)
 
             logger.info(f"Failed retrieval: {failed_retrieval}/{len(train_dataloader)} ...")
-            failed_per_epoch.append(failed_retrieval)
+            counts.failed_per_epoch.append(failed_retrieval)
             em = evaluate()
-            evals.append({"step": global_step, "epoch": epoch, "em": em, "train_loss_avg": meter.avg, "end_of_epoch": True})
+            run.evals.append({"step": run.global_step, "epoch": epoch, "em": em, "train_loss_avg": meter.avg,
+                              "end_of_epoch": True})
             if tb is not None:
-                tb.add_scalar("dev_em", em * 100, global_step)
+                tb.add_scalar("dev_em", em * 100, run.global_step)
             logger.info(f"average training loss {meter.avg}")
-            if best_em < em:
+            best_em = run.best
+            if run.note_score(em, patience=False):      # (the reference's rule here: no wait_step count, no stop taken back)
                 logger.info("Saving model with best EM: %.2f  -> %.2f on epoch=%d" % (best_em * 100, em * 100, epoch))
                 torch.save(model.state_dict(), os.path.join(args.output_dir, "best-model.pt"))
-                best_em = em
-                wait_step = 0
             if epoch > 15:
                 logger.info(f"Saving model after epoch {epoch + 1}")
                 torch.save(model.state_dict(), os.path.join(args.output_dir, f"model-{epoch+1}-{em}.pt"))
             if args.save_state:
-                if pending_grad:
+                if counts.pending_grad:
                     logger.info("no trainer state at the end of epoch %d: a gradient is accumulated and waits for its update", epoch)
                 else:
                     save_state(epoch + 1, 0, False, 0)
-            if stop_training:
+            if run.stop_training:
                 break
-        meter.flush(tb)
-        if ckpt is not None:
-            digests.flush(logger)
-            ckpt.close()
-        fused = optimizer.state_dict()["fused"]
-        seconds = time.perf_counter() - t_start
-        logger.info("Training finished!")
-
-        stats = LAST_RUN_STATS
-        stats.clear()
-        stats.update(global_step=global_step, batch_steps=batch_step, losses=meter.values, evals=evals,
-                     failed_retrieval=failed_per_epoch, failed_steps=failed_steps, update_steps=update_steps, skipped_steps=fused["skipped_steps"], loss_scale=fused["loss_scale"],
-                     seconds=seconds, best_em=best_em, output_dir=args.output_dir, deterministic=bool(args.deterministic),
-                     sampler_seconds=dict(train_dataloader.seconds), sampler_transfers=dict(train_dataloader.transfers),
-                     questions_per_pass=Q, passes=n_passes)
+        own = dict(failed_retrieval=counts.failed_per_epoch, failed_steps=counts.failed_steps, update_steps=counts.update_steps,
+                   best_em=run.best, sampler_seconds=dict(train_dataloader.seconds),
+                   sampler_transfers=dict(train_dataloader.transfers), questions_per_pass=Q, passes=counts.passes)
         if W != 1:
-            stats.update(sampler_lookahead=W, sampler_groups=groups_before + train_dataloader.groups)
-        if args.stop_after_updates > 0:
-            stats["stopped_early"] = stopped_early
-        if args.digest_every > 0:
-            stats["state_digests"] = digests.entries
-        if os.environ.get("PROQA_STATS_JSON"):
-            with open(os.environ["PROQA_STATS_JSON"], "w") as f:
-                json.dump(stats, f)
-        return stats
-    finally:
-        if ckpt is not None:
-            try:
-                ckpt.close()
-            except Exception:
-                logger.exception("the last trainer state was not written")
-        if tb is not None:
-            tb.close()
-        if para_db is not None:
-            para_db.close()
-        for h in handlers:
-            logger.removeHandler(h)
-            h.close()
+            own.update(sampler_lookahead=W, sampler_groups=counts.groups_before + train_dataloader.groups)
+        return run.finish(LAST_RUN_STATS, **own)
 
 
 if __name__ == "__main__":

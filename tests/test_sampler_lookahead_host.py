@@ -67,12 +67,12 @@ def test_fingerprint_gains_the_field_only_when_it_is_not_one():
     assert "sampler_lookahead" not in plain
     assert train_reader.reader_fingerprint_extra(_args("--sampler-lookahead", "1")) == plain
     assert train_reader.reader_fingerprint_extra(_args("--sampler-lookahead", "4")) == dict(plain, sampler_lookahead=4)
-    train_reader.check_sampler_lookahead(plain, 1)
-    train_reader.check_sampler_lookahead({"sampler_lookahead": 4}, 4)
+    train_reader.check_field_default_1(plain, "sampler_lookahead", 1)
+    train_reader.check_field_default_1({"sampler_lookahead": 4}, "sampler_lookahead", 4)
     with pytest.raises(SystemExit, match="field 'sampler_lookahead' is 2 now, was 4 when the state was saved"):
-        train_reader.check_sampler_lookahead({"sampler_lookahead": 4}, 2)
+        train_reader.check_field_default_1({"sampler_lookahead": 4}, "sampler_lookahead", 2)
     with pytest.raises(SystemExit, match="field 'sampler_lookahead' is 4 now, was 1 when the state was saved"):
-        train_reader.check_sampler_lookahead(plain, 4)
+        train_reader.check_field_default_1(plain, "sampler_lookahead", 4)
 
 
 def test_the_entry_point_is_declared_and_the_abi_version_stays():

@@ -98,11 +98,11 @@ def test_fingerprint_gains_the_field_only_when_it_is_not_one():
     assert list(fp()) == list(fp("--questions-per-pass", "1")) and "questions_per_pass" not in fp()
     checkpoint.check_fingerprint(fp(), fp())                                        # state files of today keep resuming
     checkpoint.check_fingerprint(fp("--questions-per-pass", "3"), fp("--questions-per-pass", "3"))
-    train_reader.check_questions_per_pass(fp(), 1)
-    train_reader.check_questions_per_pass(fp("--questions-per-pass", "3"), 3)
+    train_reader.check_field_default_1(fp(), "questions_per_pass", 1)
+    train_reader.check_field_default_1(fp("--questions-per-pass", "3"), "questions_per_pass", 3)
     with pytest.raises(SystemExit, match="'questions_per_pass' is 1 now, was 3"):
-        train_reader.check_questions_per_pass(fp("--questions-per-pass", "3"), 1)
+        train_reader.check_field_default_1(fp("--questions-per-pass", "3"), "questions_per_pass", 1)
     with pytest.raises(SystemExit, match="'questions_per_pass' is 3 now, was 1"):
-        train_reader.check_questions_per_pass(fp(), 3)
+        train_reader.check_field_default_1(fp(), "questions_per_pass", 3)
     with pytest.raises(SystemExit, match="'questions_per_pass' is 2 now, was 3"):
         checkpoint.check_fingerprint(fp("--questions-per-pass", "3"), fp("--questions-per-pass", "2"))
