@@ -660,6 +660,34 @@ int proqa_attention_dropout_backward_f16(const void* qkv, const void* qkv_bias, 
 int proqa_inbatch_loss_grad_f16(const void* q, const void* c, const int32_t* target, const float* lse, const float* grad_in,
                                 int nq, int nc, int dim, void* dq, void* dc, void* stream);
 /* ------------------------------------------------------------------------------------
+ * The block-diagonal in-batch objective: M micro-batches of one accumulation window in one call (pretrain_retriever.py
+ * --micro-batches-per-pass).  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive).
+ * q, c [n, 128] fp16 (device, 16-byte aligned); block_offsets: HOST int32 [n_blocks + 1], ascending from 0 to n, read
+ * during the call and handed to the kernels by value.  Block m owns the rows [o_m, o_{m+1}) of BOTH q and c: row i of the
+ * block has its gold at column i and its log-sum-exp runs over the block's columns only, as if
+ * proqa_inbatch_eval_f16(q + o_m, c + o_m, NULL, n_m, n_m, ...) had been called per block.
+ *   lse_out, gold_out  fp32 [n]
+ *   loss_out           fp32 [n_blocks]: mean_i (lse_i - gold_i) over the block's rows, summed in a fixed order
+ * The gradient call takes lse as the first call wrote it and grad_in, DEVICE fp32 [n_blocks], one incoming gradient per
+ * block: d s[i, j] = grad_in[m] / n_m (exp(s[i, j] - lse_i) - [i == j]) inside block m.  Nothing outside a block is read
+ * for it and nothing outside it contributes: a non-finite row or grad_in[m] reaches block m only.  dq, dc [n, 128] fp16.
+ * Bit rule: the block launches run the kernel bodies of proqa_inbatch_eval_f16 / proqa_inbatch_loss_grad_f16 with the
+ * block on a grid dimension and the row pointers offset (a row is 256 bytes: every slice stays 16-byte aligned); no
+ * workgroup or wave holds rows of two blocks, and the block launch never splits a block's columns.  The single eval call
+ * makes no column split when ceil(n_m / 32) <= 16, i.e. n_m <= 512 (a split is no finer than 4 column tiles for each of
+ * the 4 waves: at most ceil(tiles / 16) splits).  For every block with n_m <= 512, lse,
+ * gold, dq and dc therefore carry the BITS of the single calls on the block's slices; a larger block differs from the
+ * single call in the order of its log-sum-exp merges only.  n_blocks == 1 forms every index the single calls form.
+ * Limits: 1 <= n_blocks <= PROQA_INBATCH_MAX_BLOCKS, every block at least one row, n <= 2^24, dim == 128; anything else
+ * is PROQA_EINVAL before the device is touched.  No allocation, no host synchronisation, no atomics: bit-identical from
+ * run to run.
+ * ---------------------------------------------------------------------------------- */
+#define PROQA_INBATCH_MAX_BLOCKS 64
+int proqa_inbatch_loss_blocks_f16(const void* q, const void* c, const int32_t* block_offsets, int n_blocks, int n, int dim,
+                                  float* lse_out, float* gold_out, float* loss_out, void* stream);
+int proqa_inbatch_loss_blocks_grad_f16(const void* q, const void* c, const int32_t* block_offsets, int n_blocks, int n, int dim,
+                                       const float* lse, const float* grad_in, void* dq, void* dc, void* stream);
+/* ------------------------------------------------------------------------------------
  * The reader's training objective (qa/bert_retrieve_qa.py:64-171 with --shared-norm, joint loss and early loss, as
  * qa/train_dense_qa.sh trains it) on the hidden states of B sequences [CLS] q [SEP] p [SEP] of ONE question, and its
  * gradient.  Added WITHOUT a bump of PROQA_ABI_VERSION (purely additive); the rules of the backward block above hold:

@@ -226,6 +226,10 @@ SIGNATURES = {
                                                      c_void_p]),
     "proqa_inbatch_loss_grad_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                             c_void_p, c_void_p]),
+    "proqa_inbatch_loss_blocks_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "proqa_inbatch_loss_blocks_grad_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p]),
     "proqa_reader_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "proqa_reader_loss_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_double,

@@ -59,6 +59,9 @@ EXTRA_FLAGS = (
     ("--embed_dtype", str, "auto"),
     # pretrain_retriever.py: the word-embedding gradient summed in a fixed order (bit-reproducible training)
     ("--deterministic", "flag", False),
+    # pretrain_retriever.py: up to M micro-batches of an accumulation window share one pass per tower and one block-diagonal
+    # loss call (every micro-batch keeps its own in-batch negatives); 1 = one pass per micro-batch, the reference's loop
+    ("--micro-batches-per-pass", int, 1),
 )
 
 # the training commands' checkpoint / resume flags (pretrain_retriever.py and train_reader.py; proqa_amd/checkpoint.py)

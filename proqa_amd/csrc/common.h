@@ -109,6 +109,36 @@ inline T round_up(T a, T b) {
   return ceil_div(a, b) * b;
 }
 
+// The row blocks of the block-diagonal in-batch objective (proqa_inbatch_loss_blocks_f16 and its gradient): block m owns
+// the rows [o[m], o[m + 1]) of q AND of c.  The offsets travel by value in the kernel arguments: no device copy.
+struct BlockOffsets {
+  int o[PROQA_INBATCH_MAX_BLOCKS + 1];
+};
+// The geometry both entry points refuse, before the device is touched; on success `offs` holds the offsets and `widest`
+// the rows of the largest block.
+inline int check_inbatch_blocks(const char* who, const int32_t* block_offsets, int n_blocks, int n, int dim, BlockOffsets* offs,
+                                int* widest) {
+  if (dim != PROQA_EMBED_DIM) return fail(PROQA_EINVAL, "%s: dim=%d, only %d is supported", who, dim, PROQA_EMBED_DIM);
+  if (n_blocks < 1 || n_blocks > PROQA_INBATCH_MAX_BLOCKS)
+    return fail(PROQA_EINVAL, "%s: n_blocks=%d must be in [1, %d]", who, n_blocks, PROQA_INBATCH_MAX_BLOCKS);
+  if (n < n_blocks || n > (1 << 24)) return fail(PROQA_EINVAL, "%s: n=%d rows for %d blocks (at most 2^24 rows)", who, n, n_blocks);
+  if (!block_offsets) return fail(PROQA_EINVAL, "%s: NULL block_offsets", who);
+  if (block_offsets[0] != 0 || block_offsets[n_blocks] != n)
+    return fail(PROQA_EINVAL, "%s: block_offsets must run from 0 to n=%d (they run from %d to %d)", who, n, block_offsets[0],
+                block_offsets[n_blocks]);
+  *offs = BlockOffsets{};
+  *widest = 0;
+  for (int m = 0; m < n_blocks; ++m) {
+    const int rows = block_offsets[m + 1] - block_offsets[m];
+    if (rows < 1 || block_offsets[m + 1] > n)
+      return fail(PROQA_EINVAL, "%s: block %d is [%d, %d): every block needs at least one row inside [0, n]", who, m,
+                  block_offsets[m], block_offsets[m + 1]);
+    offs->o[m + 1] = block_offsets[m + 1];
+    if (rows > *widest) *widest = rows;
+  }
+  return PROQA_OK;
+}
+
 // number of compute units of the current device (256 on MI355X); cached
 int device_cu_count();
 

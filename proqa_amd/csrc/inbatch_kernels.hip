@@ -14,6 +14,10 @@
 // four waves (through LDS) are merged at the end.  When nq is small the column tiles are split over blockIdx.y; each split
 // leaves its merged state in a workspace and inbatch_combine, one thread per row, folds the splits in order.
 //
+// inbatch_eval_blocks (the block-diagonal training objective, proqa_inbatch_loss_blocks_f16): the same body -- one text,
+// inbatch_eval_body.h, included by both kernels -- on the square rectangle of each row block, the block on blockIdx.z and
+// never split; inbatch_block_loss folds a block's lse - gold into its mean in a fixed order.
+//
 // Order of the scores (torch's, pinned by tests/inbatch_oracle.py): a NaN is greater than every number and NaNs are equal
 // to each other; among equal scores the lowest column wins the argmax, and a column equal to the gold beats it only from
 // the left.  A row with a NaN reports max = lse = NaN and the first NaN as its argmax.  lse follows torch.logsumexp: the
@@ -95,112 +99,46 @@ __global__ __launch_bounds__(kWaves * 64) void inbatch_eval(const char* __restri
                                                             int* __restrict__ argmax_out, int* __restrict__ rank_out,
                                                             float* __restrict__ max_out, float* __restrict__ gold_out,
                                                             float* __restrict__ lse_out, Partial* __restrict__ partial) {
-  __shared__ RowState red[kWaves][kTile];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int li = lane & 31, half = lane >> 5;
-  const int row = blockIdx.x * kTile + li;            // this lane's query row; rows >= nq compute on row nq - 1, unwritten
-  const int lrow = row < nq ? row : nq - 1;
-  f16x8 qf[8];
-  load_frags(qf, q + (size_t)lrow * kRowBytes, half);
+#include "inbatch_eval_body.h"
+}
 
-  // gold: A row li = passage target[query li]; the diagonal element (li, li) sits in the lane half (li >> 2) & 1 at
-  // register (li & 3) + 4 * (li >> 3)
-  const int t = target ? target[lrow] : lrow;
-  const int target_ok = t >= 0 && t < nc;
-  float gold;
-  {
-    f16x8 af[8];
-    load_frags(af, c + (size_t)(target_ok ? t : 0) * kRowBytes, half);
-    f32x16 acc = {0};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j], qf[j], acc, 0, 0, 0);
-    const int dreg = (li & 3) + 4 * (li >> 3);
-    float d = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) d = r == dreg ? acc[r] : d;
-    const float other = __shfl_xor(d, 32, 64);
-    gold = ((li >> 2) & 1) == half ? d : other;
-    if (!target_ok) gold = NAN;   // a target outside [0, nc): gold NaN, rank -1
-  }
-  const bool gold_nan = gold != gold;
+// ---- the block-diagonal objective --------------------------------------------------------------------------------------------
+// Block m owns the rows [o[m], o[m + 1]) of q AND of c (BlockOffsets, common.h): its own square rectangle with the gold on
+// the diagonal.
+// grid (query tiles of the largest block, 1, blocks): workgroup (x, ., m) runs inbatch_eval_body on block m's slices as the
+// single launch without a column split does (tiles_per_split = every column tile), so a workgroup never holds rows of two
+// blocks and every lse / gold has the bits of that launch.  Workgroups past a smaller block's last query tile leave at once.
+__global__ __launch_bounds__(kWaves * 64) void inbatch_eval_blocks(const char* __restrict__ q_all, const char* __restrict__ c_all,
+                                                                   BlockOffsets offs, float* __restrict__ gold_all,
+                                                                   float* __restrict__ lse_all) {
+  const int block = blockIdx.z;
+  const int o = offs.o[block], n = offs.o[block + 1] - o;
+  if ((int)blockIdx.x * kTile >= n) return;           // the whole workgroup, before any barrier
+  // what the single launch is handed for this rectangle
+  const char* __restrict__ q = q_all + (size_t)o * kRowBytes;
+  const char* __restrict__ c = c_all + (size_t)o * kRowBytes;
+  const int* __restrict__ target = nullptr;
+  const int nq = n, nc = n, tiles_per_split = (n + kTile - 1) / kTile;
+  int* __restrict__ argmax_out = nullptr;
+  int* __restrict__ rank_out = nullptr;
+  float* __restrict__ max_out = nullptr;
+  float* __restrict__ gold_out = gold_all + o;
+  float* __restrict__ lse_out = lse_all + o;
+  Partial* __restrict__ partial = nullptr;
+#include "inbatch_eval_body.h"
+}
 
-  RowState st = {-INFINITY, INT_MAX, 0, 0.f, INT_MAX};
-  const int n_tiles = (nc + kTile - 1) / kTile;
-  const int tile_lo = blockIdx.y * tiles_per_split;
-  const int tile_hi = min(n_tiles, tile_lo + tiles_per_split);
-  // the next tile's fragments are requested before the current tile's arithmetic
-  f16x8 af[8], nf[8];
-  int tile = tile_lo + wave;
-  if (tile < tile_hi) load_frags(af, c + (size_t)min(tile * kTile + li, nc - 1) * kRowBytes, half);
-  for (; tile < tile_hi; tile += kWaves) {
-    const int next = tile + kWaves;
-    if (next < tile_hi) load_frags(nf, c + (size_t)min(next * kTile + li, nc - 1) * kRowBytes, half);
-    f32x16 acc = {0};
+// loss_out[m] = mean over block m's rows of lse - gold: one wave per block, lane l sums the rows l, l + 64, ... in order,
+// then the lanes fold as a fixed tree.  No atomics: the same bits every run.
+__global__ __launch_bounds__(64) void inbatch_block_loss(const float* __restrict__ lse, const float* __restrict__ gold,
+                                                         BlockOffsets offs, float* __restrict__ loss_out) {
+  const int m = blockIdx.x;
+  const int o = offs.o[m], n = offs.o[m + 1] - o;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += 64) s += lse[o + i] - gold[o + i];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[j], qf[j], acc, 0, 0, 0);
-    // register r of lane (li, half): query li, passage (r & 3) + 8 (r >> 2) + 4 half of the tile -- increasing in r, and
-    // a wave's tiles increase, so a strict > keeps the lowest column of equal scores
-    const int col0 = tile * kTile + 4 * half;
-    float tm = st.m;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int col = col0 + (r & 3) + 8 * (r >> 2);
-      const float s = acc[r];
-      if (col < nc) {
-        const bool s_nan = s != s;
-        if (s_nan) {
-          st.nan = min(st.nan, col);
-        } else if (s > tm || (s == tm && col < st.arg)) {   // (the second clause: the row's first -inf)
-          tm = s;
-          st.arg = col;
-        }
-        const bool gt = s_nan ? !gold_nan : s > gold;
-        const bool eq = s_nan ? gold_nan : s == gold;
-        st.cnt += (col != t && (gt || (eq && col < t))) ? 1 : 0;
-      }
-    }
-    float sum = rescale(st.sum, st.m, tm);
-    const float sh = shift_of(tm);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int col = col0 + (r & 3) + 8 * (r >> 2);
-      const float s = acc[r];
-      if (col < nc && s == s) sum += expf(s - sh);
-    }
-    st.sum = sum;
-    st.m = tm;
-    if (next < tile_hi) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) af[j] = nf[j];
-    }
-  }
-
-  // the other lane half holds the other 16 passages of every tile
-  {
-    RowState o;
-    o.m = __shfl_xor(st.m, 32, 64);
-    o.arg = __shfl_xor(st.arg, 32, 64);
-    o.cnt = __shfl_xor(st.cnt, 32, 64);
-    o.sum = __shfl_xor(st.sum, 32, 64);
-    o.nan = __shfl_xor(st.nan, 32, 64);
-    merge(st, o);
-  }
-  if (half == 0) red[wave][li] = st;
-  __syncthreads();
-  if (threadIdx.x < kTile) {
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) merge(st, red[w][li]);
-    if (row < nq) {
-      if (partial) {
-        Partial p = {st.m, st.sum, st.arg, st.cnt, st.nan};
-        partial[(size_t)blockIdx.y * nq + row] = p;
-        if (blockIdx.y == 0 && gold_out) gold_out[row] = gold;
-      } else {
-        finalize(st, gold, target_ok, row, argmax_out, rank_out, max_out, gold_out, lse_out);
-      }
-    }
-  }
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  if (threadIdx.x == 0) loss_out[m] = s / (float)n;
 }
 
 // one thread per query row folds the splits in column order; gold_out was written by split 0
@@ -310,6 +248,24 @@ int proqa_inbatch_eval_f16(const void* q, const void* c, const int32_t* target, 
   PROQA_HIP(hipEventRecord(ws->done, st));
   ws->last = st;
   ws->used = true;
+  return PROQA_OK;
+}
+
+int proqa_inbatch_loss_blocks_f16(const void* q, const void* c, const int32_t* block_offsets, int n_blocks, int n, int dim,
+                                  float* lse_out, float* gold_out, float* loss_out, void* stream) {
+  BlockOffsets offs;
+  int widest = 0;
+  const int rc = check_inbatch_blocks("inbatch_loss_blocks", block_offsets, n_blocks, n, dim, &offs, &widest);
+  if (rc != PROQA_OK) return rc;
+  if (!q || !c || !lse_out || !gold_out || !loss_out) return fail(PROQA_EINVAL, "inbatch_loss_blocks: NULL argument");
+  if (!aligned16(q) || !aligned16(c)) return fail(PROQA_EINVAL, "inbatch_loss_blocks: q / c must be 16-byte aligned");
+  const hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(inbatch_eval_blocks, dim3((unsigned)ceil_div(widest, kTile), 1u, (unsigned)n_blocks), dim3(kWaves * 64), 0,
+                     st, (const char*)q, (const char*)c, offs, gold_out, lse_out);
+  PROQA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(inbatch_block_loss, dim3((unsigned)n_blocks), dim3(64), 0, st, (const float*)lse_out,
+                     (const float*)gold_out, offs, loss_out);
+  PROQA_LAUNCH_CHECK();
   return PROQA_OK;
 }
 

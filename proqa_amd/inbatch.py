@@ -50,6 +50,43 @@ def inbatch_eval(q, c, target=None):
     return out
 
 
+MAX_BLOCKS = 64      # PROQA_INBATCH_MAX_BLOCKS
+
+
+def block_offsets(block_sizes, n):
+    """block_sizes (M ints >= 1 that sum to n, or an int tensor on the host) -> the host int32 [M + 1] offsets the block
+    entry points take (a ctypes array; the library copies them into the kernel arguments during the call)."""
+    import ctypes
+    sizes = [int(b) for b in (block_sizes.tolist() if torch.is_tensor(block_sizes) else block_sizes)]
+    if not 1 <= len(sizes) <= MAX_BLOCKS:
+        raise ValueError(f"inbatch blocks: {len(sizes)} blocks, must be in [1, {MAX_BLOCKS}]")
+    if any(b < 1 for b in sizes) or sum(sizes) != n:
+        raise ValueError(f"inbatch blocks: block_sizes {sizes} must be positive and sum to the {n} rows")
+    offsets = (ctypes.c_int32 * (len(sizes) + 1))()
+    for m, b in enumerate(sizes):
+        offsets[m + 1] = offsets[m] + b
+    return offsets
+
+
+def inbatch_eval_blocks(q, c, offsets):
+    """The block-diagonal objective's forward (proqa_inbatch_loss_blocks_f16): q, c [n, 128] fp16 device tensors, offsets
+    from block_offsets() -> {'lse': float32 [n], 'gold': float32 [n], 'loss': float32 [M]} on the device: per row the
+    log-sum-exp over its OWN block's columns and the diagonal score, per block mean(lse - gold).  No synchronisation."""
+    lib = _lib.load()
+    q, c = _rows_f16(q, "q"), _rows_f16(c, "c")
+    if q.device != c.device or q.shape != c.shape:
+        raise ValueError(f"inbatch_eval_blocks: q {tuple(q.shape)} on {q.device} and c {tuple(c.shape)} on {c.device} must match")
+    n, dim, M = q.shape[0], q.shape[1], len(offsets) - 1
+    dev = q.device
+    out = {"lse": torch.empty(n, dtype=torch.float32, device=dev), "gold": torch.empty(n, dtype=torch.float32, device=dev),
+           "loss": torch.empty(M, dtype=torch.float32, device=dev)}
+    with torch.cuda.device(dev):
+        _lib.check(lib.proqa_inbatch_loss_blocks_f16(q.data_ptr(), c.data_ptr(), offsets, M, n, dim, out["lse"].data_ptr(),
+                                                     out["gold"].data_ptr(), out["loss"].data_ptr(),
+                                                     _lib.current_stream_ptr()))
+    return out
+
+
 def inbatch_accuracy_and_loss(q, c, target=None):
     """(num_correct, sum over the rows of lse - gold) of one batch as Python numbers: ONE host copy.  num_correct counts
     the rows whose argmax is their target (the reference's `prediction == target`); the second is the batch's

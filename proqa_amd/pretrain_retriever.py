@@ -55,6 +55,8 @@ def check_args(args):
     if int(args.train_batch_size / args.accumulate_gradients) < 1:
         raise ValueError(f"--train_batch_size {args.train_batch_size} / --accumulate_gradients {args.accumulate_gradients} "
                          "leaves no example per batch")
+    if args.micro_batches_per_pass < 1:
+        raise SystemExit(f"pretrain_retriever.py: --micro-batches-per-pass {args.micro_batches_per_pass}: must be at least 1")
     from .config import check_state_flags
     return check_state_flags(args, "pretrain_retriever.py")
 
@@ -75,6 +77,39 @@ def is_update_step(batch_step, gradient_accumulation_steps):
 def update_schedule(n_batches, gradient_accumulation_steps):
     """[batch_step of every optimizer step] over n_batches micro-batches"""
     return [b for b in range(1, n_batches + 1) if is_update_step(b, gradient_accumulation_steps)]
+
+
+def pass_schedule(n_batches, gradient_accumulation_steps, micro_batches_per_pass, first=1):
+    """[[batch_step of every micro-batch of the pass]] over ONE epoch of n_batches micro-batches whose batch steps are
+    first .. first + n_batches - 1 (--micro-batches-per-pass): a pass holds consecutive micro-batches and closes when it
+    holds micro_batches_per_pass of them, at an update step (the optimizer step needs every gradient of its window and the
+    next micro-batch reads the new weights) or with the epoch.  The accumulation rule is the reference's: with G = 8 the
+    first update follows seven micro-batches, so the first window's passes hold seven between them."""
+    passes, open_pass = [], []
+    for b in range(first, first + n_batches):
+        open_pass.append(b)
+        if len(open_pass) >= micro_batches_per_pass or is_update_step(b, gradient_accumulation_steps):
+            passes.append(open_pass)
+            open_pass = []
+    if open_pass:
+        passes.append(open_pass)
+    return passes
+
+
+def fingerprint_extra(args):
+    """The command's own field of the resume fingerprint: micro_batches_per_pass, only when it is not 1, so that the state
+    files of one-micro-batch passes keep their fingerprint (the rule of train_reader.py's questions_per_pass)."""
+    M = int(getattr(args, "micro_batches_per_pass", 1))
+    return {"micro_batches_per_pass": M} if M != 1 else {}
+
+
+def check_micro_batches_per_pass(saved_fingerprint, value):
+    """SystemExit when the state file was written at another --micro-batches-per-pass (a state file without the field was
+    written at 1, where check_fingerprint would pass over the field)."""
+    was = int(saved_fingerprint.get("micro_batches_per_pass", 1))
+    if was != int(value):
+        raise SystemExit(f"--resume: the state file was written by a different run: field 'micro_batches_per_pass' is "
+                         f"{int(value)!r} now, was {was!r} when the state was saved")
 
 
 def load_bert_weights(model_dir):
@@ -160,7 +195,7 @@ def main(argv=None):
     from .get_embed import usable_cpus
     from .optim import FusedAdamW
     from .train_retriever import predict
-    from .trainable import TrainableRetriever, inbatch_loss
+    from .trainable import TrainableRetriever, inbatch_loss, inbatch_loss_blocks
     from .utils import move_to_cuda
 
     name = model_name(args)
@@ -178,7 +213,9 @@ def main(argv=None):
         if args.max_seq_length > cfg.max_position_embeddings:
             raise ValueError("Cannot use sequence length %d because the BERT model was only trained up to sequence length %d"
                              % (args.max_seq_length, cfg.max_position_embeddings))
-        run.begin_resume(train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention)
+        run.begin_resume(checks=[lambda saved: check_micro_batches_per_pass(saved, args.micro_batches_per_pass)],
+                         train_batch_size=flag_batch_size, hidden_dropout_prob=p_hidden, attention_probs_dropout_prob=p_attention,
+                         extra=fingerprint_extra(args))
         tokenizer = BertTokenizer.from_pretrained(args.bert_model_name)
 
         # the data first: ClusterDataset reads its folder with a process pool, and nothing forks once the GPU is in use
@@ -234,7 +271,17 @@ def main(argv=None):
         logger.info("activations and their gradients are fp16 with or without --fp16 (fp32 masters, dynamic loss scale); "
                     "--fp16_opt_level is ignored")
         run.tb = tb = tensorboard(tb_dir)
-        meter, G = run.meter, args.gradient_accumulation_steps
+        meter, G, M = run.meter, args.gradient_accumulation_steps, args.micro_batches_per_pass
+        passes = []                # [[batch_step of every micro-batch of the pass]] of this run
+        if M > 1:
+            if G == 1:
+                logger.info("--micro-batches-per-pass %d with --gradient_accumulation_steps 1: every micro-batch is followed "
+                            "by an update, so every pass holds one micro-batch", M)
+            else:
+                logger.info("--micro-batches-per-pass %d: up to %d micro-batches of an accumulation window share one pass per "
+                            "tower and one block-diagonal loss call; every micro-batch keeps its own in-batch negatives.  "
+                            "The run is a function of (data, seed, checkpoint, M), not the M = 1 run bit for bit", M, M)
+            torch.cuda.reset_peak_memory_stats(device)
         model.train()
         if run.attach(model, optimizer, len(train_dataset), lambda: [i for b in train_batches for i in b]) is not None:
             if run.stop_training and run.start_position == 0:
@@ -244,17 +291,38 @@ def main(argv=None):
         logger.info("Start training....")
         run.t_start = time.perf_counter()
         for epoch in range(run.start_epoch, int(args.num_train_epochs)):
-            first = run.start_position if epoch == run.start_epoch else 0
-            for position in range(first, len(train_batches)):
-                indices = train_batches[position]
-                run.batch_step += 1
-                batch = move_to_cuda(tensors(train_texts, indices), device)
-                outputs = model(batch)
-                loss = inbatch_loss(outputs["q"], outputs["c"])
-                if G > 1:
-                    loss = loss / G
-                optimizer.scale_loss(loss).backward()
-                meter.add(loss.detach(), run.global_step)
+            position = run.start_position if epoch == run.start_epoch else 0
+            while position < len(train_batches):
+                # the pass: consecutive micro-batches up to M, an update step or the end of the epoch (pass_schedule)
+                in_pass = []
+                while True:
+                    run.batch_step += 1
+                    in_pass.append(position)
+                    position += 1
+                    if len(in_pass) >= M or is_update_step(run.batch_step, G) or position == len(train_batches):
+                        break
+                passes.append(list(range(run.batch_step - len(in_pass) + 1, run.batch_step + 1)))
+                position -= 1                                        # of the pass's last micro-batch
+                if len(in_pass) == 1:
+                    batch = move_to_cuda(tensors(train_texts, train_batches[position]), device)
+                    outputs = model(batch)
+                    loss = inbatch_loss(outputs["q"], outputs["c"])
+                    if G > 1:
+                        loss = loss / G
+                    optimizer.scale_loss(loss).backward()
+                    meter.add(loss.detach(), run.global_step)
+                else:
+                    # one collate over the pass's examples, one pass per tower, one loss call, one backward
+                    sizes = [len(train_batches[p]) for p in in_pass]
+                    batch = move_to_cuda(tensors(train_texts, [i for p in in_pass for i in train_batches[p]]), device)
+                    rows = [0]
+                    for n in sizes:
+                        rows.append(rows[-1] + n)
+                    outputs = model([{k: v[rows[m]:rows[m + 1]] for k, v in batch.items()} for m in range(len(sizes))])
+                    losses = inbatch_loss_blocks(outputs["q"], outputs["c"], outputs["block_sizes"]) / G
+                    optimizer.scale_loss(losses.sum()).backward()
+                    for loss in losses.detach().unbind(0):
+                        meter.add(loss, run.global_step)
 
                 if is_update_step(run.batch_step, G):
                     optimizer.step()      # the unscale, the clip of --max_grad_norm and AdamW, in one fused step
@@ -287,9 +355,16 @@ def main(argv=None):
                         run.save_state(*nxt, True)
                     if run.stopped_early:
                         break
+                position += 1
             if run.stop_training or run.stopped_early:
                 break
-        return run.finish(LAST_RUN_STATS, best_acc=run.best)
+        own = {}
+        if M != 1:
+            peak = torch.cuda.max_memory_allocated(device)
+            logger.info("--micro-batches-per-pass %d: %d passes over %d micro-batches, peak device allocation %.2f GiB", M,
+                        len(passes), sum(len(p) for p in passes), peak / 2 ** 30)
+            own = dict(micro_batches_per_pass=M, passes=passes, peak_memory_bytes=int(peak))
+        return run.finish(LAST_RUN_STATS, best_acc=run.best, **own)
 
 
 if __name__ == "__main__":

@@ -39,7 +39,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from ._lib import EMBED_DIM
-from .inbatch import inbatch_eval
+from .inbatch import block_offsets, inbatch_eval, inbatch_eval_blocks
 from .retriever import config_from_dict, tower_keys
 
 _WORKSPACES = {}
@@ -355,6 +355,23 @@ def inbatch_loss_grad(q, c, target, lse, grad_in):
     return dq, dc
 
 
+def inbatch_loss_blocks_grad(q, c, offsets, lse, grad_in):
+    """Gradient of sum_m grad_in[m] * loss_m of the block-diagonal objective (offsets: inbatch.block_offsets(); lse as
+    inbatch_eval_blocks wrote it; grad_in: device fp32 [M]) -> (dq, dc) fp16"""
+    lib = _lib.load()
+    q, c = _f16(q, "q"), _f16(c, "c")
+    M = len(offsets) - 1
+    lse = lse.to(torch.float32).contiguous()
+    g = grad_in.to(device=q.device, dtype=torch.float32).contiguous()
+    if g.shape != (M,) or lse.shape != (q.shape[0],) or c.shape != q.shape:
+        raise ValueError(f"inbatch_loss_blocks_grad: grad_in {tuple(g.shape)} / lse {tuple(lse.shape)} / c {tuple(c.shape)} "
+                         f"do not fit {M} blocks over q {tuple(q.shape)}")
+    dq, dc = torch.empty_like(q), torch.empty_like(c)
+    _call(lib.proqa_inbatch_loss_blocks_grad_f16, q.device, q.data_ptr(), c.data_ptr(), offsets, M, q.shape[0], q.shape[1],
+          lse.data_ptr(), g.data_ptr(), dq.data_ptr(), dc.data_ptr())
+    return dq, dc
+
+
 # ---- autograd: each forward operator with its backward ---------------------------------------------------------------------
 # Parameters enter as the fp32 masters and are cast inside forward, so that their gradients leave as fp32.
 
@@ -524,6 +541,31 @@ def inbatch_loss(q, c, target=None):
     product in memory: the forward value is proqa_inbatch_eval_f16's mean(lse - gold), the backward
     proqa_inbatch_loss_grad_f16.  q, c: fp16 [n, 128] device tensors."""
     return _InBatchLoss.apply(q, c, target)
+
+
+class _InBatchLossBlocks(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, c, offsets):
+        out = inbatch_eval_blocks(q, c, offsets)
+        ctx.save_for_backward(q, c, out["lse"])
+        ctx.offsets = offsets
+        return out["loss"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, c, lse = ctx.saved_tensors
+        dq, dc = inbatch_loss_blocks_grad(q, c, ctx.offsets, lse, grad_out)
+        return dq, dc, None
+
+
+def inbatch_loss_blocks(q, c, block_sizes):
+    """The block-diagonal in-batch objective: block m owns the next block_sizes[m] rows of BOTH q and c [n, 128] fp16, and
+    its loss is CrossEntropyLoss(q_m @ c_m.T, arange) -- what inbatch_loss(q_m, c_m) gives per block, in one call
+    (proqa_inbatch_loss_blocks_f16, backward proqa_inbatch_loss_blocks_grad_f16) -> fp32 [M] with gradients.  One autograd
+    node; torch computes nothing in it.  For a block of at most 512 rows the gradients carry the bits of the per-block
+    calls (proqa_hip.h)."""
+    return _InBatchLossBlocks.apply(q, c, block_offsets(block_sizes, q.shape[0]))
 
 
 # ---- one tower pass, shared by TrainableRetriever and TrainableReader ----------------------------------------------------------
@@ -700,6 +742,19 @@ def _parameter_shapes(cfg, keys=None):
     return shapes
 
 
+def _cat_right_padded(xs):
+    """[B_i, S_i] tensors -> [sum B_i, max S_i], zeros (padding id, mask False) on the right"""
+    S = max(x.shape[1] for x in xs)
+    if all(x.shape[1] == S for x in xs):
+        return torch.cat(xs, 0)
+    out = xs[0].new_zeros((sum(x.shape[0] for x in xs), S))
+    r = 0
+    for x in xs:
+        out[r:r + x.shape[0], :x.shape[1]] = x
+        r += x.shape[0]
+    return out
+
+
 class _Node(torch.nn.Module):
     """A container: the dotted reference names are paths through these."""
 
@@ -817,6 +872,21 @@ class TrainableRetriever(torch.nn.Module):
 
     # -- forward ----------------------------------------------------------------------------
     def forward(self, batch):
+        """batch: one re_collate batch -> {'q', 'c'}; or a LIST of them (the micro-batches of one accumulation window, whose
+        weights are the same) -> {'q', 'c', 'block_sizes'}: ONE pass per tower over all rows, rows in the list's order,
+        block_sizes the rows of every batch (what inbatch_loss_blocks takes).  Batches of different widths are right-padded
+        to the widest on the device: run_tower packs the tokens by cu_seqlens, so the padding costs nothing further.
+        Dropout takes one (seed, call) per tower pass, as for a single batch."""
+        if isinstance(batch, (list, tuple)):
+            if not batch:
+                raise ValueError("TrainableRetriever.forward: an empty list of batches")
+            sizes = [b["input_ids_q"].shape[0] for b in batch]
+            if any(b["input_ids_c"].shape[0] != n or n < 1 for b, n in zip(batch, sizes)):
+                raise ValueError("TrainableRetriever.forward: every batch of a list needs as many paragraphs as questions (>= 1)")
+            out = self.forward({k: _cat_right_padded([b[k] for b in batch])
+                                for k in ("input_ids_q", "input_mask_q", "input_ids_c", "input_mask_c")})
+            out["block_sizes"] = sizes
+            return out
         return {"q": self._tower("bert_q", "proj_q", batch["input_ids_q"], batch["input_mask_q"]),
                 "c": self._tower("bert_c", "proj_c", batch["input_ids_c"], batch["input_mask_c"])}
 

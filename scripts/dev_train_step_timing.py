@@ -3,6 +3,7 @@ batches at the reference's --train_batch_size 640 (retrieval/train_retriever_sin
 
     python scripts/dev_train_step_timing.py [--out DIR] [--batches 640,64] [--steps 5] [--skip-trace] [--dropout P]
                                             [--deterministic] [--half-weights [--accumulate N]]
+                                            [--micro-batches-per-pass 1,4,8 [--accumulate N]]
 
 Three measurements, each in a fresh child process of this script:
   events   forward + backward + zero_grad per step between CUDA events, median of --steps after 2 warm-up steps;
@@ -23,6 +24,13 @@ backward, one FusedAdamW step (clip 2.0, dynamic scale) and zero_grad.  Two modu
 process, one casting its masters in every forward, the other with half_weights() and FusedAdamW(half_copies=...): `events`
 gives step_ms_median_casts / _copies and their ratio; `trace` runs each variant in a traced process of its own and gives
 launches per micro-batch, the adamw_update time and the time of the cast kernels.  The torch baseline is skipped.
+--micro-batches-per-pass 1,4,8 (what pretrain_retriever.py's flag of that name is worth): the step is one accumulation
+window of --accumulate N micro-batches of (first of --batches) / N pairs each, every micro-batch with seeded lengths of its
+own, one FusedAdamW step with the fp16 working copies and zero_grad.  At setting M the window's micro-batches go through
+the towers M at a time: one forward on the list, inbatch_loss_blocks, one backward; M = 1 is the command's route without
+the flag (inbatch_loss per micro-batch), the yardstick.  `events`: the settings take turns step by step in one process,
+device events, medians, peak allocated memory per setting; `trace`: one traced process per setting gives launches and
+kernel time per step.  The torch baseline is skipped.
 Questions have 5-30 tokens (--max_query_length 30), paragraphs 60-220.  Prints one JSON line.
 """
 import argparse
@@ -186,6 +194,93 @@ def child_half(mode, batches, steps, accumulate, variant):
     print("RESULT " + json.dumps(result))
 
 
+def child_passes(mode, pairs, steps, accumulate, settings):
+    """--micro-batches-per-pass: optimizer steps over one window of `accumulate` micro-batches, the settings taking turns"""
+    sys.path.insert(0, ROOT)
+    import torch
+    from proqa_amd.optim import FusedAdamW
+    from proqa_amd.retriever import BERT_BASE
+    from proqa_amd.trainable import TrainableRetriever, inbatch_loss, inbatch_loss_blocks
+    dev = torch.device("cuda", 0)
+    model = TrainableRetriever(BERT_BASE, device=dev, dropout_seed=0)
+    opt = FusedAdamW(model.parameters(), lr=1e-5, max_grad_norm=2.0, loss_scale="dynamic", half_copies=model.half_weights())
+    micro = pairs // accumulate
+    made = [make_batch(micro, 1000 + m, dev) for m in range(accumulate)]
+    window = [b for b, _, _ in made]
+    tokens = sum(sum(lq) + sum(lc) for _, lq, lc in made)
+    times, peak, losses = {M: [] for M in settings}, {M: 0 for M in settings}, {}
+    for step in range((WARMUP + steps) * len(settings)):
+        M = settings[step % len(settings)]
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        seen = []
+        for at in range(0, accumulate, M):
+            group = window[at:at + M]
+            if len(group) == 1:
+                out = model(group[0])
+                loss = inbatch_loss(out["q"], out["c"]) / accumulate
+                opt.scale_loss(loss).backward()
+                seen.append(loss.detach().reshape(1))
+            else:
+                out = model(group)
+                per = inbatch_loss_blocks(out["q"], out["c"], out["block_sizes"]) / accumulate
+                opt.scale_loss(per.sum()).backward()
+                seen.append(per.detach())
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+        t1.record()
+        torch.cuda.synchronize()
+        times[M].append(t0.elapsed_time(t1))
+        peak[M] = max(peak[M], torch.cuda.max_memory_allocated(dev))
+        losses[M] = float(torch.cat(seen).sum())
+    result = {"pairs": pairs, "accumulate": accumulate, "micro_batch_pairs": micro, "tokens_per_step": tokens, "settings": {}}
+    for M in settings:
+        t = times[M][WARMUP:]
+        result["settings"][str(M)] = {"step_ms_median": statistics.median(t), "step_ms_min": min(t), "step_ms_all": t,
+                                      "passes_per_step": -(-accumulate // M), "peak_allocated_bytes": peak[M],
+                                      "window_loss": losses[M]}
+    print("RESULT " + json.dumps(result))
+
+
+def main_passes(args, batches):
+    settings = [int(m) for m in args.micro_batches_per_pass.split(",")]
+    base = [sys.executable, os.path.abspath(__file__), "--batches", str(batches[0]), "--steps", str(args.steps), "--accumulate",
+            str(args.accumulate)]
+
+    def run(mode, which, prefix=()):
+        cmd = list(prefix) + base + ["--child", mode, "--micro-batches-per-pass", ",".join(str(m) for m in which)]
+        out = subprocess.run(cmd, check=True, timeout=900, capture_output=True, text=True).stdout
+        return json.loads([l for l in out.splitlines() if l.startswith("RESULT ")][-1][len("RESULT "):])
+
+    result = {"rocm": open("/opt/rocm/.info/version").read().strip() if os.path.exists("/opt/rocm/.info/version") else "",
+              "events": run("events", settings)}
+    ref = result["events"]["settings"][str(settings[0])]["step_ms_median"]
+    for M in settings:
+        result["events"]["settings"][str(M)]["over_first_setting"] = result["events"]["settings"][str(M)]["step_ms_median"] / ref
+    if not args.skip_trace:
+        prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+        if args.out is None:
+            import tempfile
+            args.out = tempfile.mkdtemp(prefix="train_step_timing_")
+        trace = {}
+        for M in settings:                      # one traced run per setting: its kernels are the whole trace
+            d = os.path.join(args.out, f"passes_{M}")
+            os.makedirs(d, exist_ok=True)
+            run("trace", [M], prefix=[prof, "--kernel-trace", "--output-format", "csv", "-d", d, "--"])
+            rows = read_trace(d)
+            n = WARMUP + args.steps
+            per = {}
+            for name, s, e in rows:
+                per[short(name)] = per.get(short(name), 0) + (e - s)
+            table = {k: v / n / 1e3 for k, v in sorted(per.items(), key=lambda kv: -kv[1])}
+            trace[str(M)] = {"launches_per_step": len(rows) / n, "kernels_us_per_step_total": sum(table.values()),
+                             "kernel_us_per_step": dict(list(table.items())[:12])}
+        result["trace"] = trace
+    print(json.dumps(result))
+
+
 def run_child(mode, args, prefix=(), variant=None):
     cmd = list(prefix) + [sys.executable, os.path.abspath(__file__), "--child", mode, "--batches", args.batches, "--steps", str(args.steps),
                           "--dropout", str(args.dropout)]
@@ -212,8 +307,8 @@ def short(name):
     for tag in ("attention_dropout_bwd_dq", "attention_dropout_bwd_dkv", "attention_dropout_fwd", "bias_residual_layernorm_dropout_bwd",
                 "bias_residual_layernorm_dropout", "dropout_rows",
                 "attention_bwd_dq", "attention_bwd_dkv", "attention_fwd", "bias_residual_layernorm_bwd", "bias_residual_layernorm",
-                "embed_layernorm_bwd", "embed_layernorm", "column_kernel", "reduce_slabs", "bias_gelu_out", "inbatch_loss_grad",
-                "inbatch_eval"):
+                "embed_layernorm_bwd", "embed_layernorm", "column_kernel", "reduce_slabs", "bias_gelu_out",
+                "inbatch_loss_blocks_grad", "inbatch_loss_grad", "inbatch_eval_blocks", "inbatch_block_loss", "inbatch_eval"):
         if tag in name:
             return tag
     return "gemm (library)" if ("Cijk" in name or "gemm" in name.lower()) else "torch: " + name[-60:]
@@ -257,9 +352,16 @@ def main():
     ap.add_argument("--deterministic", action="store_true", help="also time steps with the word-embedding gradient in a fixed order")
     ap.add_argument("--half-weights", action="store_true", help="optimizer steps with and without the fp16 working copies")
     ap.add_argument("--accumulate", type=int, default=1, help="micro-batches per optimizer step (with --half-weights)")
+    ap.add_argument("--micro-batches-per-pass", default=None,
+                    help="e.g. 1,4,8: optimizer steps over one window of --accumulate micro-batches, M per tower pass")
     ap.add_argument("--variant", default=None, choices=["casts", "copies"], help=argparse.SUPPRESS)
     args = ap.parse_args()
     batches = [int(b) for b in args.batches.split(",")]
+    if args.micro_batches_per_pass:
+        settings = [int(m) for m in args.micro_batches_per_pass.split(",")]
+        if args.child:
+            return child_passes(args.child, batches[0], args.steps, args.accumulate, settings)
+        return main_passes(args, batches)
     if args.child and args.half_weights:
         return child_half(args.child, batches, args.steps, args.accumulate, args.variant)
     if args.child:
